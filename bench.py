@@ -17,18 +17,31 @@ torch.distributed.run, before this process touches the GPU); under an external l
 embarrassingly -- every rank renders its own view per step (weak scaling); the only collective is one
 RCCL all-reduce per step of {sum of squared error, value count} for the global PSNR.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what the
+headline needs: set-up, warm-up, the timed steps, --dump-outputs DIR if given, the line.  --full adds
+everything else the benchmark measures, each part separately timed and never part of value:
+  kernels      -- hipEvent-timed duration of every hand-written operator inside the timed steps
   roofline     -- the dominant hand-written kernel's algorithmic bytes / its hipEvent-timed duration
   hash_fwd_roofline -- the same for the hash-grid gather (the kernel the north star's 40 % is about)
   kernels.hash_bwd_nonzero -- the table-gradient kernels timed again on the same points with a
                   gradient whose contributions are all non-zero (the headline's untrained network
                   leaves 90 % of them below the f16 underflow); outside value
-  collective   -- backend / world size / latency of the path's one all-reduce (RCCL, also at N = 1)
+  collective   -- latency of the path's one all-reduce (RCCL, also at N = 1; backend and world size
+                  are in every line)
+  optimizer_step_ms -- fused Adam and torch::optim::Adam per call
+  pixel_tiles_8x8 -- the same views handed over in 8x8 pixel tiles
   c5           -- BASELINE config C5 (hash kernels alone, T = 2^22, F = 8) run once after the
                   headline: roofline (backward), roofline_fwd, cpu_baseline; outside value
   cpu_baseline -- the CPU oracle (a port of the reference arranged as the reference is) timed on
                   this box's host cores on a bounded sample of the same workload (N=1 only).
 --workload c3 / c4 / c5 select the other BASELINE configs (presets of the flags below).
+
+--dump-outputs DIR writes what the timed path computed in its last timed step (rank 0) as
+DIR/<name>.npy, float32 or float64: per chunk the loss, squared-error sum, value and sample counts
+train_step returns, the step's all-reduced error statistics and every parameter gradient; an array of
+more than DUMP_SAMPLE entries is written as a fixed, seeded sample (<name>.sample.npy, with the flat
+indices it took in <name>.sample_index.npy).  Inputs are seeded: the same arguments give the same
+inputs on every run, so two builds can be compared output for output.
 """
 import argparse
 import importlib
@@ -45,13 +58,20 @@ sys.path.insert(0, ROOT)
 
 F32_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md: f32 vector = f32 MFMA peak
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_SAMPLE = 1 << 20     # --dump-outputs: entries kept of a larger array (64 MiB table gradient)
 
 
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps")
+    ap.add_argument("--warmup", type=int, default=1, help="untimed steps before them")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: per-kernel timings and rooflines, "
+                         "the all-reduce latency, optimizer steps, 8x8 pixel tiles, the non-zero-gradient "
+                         "backward, config C5, the CPU baselines and --workload c4's hipGraph batches")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (see the module doc)")
     ap.add_argument("--height", type=int, default=800)
     ap.add_argument("--width", type=int, default=800)
     ap.add_argument("--samples", type=int, default=128)
@@ -60,7 +80,7 @@ def parse_args():
     ap.add_argument("--log2-table", type=int, default=19)
     ap.add_argument("--chunk", type=int, default=65536)
     ap.add_argument("--regime", choices=["dense", "terminating"], default="dense")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: without the CPU baselines")
     ap.add_argument("--cpu-rays", type=int, default=4096)
     ap.add_argument("--n-images", type=int, default=50)
     ap.add_argument("--backend", default="nccl",
@@ -79,8 +99,8 @@ def parse_args():
                          "reports points/s with a roofline object per kernel")
     ap.add_argument("--focal", type=float, default=1111.1, help="fx = fy of the synthetic cameras")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the headline: skip the separately timed extra legs of the default line "
-                         "(8x8 pixel tiles, non-zero-gradient table backward, config C5)")
+                    help="with --full: skip its separately timed extra legs (8x8 pixel tiles, "
+                         "non-zero-gradient table backward, config C5)")
     ap.add_argument("--no-grad-in-place", action="store_true",
                     help="A/B: hand every chunk's table gradient to autograd (a 64 MiB fill and add per "
                          "chunk) instead of adding into feat_pool.grad directly")
@@ -118,7 +138,7 @@ def parse_args():
                          "shape (device-side ray draw + TRAIN render + loss + backward, no host read: "
                          "Renderer deferred_check) as a hipGraph and time K replays next to K eager "
                          "batches; reported as \"graphed_batch\" -- not part of value.  Default: 200 for "
-                         "--workload c4, otherwise off")
+                         "--workload c4 with --full, otherwise off")
     ap.add_argument("--train-iters", type=int, default=0,
                     help="after the headline measurement, time K complete data-parallel TRAINING "
                          "iterations of the reference's own shape (512 random rays per GPU drawn on the "
@@ -332,6 +352,25 @@ def pixel_order(h, w, B, device="cpu"):
     return ids
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each named array as out_dir/<name>.npy in float32 / float64 (counts become
+    float64, exact).  An array of more than DUMP_SAMPLE entries is written as the entries at a fixed,
+    seeded set of flat indices (<name>.sample.npy), the indices next to it (<name>.sample_index.npy)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = torch.as_tensor(a).detach()
+        if a.dtype not in (torch.float32, torch.float64):
+            a = a.double()
+        if a.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(2022)
+            idx = torch.unique(torch.randint(0, a.numel(), (DUMP_SAMPLE,), generator=g))
+            np.save(os.path.join(out_dir, name + ".sample_index.npy"), idx.double().numpy())
+            name, a = name + ".sample", a.reshape(-1)[idx.to(a.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy())
+
+
 def cpu_baseline(args, n_rays):
     """The oracle = CPU port arranged as the reference is (torch-CPU ATen ops + C/OpenMP restatement
     of the 14 CUDA kernels), same workload shape, bounded ray count, SAME RAY ORDER as the GPU arm:
@@ -429,15 +468,17 @@ def dry_run(args, rank, world):
 def run_c5(args, rank, world, dist, dev, pkg):
     """--workload c5: the C5 measurement as its own JSON line."""
     out = c5_measure(args, rank, world, dist, dev, pkg, args.steps, args.warmup,
-                     cpu_points=0 if (world > 1 or args.no_cpu_baseline) else 1 << 20)
+                     cpu_points=1 << 20 if (args.full and world == 1 and not args.no_cpu_baseline) else 0,
+                     dump_dir=args.dump_outputs)
     if rank == 0:
         print(json.dumps(out), flush=True)
 
 
-def c5_measure(args, rank, world, dist, dev, pkg, steps, warmup, cpu_points):
+def c5_measure(args, rank, world, dist, dev, pkg, steps, warmup, cpu_points, dump_dir=None):
     """BASELINE config C5: hash-grid encode forward + table-gradient backward through the C ABI,
     inputs resident in HBM; one step = both kernels over the whole point set.  Returns the JSON
-    object on rank 0 (None elsewhere)."""
+    object on rank 0 (None elsewhere).  dump_dir: the encoding of the last step and the table
+    gradient (summed over all steps: nothing zeroes it in between) as --dump-outputs writes them."""
     capi = pkg.capi
     L, F, log2_T = 16, 8, 22
     T, C, n = 1 << log2_T, 16 * 8, args.c5_points
@@ -493,6 +534,8 @@ def c5_measure(args, rank, world, dist, dev, pkg, steps, warmup, cpu_points):
     if dist is not None:
         dist.all_reduce(t_max, op=dist.ReduceOp.MAX)
     elapsed = float(t_max.item())
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, {"hash_fwd.enc": enc, "hash_bwd.table_grad": tg})
     del ws, enc, grad, tg, table16, pts
     if rank != 0:
         return None
@@ -788,6 +831,8 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # decided before any torch.cuda call: the ranks are fresh child processes
         raise SystemExit(launch_ranks(args, sys.argv[1:]))
@@ -861,7 +906,8 @@ def main():
 
     in_flight = []   # the previous step's all-reduce: (error statistics, work handle)
 
-    def run_step(view, timed=False):
+    def run_step(view, keep=None):
+        """keep: a list that receives train_step's (loss, sq_err, n_values, n_samples) per chunk."""
         o, d, gt, emb = view
         ren.zero_grad()
         sq = None
@@ -870,6 +916,8 @@ def main():
         for lo in range(0, n_rays_view, args.chunk):
             hi = min(lo + args.chunk, n_rays_view)
             loss, sq_err, nv, ns = ren.train_step(o[lo:hi], d[lo:hi], emb[lo:hi], gt[lo:hi], 0.0)
+            if keep is not None:
+                keep.append((loss, sq_err, nv, ns))
             sq = sq_err.double() if sq is None else sq + sq_err.double()
             n_val += nv
             n_samples += ns
@@ -895,24 +943,28 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed_leg(views, n_warm):
+    def timed_leg(views, n_warm, last_step=None):
         """n_warm untimed steps, then the rest timed between barrier + synchronize on both sides;
-        returns (elapsed seconds = max over ranks, samples, last error statistics, kernel timings)."""
+        returns (elapsed seconds = max over ranks, samples, last error statistics, kernel timings:
+        --full only, else {}).  last_step: a list that receives the last step's chunk outputs."""
         for s in range(n_warm):
             run_step(views[s])
         barrier()
-        H.kernel_timer_enable(True)
-        H.kernel_timer_collect()
+        if args.full:
+            H.kernel_timer_enable(True)
+            H.kernel_timer_collect()
         t0 = time.perf_counter()
         n_samples_total = 0
         stat = None
         for s in range(n_warm, len(views)):
-            stat, ns = run_step(views[s], timed=True)
+            stat, ns = run_step(views[s], keep=last_step if s == len(views) - 1 else None)
             n_samples_total += ns
         barrier()
         elapsed = time.perf_counter() - t0
-        H.kernel_timer_enable(False)
-        timings = H.kernel_timer_collect()
+        timings = {}
+        if args.full:
+            H.kernel_timer_enable(False)
+            timings = H.kernel_timer_collect()
         t_max = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         if dist is not None:
             dist.all_reduce(t_max, op=dist.ReduceOp.MAX)
@@ -924,10 +976,19 @@ def main():
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import bin_stats
         bin_counters = bin_stats.enable(pkg.capi.lib().cdll, dev)
-    elapsed, n_samples_total, stat, timings = timed_leg(views, args.warmup)
+    last_step = [] if args.dump_outputs else None
+    elapsed, n_samples_total, stat, timings = timed_leg(views, args.warmup, last_step)
     if bin_counters is not None:
         bin_stats.report(pkg.capi.lib().cdll, bin_counters, L, out=sys.stderr)
-    if dist is not None:
+    if last_step is not None and rank == 0:
+        outs = {"loss": torch.stack([c[0].reshape(()) for c in last_step]),
+                "sq_err_sum": torch.stack([c[1].reshape(()) for c in last_step]),
+                "n_values": torch.tensor([c[2] for c in last_step], dtype=torch.float64),
+                "n_samples": torch.tensor([c[3] for c in last_step], dtype=torch.float64),
+                "error_stats": stat}
+        outs.update({"grad." + k: g for k, g in sorted(ren.grads().items()) if g is not None})
+        dump_outputs(args.dump_outputs, outs)
+    if args.full and dist is not None:
         # latency of the path's collective, measured after the timed region: blocking calls on the
         # same 16-byte payload, host-timed between synchronizes
         probe = torch.zeros(2, device=dev, dtype=torch.float64)
@@ -948,7 +1009,7 @@ def main():
 
     # ---- extras: separately timed, never part of value ---------------------------------------------
     extras = {}
-    want_extras = not args.no_extras and args.workload in ("render", "c2") and args.rays == 0
+    want_extras = args.full and not args.no_extras and args.workload in ("render", "c2") and args.rays == 0
     if want_extras and tiles_active(args, 8) and args.pixel_tiles != 8:
         # the same views handed over in 8x8 pixel tiles (the Renderer's own traversal in render_image)
         n_w, n_t = min(args.warmup, 2), min(args.steps, 5)
@@ -967,7 +1028,7 @@ def main():
 
     # optimiser step: outside the headline (BASELINE.md excludes it) but reported next to it
     opt_ms = {}
-    for name in ("make_fused_adam", "make_adam"):
+    for name in ("make_fused_adam", "make_adam") if args.full else ():
         opt = getattr(ren, name)(1e-2)
         opt.step()                       # first step allocates the moment buffers
         torch.cuda.synchronize()
@@ -993,7 +1054,7 @@ def main():
                       "note": "%dx%d, %d samples/ray, VALIDATE (no jitter), forward only, one GPU; "
                               "not part of value" % (args.height, args.width, S)}
     graphed = None
-    n_graph = args.graph_iters if args.graph_iters >= 0 else (200 if args.workload == "c4" else 0)
+    n_graph = args.graph_iters if args.graph_iters >= 0 else (200 if args.workload == "c4" and args.full else 0)
     if n_graph > 0 and rank == 0:
         graphed = time_graphed_batches(args, H, dev, poses, intr, n_graph)
     train_iter = None
@@ -1079,13 +1140,16 @@ def main():
             "kernel_options": args.option,
             "psnr_vs_random_gt": psnr,
             "collective": collective,
-            "optimizer_step_ms": {"fused_adam_with_f16_shadow": opt_ms["make_fused_adam"],
-                                  "torch_optim_adam": opt_ms["make_adam"],
-                                  "note": "per call, not part of value (BASELINE.md section 2)"},
-            "roofline": roofline_of(dom) if dom else None,
-            "hash_fwd_roofline": roofline_of("hash_fwd"),
-            "kernels": kernels,
         }
+        if args.full:
+            out.update({
+                "optimizer_step_ms": {"fused_adam_with_f16_shadow": opt_ms["make_fused_adam"],
+                                      "torch_optim_adam": opt_ms["make_adam"],
+                                      "note": "per call, not part of value (BASELINE.md section 2)"},
+                "roofline": roofline_of(dom) if dom else None,
+                "hash_fwd_roofline": roofline_of("hash_fwd"),
+                "kernels": kernels,
+            })
         out.update(extras)
         if c5 is not None:
             out["c5"] = c5
@@ -1095,7 +1159,7 @@ def main():
             out["train_iteration"] = train_iter
         if render_img is not None:
             out["render_image"] = render_img
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args, args.cpu_rays)
                 out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]

@@ -38,7 +38,7 @@ def test_bench_two_ranks_share_one_gpu(dev):
     res = subprocess.run(
         [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu",
          "--steps", "1", "--warmup", "1", "--rays", "2048", "--samples", "64", "--levels", "4",
-         "--chunk", "2048", "--no-cpu-baseline"],
+         "--chunk", "2048", "--no-cpu-baseline", "--full"],
         env=_clean_env(), capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [json.loads(l) for l in res.stdout.splitlines() if l.startswith("{")]

@@ -27,7 +27,7 @@ prof() {  # prof NAME KIND(stats|pmc COUNTER) -- bench args
 }
 bench() {  # bench NAME args
   local name=$1; shift
-  timeout -k 10 500 python3 bench.py "$@" > "$out/$name.log" 2>&1
+  timeout -k 10 500 python3 bench.py --full "$@" > "$out/$name.log" 2>&1
   grep '^{"metric"' "$out/$name.log" | tail -1 > "$out/$name.json"
   python3 -c "import json,sys; d=json.load(open('$out/$name.json')); print('$name', d['value'], d['unit'], d['ms_per_step'])"
 }
