@@ -107,6 +107,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     py::arg("images") = Tensor());
   m.def("train_loss", &f2n::train_loss, py::arg("colors"), py::arg("gt_colors"), py::arg("var"),
         py::arg("var_loss_weight"));
+  m.def("ray_order", &f2n::ray_order, "caller indices of rays_d sorted into pixel-compact bundles");
   m.def("manual_seed", [](uint64_t s) { torch::manual_seed(s); });
   m.def("kernel_timer_enable", &f2n::kernel_timer_enable);
   m.def("kernel_timer_collect", []() {

@@ -127,135 +127,12 @@ RenderResult Renderer::render_fused(
   const bool dense = dense_ok && (options_.dense_first_pass == 1 ||
                                   (options_.dense_first_pass < 0 && last_kept_fraction_ > 0.4f));
   if (dense) {
-    // Dense first pass: every sample is encoded once (level-major kernel), the keep-prefix comes
-    // from that encoding, and the shading pass reuses it -- same counts as the march, bit for bit.
-    SampleResultFlex all = pts_sampler_->get_samples(rays_o, rays_d, noise);
-    const int64_t n_all = all.pts.size(0);
-    SampleResultFlex kept;
-    Tensor enc_kept_cm, contracted_kept, contracted_all, enc_all_cm;
-    Tensor total = torch::empty({1}, iopt);
-    {
-      torch::NoGradGuard no_grad;
-      // all.pts is the dense [n_rays, S] grid of the sampler: ray-tile mapping of the encode
-      enc_all_cm = field.encode(all.pts, S, &contracted_all).t();  // [C, n_all] contiguous storage
-      TORCH_CHECK(enc_all_cm.is_contiguous(), "encode() must return channel-major storage");
-    }
-    // The number of survivors sizes everything downstream, so the host has to read it: one blocking
-    // read per chunk.  When the previous chunk kept every sample the next one most likely does too
-    // (no density yet, or validation of empty space), so that case is tried first and for free: the
-    // shading pass is run over ALL samples (fresh buffers, nothing observable), the density logits
-    // it produces anyway are summed per ray (f2n_density_margin: 67 MB instead of the 1 GB encoding
-    // the exact scan reads) and a flag says whether some ray comes within a factor e^0.5 of the
-    // early-stop threshold.  Flag clear = the exact scan would keep everything too (its logits
-    // differ from these in the last bits only): the guess IS the result, and neither the scan
-    // (0.22 ms per 8.4 M samples) nor an idle GPU across the read (the flag travels while
-    // compositing runs) was paid.  Flag set = drop the guess, run the exact scan, compact.
-    //   Small chunks (the 512-ray training batch) keep the exact scan instead -- there it costs
-    // 20 us, less than the GPU would idle while the host waits for a flag that only exists after
-    // the shading pass -- and hide ITS read-back behind the same guess (further down).
-    if (options_.deferred_check && options_.fused_shade) {
-      // no host read: exact scan -> device-side "kept fewer than shaded" flag, all samples shaded
-      torch::NoGradGuard no_grad;
-      auto head = field.density_head();
-      Tensor counts = torch::empty({n_rays}, iopt);
-      {
-        f2n::ScopedKernelTimer timer("density_scan", stream, (double)n_rays);
-        f2n::check(
-          f2n_density_scan(
-            enc_all_cm.data_ptr<float>(), (int)C, all.dt.data_ptr<float>(),
-            head.first.data_ptr<float>(), head.second.data_ptr<float>(),
-            counts.data_ptr<int32_t>(), n_rays, S, options_.early_stop_trans, 3.f, stream),
-          "f2n_density_scan");
-      }
-      Tensor scratch_bounds = torch::empty({n_rays, 2}, iopt);
-      f2n::check(
-        f2n_bounds_from_counts(
-          counts.data_ptr<int32_t>(), scratch_bounds.data_ptr<int32_t>(), total.data_ptr<int32_t>(),
-          n_rays, stream),
-        "f2n_bounds_from_counts");
-      if (!deferred_bad_.defined()) deferred_bad_ = torch::zeros({1}, iopt);
-      deferred_bad_.add_(total.ne(n_all).to(torch::kInt32));
-      last_n_samples_ = n_all;
-      last_kept_fraction_ = 1.f;
-    }
-    if (options_.deferred_check && options_.fused_shade)
-      return shade_and_composite(all, emb_idx, mode, bg_color, enc_all_cm, contracted_all);
-    const bool may_guess = options_.speculate_dense && last_kept_fraction_ >= 1.f && n_all > 0;
-    const int64_t kMarginMinSamples = options_.margin_min_samples;
-    if (may_guess && n_all >= kMarginMinSamples) {
-      Tensor near_threshold = torch::zeros({1}, iopt);
-      RenderResult guess = shade_and_composite(
-        all, emb_idx, mode, bg_color, enc_all_cm, contracted_all, &near_threshold, S);
-      if (survivors_.wait() == 0) {
-        last_n_samples_ = n_all;
-        last_kept_fraction_ = 1.f;
-        return guess;
-      }
-    }
-    {
-      torch::NoGradGuard no_grad;
-      auto head = field.density_head();
-      Tensor counts = torch::empty({n_rays}, iopt);
-      {
-        f2n::ScopedKernelTimer timer("density_scan", stream, (double)n_rays);
-        f2n::check(
-          f2n_density_scan(
-            enc_all_cm.data_ptr<float>(), (int)C, all.dt.data_ptr<float>(),
-            head.first.data_ptr<float>(), head.second.data_ptr<float>(),
-            counts.data_ptr<int32_t>(), n_rays, S, options_.early_stop_trans, 3.f, stream),
-          "f2n_density_scan");
-      }
-      kept.pts_idx_bounds = torch::empty({n_rays, 2}, iopt);
-      f2n::check(
-        f2n_bounds_from_counts(
-          counts.data_ptr<int32_t>(), kept.pts_idx_bounds.data_ptr<int32_t>(),
-          total.data_ptr<int32_t>(), n_rays, stream),
-        "f2n_bounds_from_counts");
-    }
-    survivors_.request(total, stream);
-    RenderResult guess;
-    bool guessed = false;
-    if (may_guess && n_all < kMarginMinSamples) {
-      // enqueued BEFORE the host waits for the count: the GPU does not idle across the read
-      guess = shade_and_composite(all, emb_idx, mode, bg_color, enc_all_cm, contracted_all);
-      guessed = true;
-    }
-    const int64_t n_kept = survivors_.wait();
-    last_n_samples_ = n_kept;
-    last_kept_fraction_ = n_all > 0 ? (float)n_kept / (float)n_all : 0.f;
-    if (guessed && n_kept == n_all) return guess;
-    guess = RenderResult();
-    {
-      torch::NoGradGuard no_grad;
-      if (n_kept == n_all) {
-        // nothing terminated: the uncompacted arrays ARE the compacted ones
-        kept.pts = all.pts;
-        kept.dirs = all.dirs;
-        kept.dt = all.dt;
-        kept.t = all.t;
-        enc_kept_cm = enc_all_cm;
-        contracted_kept = contracted_all;  // ... and so are their contracted positions
-      } else {
-        kept.pts = torch::empty({n_kept, 3}, fopt);
-        kept.dirs = torch::empty({n_kept, 3}, fopt);
-        kept.dt = torch::empty({n_kept}, fopt);
-        kept.t = torch::empty({n_kept}, fopt);
-        f2n::check(
-          f2n_sample_compact(
-            rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), f2n::fptr(noise),
-            kept.pts_idx_bounds.data_ptr<int32_t>(), kept.pts.data_ptr<float>(),
-            kept.dirs.data_ptr<float>(), kept.dt.data_ptr<float>(), kept.t.data_ptr<float>(),
-            n_rays, S, step, stream),
-          "f2n_sample_compact");
-        enc_kept_cm = torch::empty({C, n_kept}, fopt);
-        f2n::check(
-          f2n_compact_rows_cm(
-            enc_all_cm.data_ptr<float>(), n_all, enc_kept_cm.data_ptr<float>(), n_kept, (int)C,
-            kept.pts_idx_bounds.data_ptr<int32_t>(), n_rays, S, stream),
-          "f2n_compact_rows_cm");
-      }
-    }
-    return shade_and_composite(kept, emb_idx, mode, bg_color, enc_kept_cm, contracted_kept);
+    // bg_color that carries a gradient stays on the caller's order (the bucketed route detaches it)
+    const bool bucket = n_rays >= options_.ray_order_min_rays &&
+                        f2n_get_option(F2N_OPT_RAY_ORDER) == 0 &&
+                        !(torch::GradMode::is_enabled() && bg_color.requires_grad());
+    return bucket ? render_dense_bucketed(rays_o, rays_d, emb_idx, mode, noise, bg_color)
+                  : render_dense(rays_o, rays_d, emb_idx, mode, noise, bg_color);
   }
 
   SampleResultFlex kept;
@@ -300,6 +177,292 @@ RenderResult Renderer::render_fused(
       "f2n_sample_compact");
   }
   return shade_and_composite(kept, emb_idx, mode, bg_color);
+}
+
+// ---- bucketed dense pass ---------------------------------------------------------------------------
+
+namespace
+{
+
+// colors [n,3], depths [n] and weights (ragged) of the bucketed order back into the caller's order:
+// row i of the caller is row inv[i] of the bucketed storage; the backward is the inverse gather
+// (map perm).  `rows`: every ray kept all S samples, the weights are plain [n, S] rows.
+class RayUnpermuteFn : public torch::autograd::Function<RayUnpermuteFn>
+{
+public:
+  static torch::autograd::variable_list forward(
+    torch::autograd::AutogradContext * ctx, Tensor colors, Tensor depths, Tensor weights,
+    Tensor perm, Tensor inv, Tensor bounds_sorted, Tensor bounds_caller, int64_t S, bool rows)
+  {
+    colors = f2n::dev_f32(colors, "colors");
+    depths = f2n::dev_f32(depths, "depths");
+    weights = f2n::dev_f32(weights, "weights");
+    const int n = (int)perm.size(0);
+    void * s = f2n::current_stream(colors);
+    Tensor c = torch::empty_like(colors), d = torch::empty_like(depths), w = torch::empty_like(weights);
+    gather(colors, depths, weights, c, d, w, inv, bounds_sorted, bounds_caller, n, S, rows, s);
+    ctx->save_for_backward({perm, bounds_sorted, bounds_caller});
+    ctx->saved_data["S"] = S;
+    ctx->saved_data["rows"] = rows;
+    return {c, d, w};
+  }
+
+  static torch::autograd::variable_list backward(
+    torch::autograd::AutogradContext * ctx, torch::autograd::variable_list g)
+  {
+    auto saved = ctx->get_saved_variables();
+    const Tensor & perm = saved[0];
+    const int n = (int)perm.size(0);
+    const int64_t S = ctx->saved_data["S"].toInt();
+    const bool rows = ctx->saved_data["rows"].toBool();
+    Tensor gc = g[0].defined() ? f2n::dev_f32(g[0], "grad colors") : Tensor();
+    Tensor gd = g[1].defined() ? f2n::dev_f32(g[1], "grad depths") : Tensor();
+    Tensor gw = g[2].defined() ? f2n::dev_f32(g[2], "grad weights") : Tensor();
+    Tensor dc = gc.defined() ? torch::empty_like(gc) : Tensor();
+    Tensor dd = gd.defined() ? torch::empty_like(gd) : Tensor();
+    Tensor dw = gw.defined() ? torch::empty_like(gw) : Tensor();
+    void * s = f2n::current_stream(perm);
+    gather(gc, gd, gw, dc, dd, dw, perm, saved[2], saved[1], n, S, rows, s);
+    return {dc, dd, dw, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+  }
+
+private:
+  // dst = src through `map` for each defined pair; segment bounds src_b -> dst_b
+  static void gather(
+    const Tensor & c, const Tensor & d, const Tensor & w, Tensor & c_out, Tensor & d_out,
+    Tensor & w_out, const Tensor & map, const Tensor & src_b, const Tensor & dst_b, int n, int64_t S,
+    bool rows, void * s)
+  {
+    const int32_t * m = map.data_ptr<int32_t>();
+    if (c.defined())
+      f2n::check(f2n_gather_rows(f2n::fptr(c), c_out.data_ptr<float>(), m, n, 3, s), "f2n_gather_rows");
+    if (d.defined())
+      f2n::check(f2n_gather_rows(f2n::fptr(d), d_out.data_ptr<float>(), m, n, 1, s), "f2n_gather_rows");
+    if (!w.defined()) return;
+    if (rows)
+      f2n::check(
+        f2n_gather_rows(f2n::fptr(w), w_out.data_ptr<float>(), m, n, (int)S, s), "f2n_gather_rows");
+    else
+      f2n::check(
+        f2n_gather_segments(
+          f2n::fptr(w), f2n::iptr(src_b), w_out.data_ptr<float>(), f2n::iptr(dst_b), m, n, s),
+        "f2n_gather_segments");
+  }
+};
+
+}  // namespace
+
+Tensor f2n::ray_order(const Tensor & rays_d_in)
+{
+  const Tensor rays_d = f2n::dev_f32(rays_d_in.detach(), "rays_d");
+  TORCH_CHECK(rays_d.dim() == 2 && rays_d.size(1) == 3, "rays_d must be [n, 3]");
+  const int n = (int)rays_d.size(0);
+  Tensor keys = torch::empty({n}, f2n::int_on(rays_d.device()));
+  f2n::check(
+    f2n_ray_keys(rays_d.data_ptr<float>(), keys.data_ptr<int32_t>(), n, f2n::current_stream(rays_d)),
+    "f2n_ray_keys");
+  // stable: equal keys keep the caller's order, the permutation is deterministic
+  return std::get<1>(keys.sort(/*stable=*/true, /*dim=*/0, /*descending=*/false));
+}
+
+// The dense pass on the rays sorted into pixel-compact bundles (f2n::ray_order): 64 consecutive rays
+// are one ray tile of the encode, and a compact blob of pixels touches fewer table lines per gather
+// than a row strip.  Every ray keeps its own noise row, background colour and image id, so each
+// ray's samples, encoding, colour and weights are those of the caller's order; only their storage
+// order differs, and the results are gathered back (bounds re-scanned in the caller's order).
+RenderResult Renderer::render_dense_bucketed(
+  const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx_in, RunningMode mode,
+  const Tensor & noise, const Tensor & bg_in)
+{
+  const int n_rays = (int)rays_o.size(0);
+  const int64_t S = pts_sampler_->options_.max_samples;
+  const auto iopt = f2n::int_on(rays_o.device());
+  void * stream = f2n::current_stream(rays_o);
+  const Tensor emb_idx = (mode == RunningMode::TRAIN && emb_idx_in.defined())
+                           ? f2n::dev_i32(emb_idx_in, "emb_idx") : Tensor();
+  const Tensor bg = f2n::dev_f32(bg_in.detach(), "bg_color");
+  TORCH_CHECK(bg.numel() == (int64_t)n_rays * 3, "bg_color shape");
+  TORCH_CHECK(!emb_idx.defined() || emb_idx.numel() == n_rays, "emb_idx shape");
+
+  const Tensor order = f2n::ray_order(rays_d);
+  Tensor perm = torch::empty({n_rays}, iopt), inv = torch::empty({n_rays}, iopt);
+  Tensor o_p = torch::empty_like(rays_o), d_p = torch::empty_like(rays_d), bg_p = torch::empty_like(bg);
+  Tensor emb_p = emb_idx.defined() ? torch::empty_like(emb_idx) : Tensor();
+  Tensor noise_p = noise.defined() ? torch::empty_like(noise) : Tensor();
+  f2n::check(
+    f2n_ray_permute(
+      order.data_ptr<int64_t>(), n_rays, (int)S, rays_o.data_ptr<float>(), rays_d.data_ptr<float>(),
+      f2n::iptr(emb_idx), bg.data_ptr<float>(), f2n::fptr(noise), perm.data_ptr<int32_t>(),
+      o_p.data_ptr<float>(), d_p.data_ptr<float>(),
+      emb_idx.defined() ? emb_p.data_ptr<int32_t>() : nullptr, bg_p.data_ptr<float>(),
+      f2n::fptr_mut(noise_p), inv.data_ptr<int32_t>(), stream),
+    "f2n_ray_permute");
+  RenderResult r = render_dense(o_p, d_p, emb_p, mode, noise_p, bg_p);
+
+  // every ray kept all S samples (n_kept = n*S, counts <= S): the bounds {i*S, (i+1)*S} are the same
+  // in both orders; otherwise the caller-order counts are scanned as the unbucketed route scans them
+  const bool rows = r.weights.size(0) == (int64_t)n_rays * S;
+  Tensor bounds = r.idx_start_end;
+  if (!rows) {
+    Tensor counts = torch::empty({n_rays}, iopt), total = torch::empty({1}, iopt);
+    bounds = torch::empty({n_rays, 2}, iopt);
+    f2n::check(
+      f2n_counts_through(
+        r.idx_start_end.data_ptr<int32_t>(), inv.data_ptr<int32_t>(), counts.data_ptr<int32_t>(),
+        n_rays, stream),
+      "f2n_counts_through");
+    f2n::check(
+      f2n_bounds_from_counts(
+        counts.data_ptr<int32_t>(), bounds.data_ptr<int32_t>(), total.data_ptr<int32_t>(), n_rays,
+        stream),
+      "f2n_bounds_from_counts");
+  }
+  auto out = RayUnpermuteFn::apply(
+    r.colors, r.depths, r.weights, perm, inv, r.idx_start_end, bounds, S, rows);
+  return {out[0], out[1], out[2], bounds};
+}
+
+RenderResult Renderer::render_dense(
+  const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
+  const Tensor & noise, const Tensor & bg_color)
+{
+  const int n_rays = (int)rays_o.size(0);
+  const int S = pts_sampler_->options_.max_samples;
+  const float step = pts_sampler_->options_.step;
+  const auto fopt = rays_o.options();
+  const auto iopt = f2n::int_on(rays_o.device());
+  void * stream = f2n::current_stream(rays_o);
+  Hash3DAnchored & field = *scene_field_;
+  const int64_t C = field.options_.n_levels * field.options_.n_channels;
+  // Dense first pass: every sample is encoded once (level-major kernel), the keep-prefix comes
+  // from that encoding, and the shading pass reuses it -- same counts as the march, bit for bit.
+  SampleResultFlex all = pts_sampler_->get_samples(rays_o, rays_d, noise);
+  const int64_t n_all = all.pts.size(0);
+  SampleResultFlex kept;
+  Tensor enc_kept_cm, contracted_kept, contracted_all, enc_all_cm;
+  Tensor total = torch::empty({1}, iopt);
+  {
+    torch::NoGradGuard no_grad;
+    // all.pts is the dense [n_rays, S] grid of the sampler: ray-tile mapping of the encode
+    enc_all_cm = field.encode(all.pts, S, &contracted_all).t();  // [C, n_all] contiguous storage
+    TORCH_CHECK(enc_all_cm.is_contiguous(), "encode() must return channel-major storage");
+  }
+  // The number of survivors sizes everything downstream, so the host has to read it: one blocking
+  // read per chunk.  When the previous chunk kept every sample the next one most likely does too
+  // (no density yet, or validation of empty space), so that case is tried first and for free: the
+  // shading pass is run over ALL samples (fresh buffers, nothing observable), the density logits
+  // it produces anyway are summed per ray (f2n_density_margin: 67 MB instead of the 1 GB encoding
+  // the exact scan reads) and a flag says whether some ray comes within a factor e^0.5 of the
+  // early-stop threshold.  Flag clear = the exact scan would keep everything too (its logits
+  // differ from these in the last bits only): the guess IS the result, and neither the scan
+  // (0.22 ms per 8.4 M samples) nor an idle GPU across the read (the flag travels while
+  // compositing runs) was paid.  Flag set = drop the guess, run the exact scan, compact.
+  //   Small chunks (the 512-ray training batch) keep the exact scan instead -- there it costs
+  // 20 us, less than the GPU would idle while the host waits for a flag that only exists after
+  // the shading pass -- and hide ITS read-back behind the same guess (further down).
+  if (options_.deferred_check && options_.fused_shade) {
+    // no host read: exact scan -> device-side "kept fewer than shaded" flag, all samples shaded
+    torch::NoGradGuard no_grad;
+    auto head = field.density_head();
+    Tensor counts = torch::empty({n_rays}, iopt);
+    {
+      f2n::ScopedKernelTimer timer("density_scan", stream, (double)n_rays);
+      f2n::check(
+        f2n_density_scan(
+          enc_all_cm.data_ptr<float>(), (int)C, all.dt.data_ptr<float>(),
+          head.first.data_ptr<float>(), head.second.data_ptr<float>(),
+          counts.data_ptr<int32_t>(), n_rays, S, options_.early_stop_trans, 3.f, stream),
+        "f2n_density_scan");
+    }
+    Tensor scratch_bounds = torch::empty({n_rays, 2}, iopt);
+    f2n::check(
+      f2n_bounds_from_counts(
+        counts.data_ptr<int32_t>(), scratch_bounds.data_ptr<int32_t>(), total.data_ptr<int32_t>(),
+        n_rays, stream),
+      "f2n_bounds_from_counts");
+    if (!deferred_bad_.defined()) deferred_bad_ = torch::zeros({1}, iopt);
+    deferred_bad_.add_(total.ne(n_all).to(torch::kInt32));
+    last_n_samples_ = n_all;
+    last_kept_fraction_ = 1.f;
+  }
+  if (options_.deferred_check && options_.fused_shade)
+    return shade_and_composite(all, emb_idx, mode, bg_color, enc_all_cm, contracted_all);
+  const bool may_guess = options_.speculate_dense && last_kept_fraction_ >= 1.f && n_all > 0;
+  const int64_t kMarginMinSamples = options_.margin_min_samples;
+  if (may_guess && n_all >= kMarginMinSamples) {
+    Tensor near_threshold = torch::zeros({1}, iopt);
+    RenderResult guess = shade_and_composite(
+      all, emb_idx, mode, bg_color, enc_all_cm, contracted_all, &near_threshold, S);
+    if (survivors_.wait() == 0) {
+      last_n_samples_ = n_all;
+      last_kept_fraction_ = 1.f;
+      return guess;
+    }
+  }
+  {
+    torch::NoGradGuard no_grad;
+    auto head = field.density_head();
+    Tensor counts = torch::empty({n_rays}, iopt);
+    {
+      f2n::ScopedKernelTimer timer("density_scan", stream, (double)n_rays);
+      f2n::check(
+        f2n_density_scan(
+          enc_all_cm.data_ptr<float>(), (int)C, all.dt.data_ptr<float>(),
+          head.first.data_ptr<float>(), head.second.data_ptr<float>(),
+          counts.data_ptr<int32_t>(), n_rays, S, options_.early_stop_trans, 3.f, stream),
+        "f2n_density_scan");
+    }
+    kept.pts_idx_bounds = torch::empty({n_rays, 2}, iopt);
+    f2n::check(
+      f2n_bounds_from_counts(
+        counts.data_ptr<int32_t>(), kept.pts_idx_bounds.data_ptr<int32_t>(),
+        total.data_ptr<int32_t>(), n_rays, stream),
+      "f2n_bounds_from_counts");
+  }
+  survivors_.request(total, stream);
+  RenderResult guess;
+  bool guessed = false;
+  if (may_guess && n_all < kMarginMinSamples) {
+    // enqueued BEFORE the host waits for the count: the GPU does not idle across the read
+    guess = shade_and_composite(all, emb_idx, mode, bg_color, enc_all_cm, contracted_all);
+    guessed = true;
+  }
+  const int64_t n_kept = survivors_.wait();
+  last_n_samples_ = n_kept;
+  last_kept_fraction_ = n_all > 0 ? (float)n_kept / (float)n_all : 0.f;
+  if (guessed && n_kept == n_all) return guess;
+  guess = RenderResult();
+  {
+    torch::NoGradGuard no_grad;
+    if (n_kept == n_all) {
+      // nothing terminated: the uncompacted arrays ARE the compacted ones
+      kept.pts = all.pts;
+      kept.dirs = all.dirs;
+      kept.dt = all.dt;
+      kept.t = all.t;
+      enc_kept_cm = enc_all_cm;
+      contracted_kept = contracted_all;  // ... and so are their contracted positions
+    } else {
+      kept.pts = torch::empty({n_kept, 3}, fopt);
+      kept.dirs = torch::empty({n_kept, 3}, fopt);
+      kept.dt = torch::empty({n_kept}, fopt);
+      kept.t = torch::empty({n_kept}, fopt);
+      f2n::check(
+        f2n_sample_compact(
+          rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), f2n::fptr(noise),
+          kept.pts_idx_bounds.data_ptr<int32_t>(), kept.pts.data_ptr<float>(),
+          kept.dirs.data_ptr<float>(), kept.dt.data_ptr<float>(), kept.t.data_ptr<float>(),
+          n_rays, S, step, stream),
+        "f2n_sample_compact");
+      enc_kept_cm = torch::empty({C, n_kept}, fopt);
+      f2n::check(
+        f2n_compact_rows_cm(
+          enc_all_cm.data_ptr<float>(), n_all, enc_kept_cm.data_ptr<float>(), n_kept, (int)C,
+          kept.pts_idx_bounds.data_ptr<int32_t>(), n_rays, S, stream),
+        "f2n_compact_rows_cm");
+    }
+  }
+  return shade_and_composite(kept, emb_idx, mode, bg_color, enc_kept_cm, contracted_kept);
 }
 
 bool Renderer::deferred_check_ok()

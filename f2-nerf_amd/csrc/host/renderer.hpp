@@ -84,6 +84,11 @@ struct RendererOptions
   // weights are below 1e-4 of the ray's, but not zero) and must be repeated without this option.
   bool deferred_check = false;
   bool check_finite = false;       // the reference's CHECK(isfinite(colors.mean())) host sync
+  // Dense first pass of at least this many rays: render the rays bucketed into pixel-compact bundles
+  // (f2n_ray_keys) and hand the results back in the caller's order, bit for bit the same
+  // (F2N_OPT_RAY_ORDER = 1 switches it off).  The sort, permutes and gathers cost ~0.1 ms per chunk
+  // (measured: +3.5 % at 65536-ray chunks of S = 128, L = 16; -15 % at 8192-ray chunks of S = 64, L = 4).
+  int64_t ray_order_min_rays = 65536;
 };
 
 class Renderer : public torch::nn::Module
@@ -131,6 +136,12 @@ private:
   RenderResult render_fused(
     const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
     const Tensor & noise, const Tensor & bg_color);
+  RenderResult render_dense(
+    const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
+    const Tensor & noise, const Tensor & bg_color);
+  RenderResult render_dense_bucketed(
+    const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
+    const Tensor & noise, const Tensor & bg_color);
   RenderResult render_op_by_op(
     const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
     const Tensor & noise, const Tensor & bg_color);
@@ -153,6 +164,10 @@ struct TrainStepResult
   int64_t n_values;   // n_rays * 3
   int64_t n_samples;  // surviving samples in this step
 };
+
+// Caller indices of the rays sorted into pixel-compact bundles: the stable sort of their
+// f2n_ray_keys, int64 [n].
+Tensor ray_order(const Tensor & rays_d);
 
 TrainStepResult train_step(
   Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,

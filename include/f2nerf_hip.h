@@ -64,7 +64,10 @@ const char * f2n_status_string(int status);
                                   reduce pass runs in ceil(T*F / level_stride) launches of levels that
                                   do not overlap: bit-reproducible also when accumulating into an
                                   existing gradient, 4-25 % slower                                   */
-#define F2N_OPT_COUNT 9
+#define F2N_OPT_RAY_ORDER 9     /* Renderer dense first pass: 0 rays bucketed into pixel-compact bundles
+                                  (f2n_ray_keys) and results handed back in caller order, 1 rays
+                                  rendered in the caller's order; same results bit for bit          */
+#define F2N_OPT_COUNT 10
 int f2n_set_option(int key, int value);
 int f2n_get_option(int key);
 
@@ -267,6 +270,40 @@ int f2n_bounds_from_counts(
 int f2n_sample_compact(
   const float * rays_o, const float * rays_d, const float * noise, const int32_t * bounds,
   float * pts, float * dirs, float * dt, float * t, int n_rays, int S, float step, void * stream);
+
+/* ------------------------------------------------------------------ ray order --------------- */
+
+/* Bucketing of a ray batch for the gather locality of f2n_hash_fwd_raytile (no reference
+ * counterpart: Renderer::render, src/renderer.cpp:33-123, renders rays in the order it is given
+ * them; its RenderResult, :122, is what the gathers below restore).  keys [n] int32 (>= 0) from
+ * the direction alone (cube-face projection, 14 bits per face axis, Hilbert order): sorted stably,
+ * 64 consecutive rays of one view become a compact pixel blob. */
+int f2n_ray_keys(const float * rays_d, int32_t * keys, int n, void * stream);
+
+/* Inputs of ray j of the sorted order from caller ray order[j] (order: the int64 indices of a
+ * stable sort of the keys): rays_o / rays_d / bg [n,3], emb_idx [n], noise [n, S] (emb_idx, bg,
+ * noise may be NULL together with their outputs); perm[j] = order[j] as int32, inv[perm[j]] = j. */
+int f2n_ray_permute(
+  const int64_t * order, int n, int S, const float * rays_o, const float * rays_d,
+  const int32_t * emb_idx, const float * bg, const float * noise, int32_t * perm, float * rays_o_p,
+  float * rays_d_p, int32_t * emb_idx_p, float * bg_p, float * noise_p, int32_t * inv,
+  void * stream);
+
+/* dst row i = src row map[i], rows of row_floats floats (a permutation's gather; with the inverse
+ * map it is also the scatter). */
+int f2n_gather_rows(
+  const float * src, float * dst, const int32_t * map, int n, int row_floats, void * stream);
+
+/* Ragged counterpart: dst[dst_bounds[i].start + k] = src[src_bounds[map[i]].start + k] for
+ * k < dst_bounds[i].end - dst_bounds[i].start (the two segments have equal lengths). */
+int f2n_gather_segments(
+  const float * src, const int32_t * src_bounds, float * dst, const int32_t * dst_bounds,
+  const int32_t * map, int n_rays, void * stream);
+
+/* counts[i] = bounds[map[i]].end - bounds[map[i]].start (f2n_bounds_from_counts turns them into
+ * the bounds of the caller's order). */
+int f2n_counts_through(
+  const int32_t * bounds, const int32_t * map, int32_t * counts, int n_rays, void * stream);
 
 /* ------------------------------------------------------------------ compositing (rows A7, A8) - */
 
