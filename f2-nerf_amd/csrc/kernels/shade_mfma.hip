@@ -10,14 +10,14 @@
 //
 // Layouts.  lane l = (q = l >> 4, m = l & 15).  One 16x16x4 MFMA: D[4q+r][m] += sum_k A[m][k] B[k][m]
 // with lane (q, m) supplying a = A[row m][k = q], b = B[k = q][col m] and holding D rows 4q+r, r<4.
-//   Q-layout (activations of 64 samples): lane (q, m) holds feature 4q+r (+16 per M-tile) of
-//     samples 16T+m, T = 0..3.  An MFMA output IS in Q-layout (rows = features, cols = samples), and
+//   Q-layout (activations of a stride of 16 TS samples): lane (q, m) holds feature 4q+r (+16 per
+//     M-tile) of samples 16T+m, T < TS.  An MFMA output IS in Q-layout (rows = features, cols = samples), and
 //     is the next layer's B operand when that layer walks its k index in the order (M, r) with
 //     k = 16M + 4q + r -- so the whole forward and the data-gradient chain need no lane movement.
 //     The weight (A) operands are staged in LDS once per workgroup, pre-arranged per lane in
 //     exactly that k order ("slots" of 64 floats, conflict-free ds_read_b32).
 //   S-layout (for sums over samples: d w1, d w2, d w_h): operands need the SAMPLE on the k axis and
-//     the feature on the lane, i.e. the transpose.  Each wave has an LDS tile [feature][72]: Q-layout
+//     the feature on the lane, i.e. the transpose.  Each wave has an LDS tile [feature][kP]: Q-layout
 //     registers are written with ds_write_b32 (lanes of a quarter = consecutive samples) and read back
 //     as float4 = four consecutive k-steps (k-step t of quarter q = sample 16(t/4) + 4q + t%4).
 //
@@ -28,9 +28,24 @@
 // the four quarters (the MFMA's k axis) and hands the sum to every lane: 12 products instead of 64.
 // Its two backward products (d w2, and d_hid = w2^T d_o) are vector FMAs on the same registers.
 //
-// Per 64-sample stride: 428 MFMAs + ~580 vector FMAs, ~130 KB of LDS traffic.  Accumulators of all
-// parameter gradients stay in registers across the strides of a (persistent) wave; one atomic flush
-// per wave at the end.
+// Per 64 samples: 428 MFMAs + ~580 vector FMAs, ~130 KB of LDS traffic.  Accumulators of all
+// parameter gradients stay in registers across the strides of a (persistent) wave; the waves of a
+// workgroup meet in LDS at the end and send one set of atomics.
+//
+// Occupancy (round 5).  Strides of TS = 2 tiles (32 samples) at two waves per SIMD, one 8-wave
+// workgroup per CU, are the default; TS = 4 (64 samples) at one wave per SIMD, the round-3 form, is
+// F2N_OPT_SHADE_BWD_WAVES = 1.  At one wave every dependent chain was exposed (MFMA result -> vector
+// op, LDS write -> transposed read): the matrix pipe was busy half the time.  Route taken: the
+// issue's first one, not wave specialisation -- 32-sample strides halve every per-stride array; the
+// hidden layer's weight operands are read from LDS when needed instead of pinned in 32 registers;
+// the d w2 partials (48 registers replicated over a quarter's lanes) are reduce-scattered over the
+// quarter every stride with three DPP steps, leaving 6; the next stride's inputs are no longer
+// prefetched (the partner wave covers the wait); the end-of-kernel meet goes through the whole LDS
+// in rounds.  With all of that every instantiation fits 256 registers without scratch; the WIDE
+// kernels need the phase fences (V = 0) for it.  Launches of fewer than
+// F2N_SHADE_BWD_TWO_WAVES_MIN_SAMPLES samples (few strides per wave) take the one-wave form, which
+// is faster there.  The data-gradient chain per sample is unchanged:
+// d_enc is bit-identical to the TS = 4 form, the parameter gradients differ in the order of sums.
 #include "shade_mfma.hiph"
 
 #include "sh_basis.hiph"
@@ -52,10 +67,13 @@ constexpr int kIn2 = 32;    // shader input = 16 shading features + 16 SH
 constexpr int kHid = 64;    // shader hidden width
 constexpr float kEps = 1e-3f;
 
-template <int C>
+// TS = 16-sample column tiles per stride: 2 (the default, two waves per SIMD) or 4 (round 3, one).
+template <int C, int TS>
 struct MShape
 {
   static_assert(C % 8 == 0 && C <= 64, "MFMA path: C must be 8, 16, 32 or 64");
+  static_assert(TS == 2 || TS == 4, "16-sample tiles per stride: 2 or 4");
+  static constexpr int kStride = 16 * TS;  // samples per stride
   static constexpr int kS1 = C / 4;    // k-steps of the head layer (quarter q owns channels q*kS1 ..)
   static constexpr int kM6 = (C + 15) / 16;  // 16-channel tiles of enc (C = 8: half a tile, zero padded)
   // weight operand slots (64 floats each, one per lane)
@@ -69,30 +87,46 @@ struct MShape
   static constexpr int oB1 = oBh + 16;         // b1[64]
   static constexpr int oB2 = oB1 + 64;         // b2[3], 0
   static constexpr int kWFloats = oB2 + 4;
-  // per-wave S-layout tiles
-  static constexpr int kP = 72;                // row pitch: 16-byte aligned rows; with 72 the float4
-                                               // reads (row m, column 16u+4q) are conflict-free in
-                                               // ds_read_b128's four 16-lane groups (68 is 2-way)
+  // per-wave S-layout tiles, rows of kStride samples.  Row pitch: 16-byte aligned rows, and the
+  // float4 reads (row m, column 16u+4q) conflict-free in ds_read_b128's four 16-lane groups (banks
+  // (a/4) mod 64, four per lane): the pitch must be 8 mod 16 so that the 16 rows m of a group start
+  // on 16 distinct 4-bank slots.  40 and 72 are the smallest such pitches above 32 and 64 columns
+  // (36 and 68 are 2-way).  C = 64 at two waves takes 36 -- 2-way on those reads -- because eight
+  // 40-float tiles of 116 rows and the weights exceed the 160 KiB of a CU by 6 KiB.  (The b32 writes
+  // of the Q-layout are 2-way at 40 and 72, which costs nothing extra on a ds_write_b32.)
+  static constexpr int kP = (TS == 4) ? 72 : (C == 64) ? 36 : 40;
   static constexpr int oXS = 0;                // [32][kP]  X
   static constexpr int oES = oXS + 32 * kP;    // [C][kP]   enc
   static constexpr int oPS = oES + kM6 * 16 * kP;  // [16][kP]  one M-tile of relu(pre) / d_hid, then d_h
   static constexpr int oDS = oPS + 16 * kP;    // [4][kP]   d_o rows 0..2
-  static constexpr int kAccs = 89 + 4 * kM6;   // accumulator registers a wave hands to wave 0 at the end
-  static constexpr int kWaveFloats = (oDS + 4 * kP > kAccs * 64) ? oDS + 4 * kP : kAccs * 64;
-  // One wave per SIMD.  The live state of a stride (64 pre-activations, 65 accumulators, operands in
-  // flight) does not fit the 256 registers a wave gets at two per SIMD: hipcc then parks the
-  // accumulators in scratch and every reload drains vmcnt (2.0-2.6 ms per 8.4 M samples); with 512
-  // registers there is no spill and room to prefetch the next stride's inputs (measured 1.8 ms
-  // before, see DESIGN.md, the prefetch).
-  static constexpr int kWaves = 4;
+  // d w2 partials per lane, [c][kW2M][kW2R]: TS = 4 all 48 (c, j) of the lane's quarter; TS = 2 an
+  // eighth of them, the rest handed to partner lanes every stride (see the d w2 phase)
+  static constexpr int kW2M = (TS == 4) ? 4 : 2, kW2R = (TS == 4) ? 4 : 1;
+  static constexpr int kAccs = 41 + 3 * kW2M * kW2R + 4 * kM6;  // accumulator registers a wave hands to wave 0
+  // TS = 4: a wave's tile also holds its accumulators at the end (the meet below)
+  static constexpr int kWaveFloats =
+    (TS == 4 && kAccs * 64 > oDS + 4 * kP) ? kAccs * 64 : oDS + 4 * kP;
+  // TS = 2: two waves per SIMD, one 8-wave workgroup per CU.  The live state of a 32-sample stride
+  // (32 pre-activations, ~100 accumulators, operands in flight) fits the 256 registers a wave gets
+  // at two per SIMD without spilling, and the partner wave covers the chains one wave leaves exposed
+  // (MFMA result -> vector op, LDS write -> transposed read, the weight operands read from LDS).
+  // TS = 4, round 3: one wave per SIMD.  64 pre-activations and the accumulators do not fit 256
+  // registers (hipcc parked the accumulators in scratch: 2.0-2.6 ms per 8.4 M samples), only 512.
+  static constexpr int kWaves = (TS == 4) ? 4 : 8;
   static constexpr int kLdsFloats = kWFloats + kWaves * kWaveFloats;
   static_assert(kLdsFloats * 4 <= 160 * 1024, "LDS budget");
+  // TS = 2, the end-of-kernel meet of the accumulators in wave 0: waves 1.. hand over kMeetRegs
+  // registers per round through the whole LDS (one round since the d w2 partials take 6 registers)
+  static constexpr int kMeetRegs = kLdsFloats / ((kWaves - 1) * 64);
+  static constexpr int kMeetRounds = (kAccs + kMeetRegs - 1) / kMeetRegs;
 };
 
-// V & 1: the scheduler may mix the phases of a stride (the default since the output layer moved to
-// the vector pipe: 1.47 vs 1.54 ms per 8.4 M samples -- its vector phases then fill the gaps of the
-// matrix phases around them; with every phase on the matrix cores, round 2, the fenced form was 5 %
-// faster).  F2N_OPT_SHADE_VARIANT = 1 puts the fences back, for measurements.
+// V & 1: the scheduler may mix the phases of a stride (the default of the one-wave form since the
+// output layer moved to the vector pipe: 1.47 vs 1.54 ms per 8.4 M samples -- its vector phases then
+// fill the gaps of the matrix phases around them; with every phase on the matrix cores, round 2, the
+// fenced form was 5 % faster).  At two waves per SIMD the partner wave fills those gaps and the
+// fenced form is the default (1.30 vs 1.33 ms).  F2N_OPT_SHADE_VARIANT = 1 puts the fences into the
+// one-wave form, F2N_OPT_SHADE_BWD_WAVES = 3 takes them out of the two-wave form, for measurements.
 template <int V>
 __device__ __forceinline__ void phase_fence_v()
 {
@@ -147,6 +181,14 @@ __device__ __forceinline__ float relu(float x)
   return __int_as_float(b > 0 ? b : 0);
 }
 
+// another lane's v by DPP: 0x140 row_mirror, lane 15 - m within each 16-lane row; 0x141
+// row_half_mirror, lane 7 - m within each 8; 0x4e quad_perm [2,3,0,1], lane m ^ 2
+template <int kCtrl>
+__device__ __forceinline__ float dpp_move(float v)
+{
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), kCtrl, 0xf, 0xf, false));
+}
+
 // sum over the 16 lanes of a quarter (a DPP row), result in every lane of the quarter
 __device__ __forceinline__ float quarter_sum(float v)
 {
@@ -157,8 +199,8 @@ __device__ __forceinline__ float quarter_sum(float v)
   return v;
 }
 
-template <int C, int V, bool WIDE>
-__global__ __launch_bounds__(MShape<C>::kWaves * 64) void shade_bwd_mfma_kernel(
+template <int C, int V, bool WIDE, int TS>
+__global__ __launch_bounds__((MShape<C, TS>::kWaves * 64)) void shade_bwd_mfma_kernel(
   const float * __restrict__ enc, const float * __restrict__ dirs,
   const int32_t * __restrict__ sample_img, const float * __restrict__ p_w_h,
   const float * __restrict__ p_b_h, const float * __restrict__ p_w1,
@@ -169,8 +211,8 @@ __global__ __launch_bounds__(MShape<C>::kWaves * 64) void shade_bwd_mfma_kernel(
   float * __restrict__ g_b1, float * __restrict__ g_w2, float * __restrict__ g_b2,
   float * __restrict__ g_emb, int64_t n)
 {
-  using S = MShape<C>;
-  constexpr int kS1 = S::kS1, kM6 = S::kM6, kP = S::kP;
+  using S = MShape<C, TS>;
+  constexpr int kS1 = S::kS1, kM6 = S::kM6, kP = S::kP, kStride = S::kStride;
   __shared__ __attribute__((aligned(16))) float lds_all[S::kLdsFloats];
   float * lds_w = lds_all;
 
@@ -211,16 +253,18 @@ __global__ __launch_bounds__(MShape<C>::kWaves * 64) void shade_bwd_mfma_kernel(
   float * PS = tile + S::oPS;
   float * DS = tile + S::oDS;
   if constexpr (C % 16 != 0) {  // enc rows beyond C (read as zeros by the d w_h product)
-    for (int r = C; r < kM6 * 16; r++) ES[r * kP + lane] = 0.f;
+    if (lane < kStride)
+      for (int r = C; r < kM6 * 16; r++) ES[r * kP + lane] = 0.f;
   }
   __syncthreads();
 
   const float * wop = lds_w + lane;  // slot s of this lane: wop[s * 64]
-  // With 512 registers the weight operands stay in registers for the whole kernel (C <= 32: 84 of
-  // them); read just in time from LDS they cost a full LDS latency every eight products.
-  // (the head and hidden layers' operands, slots below oWA5; the data-gradient operands of the last
-  // two phases are read when needed: the vector phases of the output layer need their registers)
-  constexpr bool kWReg = C <= 32;
+  // One wave per SIMD, 512 registers: the hidden layer's weight operands stay in registers for the
+  // whole kernel (C <= 32); read just in time from LDS they cost a full LDS latency every eight
+  // products.  (The data-gradient operands of the last two phases are read when needed: the vector
+  // phases of the output layer need their registers.)  At two waves per SIMD the 32 registers are
+  // needed elsewhere and the partner wave covers the LDS latency.
+  constexpr bool kWReg = TS == 4 && C <= 32;
   constexpr int kRegLo = S::oWA2, kRegHi = S::oWA5;  // the hidden layer's 32 slots
   float wreg[kWReg ? kRegHi - kRegLo : 1];
   if constexpr (kWReg) {
@@ -239,7 +283,10 @@ __global__ __launch_bounds__(MShape<C>::kWaves * 64) void shade_bwd_mfma_kernel(
   // per-lane accumulators that live across all strides of this wave
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   f32x4 acc_w1[4][2];   // d w1[16M+4q+r][16N+m]
-  f32x4 acc_w2[3][4];   // d w2[c][16M+4q+r], partial over this lane's samples (vector FMAs)
+  constexpr int kW2M = S::kW2M, kW2R = S::kW2R;
+  float acc_w2[3][kW2M][kW2R];  // d w2[c][16M+4q+r], partial over this lane's samples (vector FMAs);
+                                // TS = 2: M = 2 M' + [m & 3 >= 2], r = m >> 2, over 8 lanes' samples
+  float w2_even[3];             // TS = 2: the even M-tile's partials, combined with the odd one's
   f32x4 acc_wh[kM6];    // d w_h[4q+r][16N+m]
   float acc_b1[4];      // d b1[16M+m], partial over this quarter's k-steps (S-layout reads)
   f32x4 acc_bh = zero4; // d b_h[4q+r]
@@ -259,90 +306,110 @@ __global__ __launch_bounds__(MShape<C>::kWaves * 64) void shade_bwd_mfma_kernel(
 #pragma unroll
   for (int M = 0; M < 4; M++) {
     acc_w1[M][0] = acc_w1[M][1] = zero4;
-    acc_w2[0][M] = acc_w2[1][M] = acc_w2[2][M] = zero4;
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+#pragma unroll
+      for (int r = 0; r < kW2R; r++)
+        if (M < kW2M) acc_w2[c][M][r] = 0.f;
     acc_b1[M] = 0.f;
   }
 #pragma unroll
   for (int N = 0; N < kM6; N++) acc_wh[N] = zero4;
 
-  const int64_t n_strides = (n + 63) / 64;
+  const int64_t n_strides = (n + kStride - 1) / kStride;
   const int64_t wave_global = (int64_t)blockIdx.x * S::kWaves + wave;
   const int64_t wave_count = (int64_t)gridDim.x * S::kWaves;
   // inputs of one stride that depend on nothing: issued together (one memory latency), and for
   // the NEXT stride while the current one is in its hidden layer
-  float eB[kS1][4];
-  int img[4] = {0, 0, 0, 0};
-  float dir[3];
-  auto load_inputs = [&](int64_t st_, float (&eB_)[kS1][4], int (&img_)[4], float (&dir_)[3]) {
-    const int64_t s0_ = st_ * 64;  // may lie beyond the end: every index is clamped to a real sample
-    uint32_t off_[4];
+  float eB[kS1][TS];
+  int img[TS];
 #pragma unroll
-    for (int T = 0; T < 4; T++) off_[T] = (uint32_t)(((s0_ + 16 * T + m < n) ? s0_ + 16 * T + m : n - 1) * 4);
+  for (int T = 0; T < TS; T++) img[T] = 0;
+  float dir[3];
+  // SH: lane l evaluates sample s0 + l % kStride (at TS = 2 both halves of the wave the same 32)
+  const int lS = lane % kStride;
+  auto load_inputs = [&](int64_t st_, float (&eB_)[kS1][TS], int (&img_)[TS], float (&dir_)[3]) {
+    const int64_t s0_ = st_ * kStride;  // may lie beyond the end: every index is clamped to a real sample
+    uint32_t off_[TS];
+#pragma unroll
+    for (int T = 0; T < TS; T++) off_[T] = (uint32_t)(((s0_ + 16 * T + m < n) ? s0_ + 16 * T + m : n - 1) * 4);
 #pragma unroll
     for (int t = 0; t < kS1; t++)
 #pragma unroll
-      for (int T = 0; T < 4; T++) eB_[t][T] = ld_row(enc + (int64_t)t * n, off_[T] + cE);
+      for (int T = 0; T < TS; T++) eB_[t][T] = ld_row(enc + (int64_t)t * n, off_[T] + cE);
     if (has_emb) {
 #pragma unroll
-      for (int T = 0; T < 4; T++) img_[T] = ld_row(sample_img, off_[T]);
+      for (int T = 0; T < TS; T++) img_[T] = ld_row(sample_img, off_[T]);
     }
-    const uint32_t offL = (uint32_t)(((s0_ + lane < n) ? s0_ + lane : n - 1) * 12);
+    const uint32_t offL = (uint32_t)(((s0_ + lS < n) ? s0_ + lS : n - 1) * 12);
 #pragma unroll
     for (int k = 0; k < 3; k++) dir_[k] = ld_row(dirs + k, offL);
   };
-  load_inputs(wave_global, eB, img, dir);
-  issue_fence();
+  if constexpr (TS == 4) {
+    load_inputs(wave_global, eB, img, dir);
+    issue_fence();
+  }
 
   for (int64_t st = wave_global; st < n_strides; st += wave_count) {
-    const int64_t s0 = st * 64;
+    const int64_t s0 = st * kStride;
+    // TS = 2: no prefetch of the next stride (its registers would spill); the partner wave on the
+    // SIMD runs while this one waits
+    if constexpr (TS == 2) load_inputs(st, eB, img, dir);
     // this lane's Q-layout samples 16T+m (clamped: invalid ones read a real sample and get zero
     // gradients).  Everything per sample is addressed as wave-uniform pointer + 32-bit byte offset
-    // (the launcher guarantees C * n * 4 < 2^32): four offset registers serve all rows.
-    bool vT[4];
-    uint32_t offS[4];
+    // (the launcher guarantees C * n * 4 < 2^32): TS offset registers serve all rows.
+    bool vT[TS];
+    uint32_t offS[TS];
 #pragma unroll
-    for (int T = 0; T < 4; T++) {
+    for (int T = 0; T < TS; T++) {
       const int64_t s = s0 + 16 * T + m;
       vT[T] = s < n;
       offS[T] = (uint32_t)((vT[T] ? s : n - 1) * 4);
     }
 
     // ---- head layer: h[4q+r][s] = w_h . enc + b_h
-    f32x4 h[4];
+    f32x4 h[TS];
 #pragma unroll
-    for (int T = 0; T < 4; T++) h[T] = *reinterpret_cast<const f32x4 *>(lds_w + S::oBh + 4 * q);
+    for (int T = 0; T < TS; T++) h[T] = *reinterpret_cast<const f32x4 *>(lds_w + S::oBh + 4 * q);
 #pragma unroll
     for (int t = 0; t < kS1; t++) {
       const float a = W(S::oWA1 + t);
 #pragma unroll
-      for (int T = 0; T < 4; T++) h[T] = mfma16(a, eB[t][T], h[T]);
+      for (int T = 0; T < TS; T++) h[T] = mfma16(a, eB[t][T], h[T]);
     }
     // enc's S-layout image for d w_h at the end of the stride
 #pragma unroll
     for (int t = 0; t < kS1; t++)
 #pragma unroll
-      for (int T = 0; T < 4; T++) ES[(q * kS1 + t) * kP + 16 * T + m] = eB[t][T];
+      for (int T = 0; T < TS; T++) ES[(q * kS1 + t) * kP + 16 * T + m] = eB[t][T];
 
     phase_fence_v<V>();
     // ---- shader input X: rows 0..15 = [1, h[1..15]] (+ embedding), rows 16..31 = SH16(dir)
-    f32x4 Xh[4];
-    int img_cur[4];
+    f32x4 Xh[TS];
+    int img_cur[TS];
 #pragma unroll
-    for (int T = 0; T < 4; T++) img_cur[T] = img[T];
+    for (int T = 0; T < TS; T++) img_cur[T] = img[T];
     {
-      f32x4 e4[4];
+      f32x4 e4[TS];
       if (has_emb) {
 #pragma unroll
-        for (int T = 0; T < 4; T++)
+        for (int T = 0; T < TS; T++)
           e4[T] = *reinterpret_cast<const f32x4 *>(p_emb + (int64_t)img_cur[T] * kOut1 + 4 * q);
       }
-      // SH: lane l evaluates sample s0 + l and writes its column of the S-layout tile directly
+      // SH: lane l evaluates sample s0 + l % kStride and writes its column of the S-layout tile
+      // directly (at TS = 2 the lower half of the wave rows 16..23, the upper half rows 24..31)
       float sh[16];
       sh_basis<4>(dir[0], dir[1], dir[2], sh);
+      if constexpr (TS == 4) {
 #pragma unroll
-      for (int k = 0; k < 16; k++) XS[(16 + k) * kP + lane] = sh[k];
+        for (int k = 0; k < 16; k++) XS[(16 + k) * kP + lane] = sh[k];
+      } else {
+        const bool hi = lane >= 32;
 #pragma unroll
-      for (int T = 0; T < 4; T++) {
+        for (int k = 0; k < 8; k++) XS[(16 + (hi ? 8 : 0) + k) * kP + lS] = hi ? sh[8 + k] : sh[k];
+      }
+#pragma unroll
+      for (int T = 0; T < TS; T++) {
         Xh[T] = h[T];
         if (q == 0) Xh[T][0] = 1.f;
         if (has_emb) Xh[T] += e4[T];
@@ -354,23 +421,23 @@ __global__ __launch_bounds__(MShape<C>::kWaves * 64) void shade_bwd_mfma_kernel(
 
     phase_fence_v<V>();
     // ---- hidden layer: pre[16M+4q+r][s] = w1 . X + b1
-    f32x4 pre[4][4];
+    f32x4 pre[4][TS];
     {
-      float Xs[4][4];  // SH rows 16+4q+t' of this lane's samples
+      float Xs[4][TS];  // SH rows 16+4q+t' of this lane's samples
 #pragma unroll
       for (int t = 0; t < 4; t++)
 #pragma unroll
-        for (int T = 0; T < 4; T++) Xs[t][T] = XS[(16 + 4 * q + t) * kP + 16 * T + m];
+        for (int T = 0; T < TS; T++) Xs[t][T] = XS[(16 + 4 * q + t) * kP + 16 * T + m];
 #pragma unroll
       for (int M = 0; M < 4; M++) {
 #pragma unroll
-        for (int T = 0; T < 4; T++)
+        for (int T = 0; T < TS; T++)
           pre[M][T] = *reinterpret_cast<const f32x4 *>(lds_w + S::oB1 + 16 * M + 4 * q);
 #pragma unroll
         for (int t = 0; t < 8; t++) {
           const float a = W(S::oWA2 + M * 8 + t);
 #pragma unroll
-          for (int T = 0; T < 4; T++)
+          for (int T = 0; T < TS; T++)
             pre[M][T] = mfma16(a, (t < 4) ? Xh[T][t] : Xs[t - 4][T], pre[M][T]);
         }
       }
@@ -380,17 +447,17 @@ __global__ __launch_bounds__(MShape<C>::kWaves * 64) void shade_bwd_mfma_kernel(
     // ---- output layer on the vector pipe: per-quarter partial sums over this lane's 16 hidden
     // neurons (pre becomes relu(pre): its sign is all the ReLU's backward needs), the four quarters
     // summed by one all-ones product per (c, sample tile); then d_o for c = q
-    float d_o[4];
+    float d_o[TS];
     {
-      float g_rgb[4];  // d_rgb[s][c = q]: in flight during the sums below
+      float g_rgb[TS];  // d_rgb[s][c = q]: in flight during the sums below
 #pragma unroll
-      for (int T = 0; T < 4; T++) g_rgb[T] = ld_row(d_rgb, 3 * offS[T] + ((q < 3) ? 4 * q : 8));
+      for (int T = 0; T < TS; T++) g_rgb[T] = ld_row(d_rgb, 3 * offS[T] + ((q < 3) ? 4 * q : 8));
       issue_fence();
-      float po[3][4];
+      float po[3][TS];
 #pragma unroll
       for (int c = 0; c < 3; c++)
 #pragma unroll
-        for (int T = 0; T < 4; T++) po[c][T] = 0.f;
+        for (int T = 0; T < TS; T++) po[c][T] = 0.f;
 #pragma unroll
       for (int M = 0; M < 4; M++) {
         f32x4 wq[3];
@@ -398,7 +465,7 @@ __global__ __launch_bounds__(MShape<C>::kWaves * 64) void shade_bwd_mfma_kernel(
         for (int c = 0; c < 3; c++)
           wq[c] = *reinterpret_cast<const f32x4 *>(lds_w + S::oW2Q + ((M * 4 + q) * 3 + c) * 4);
 #pragma unroll
-        for (int T = 0; T < 4; T++)
+        for (int T = 0; T < TS; T++)
 #pragma unroll
           for (int r = 0; r < 4; r++) {
             const float p = relu(pre[M][T][r]);
@@ -409,7 +476,7 @@ __global__ __launch_bounds__(MShape<C>::kWaves * 64) void shade_bwd_mfma_kernel(
       }
       const float b2q = lds_w[S::oB2 + q];
 #pragma unroll
-      for (int T = 0; T < 4; T++) {
+      for (int T = 0; T < TS; T++) {
         const float s0 = mfma16(1.f, po[0][T], zero4)[0];
         const float s1 = mfma16(1.f, po[1][T], zero4)[0];
         const float s2 = mfma16(1.f, po[2][T], zero4)[0];
@@ -428,33 +495,77 @@ __global__ __launch_bounds__(MShape<C>::kWaves * 64) void shade_bwd_mfma_kernel(
     // d_o[c][s], both on the registers that hold relu(pre): d_o of all three colours comes back from
     // the LDS tile (lane (q, m) computed colour q only); d_hid replaces pre
     {
-      float doc[3][4];
+      float doc[3][TS];
 #pragma unroll
       for (int c = 0; c < 3; c++)
 #pragma unroll
-        for (int T = 0; T < 4; T++) doc[c][T] = DS[c * kP + 16 * T + m];
+        for (int T = 0; T < TS; T++) doc[c][T] = DS[c * kP + 16 * T + m];
 #pragma unroll
       for (int M = 0; M < 4; M++) {
         f32x4 wq[3];
 #pragma unroll
         for (int c = 0; c < 3; c++)
           wq[c] = *reinterpret_cast<const f32x4 *>(lds_w + S::oW2Q + ((M * 4 + q) * 3 + c) * 4);
+        auto d_hid = [&](int r) {
 #pragma unroll
-        for (int r = 0; r < 4; r++) {
-#pragma unroll
-          for (int c = 0; c < 3; c++) {
-            float t = doc[c][0] * pre[M][0][r];
-#pragma unroll
-            for (int T = 1; T < 4; T++) t = __builtin_fmaf(doc[c][T], pre[M][T][r], t);
-            acc_w2[c][M][r] += t;
-          }
-#pragma unroll
-          for (int T = 0; T < 4; T++) {
+          for (int T = 0; T < TS; T++) {
             float dh = wq[0][r] * doc[0][T];
             dh = __builtin_fmaf(wq[1][r], doc[1][T], dh);
             dh = __builtin_fmaf(wq[2][r], doc[2][T], dh);
             pre[M][T][r] = (pre[M][T][r] > 0.f) ? dh : 0.f;
           }
+        };
+        if constexpr (kW2R == 4) {
+#pragma unroll
+          for (int r = 0; r < 4; r++) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+              float t = doc[c][0] * pre[M][0][r];
+#pragma unroll
+              for (int T = 1; T < TS; T++) t = __builtin_fmaf(doc[c][T], pre[M][T][r], t);
+              acc_w2[c][M][r] += t;
+            }
+            d_hid(r);
+          }
+        } else {
+          float t4[3][4];
+#pragma unroll
+          for (int r = 0; r < 4; r++)
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+              float t = doc[c][0] * pre[M][0][r];
+#pragma unroll
+              for (int T = 1; T < TS; T++) t = __builtin_fmaf(doc[c][T], pre[M][T][r], t);
+              t4[c][r] = t;
+            }
+          // three steps of a reduce-scatter over the quarter, 6 accumulators instead of 48: lane m
+          // keeps rows r = 2 [m >= 8] + r' and adds them from lane 15 - m (DPP row_mirror), which
+          // keeps the other two; then row r = m >> 2 from lane (m & 8) + 7 - (m & 7)
+          // (row_half_mirror); then, over a pair of M-tiles, M = 2 M' + [m & 3 >= 2] from lane
+          // m ^ 2 (quad_perm [2,3,0,1]).  The rest of the sum, over lanes m and m ^ 1, at the flush.
+          const bool lo = m < 8, lo2 = (m & 7) < 4, lo3 = (m & 3) < 2;
+#pragma unroll
+          for (int c = 0; c < 3; c++) {
+            float h2[2];
+#pragma unroll
+            for (int r = 0; r < 2; r++) {
+              const float own = lo ? t4[c][r] : t4[c][r + 2];
+              const float give = lo ? t4[c][r + 2] : t4[c][r];
+              h2[r] = own + dpp_move<0x140>(give);
+            }
+            const float own = lo2 ? h2[0] : h2[1];
+            const float give = lo2 ? h2[1] : h2[0];
+            const float h1 = own + dpp_move<0x141>(give);
+            if (M % 2 == 0) {
+              w2_even[c] = h1;
+            } else {
+              const float own3 = lo3 ? w2_even[c] : h1;
+              const float give3 = lo3 ? h1 : w2_even[c];
+              acc_w2[c][M / 2][0] += own3 + dpp_move<0x4e>(give3);
+            }
+          }
+#pragma unroll
+          for (int r = 0; r < 4; r++) d_hid(r);
         }
       }
     }
@@ -465,7 +576,7 @@ __global__ __launch_bounds__(MShape<C>::kWaves * 64) void shade_bwd_mfma_kernel(
     {
       auto put = [&](int M) {
 #pragma unroll
-        for (int T = 0; T < 4; T++)
+        for (int T = 0; T < TS; T++)
 #pragma unroll
           for (int r = 0; r < 4; r++) PS[(4 * q + r) * kP + 16 * T + m] = pre[M][T][r];
       };
@@ -473,9 +584,9 @@ __global__ __launch_bounds__(MShape<C>::kWaves * 64) void shade_bwd_mfma_kernel(
       wave_lds_sync();
 #pragma unroll
       for (int M = 0; M < 4; M++) {
-        f32x4 a4[4];
+        f32x4 a4[TS];
 #pragma unroll
-        for (int u = 0; u < 4; u++)
+        for (int u = 0; u < TS; u++)
           a4[u] = *reinterpret_cast<const f32x4 *>(PS + m * kP + 16 * u + 4 * q);
         wave_lds_sync();
         if (M < 3) {
@@ -483,7 +594,7 @@ __global__ __launch_bounds__(MShape<C>::kWaves * 64) void shade_bwd_mfma_kernel(
           wave_lds_sync();
         }
 #pragma unroll
-        for (int u = 0; u < 4; u++) {
+        for (int u = 0; u < TS; u++) {
           acc_b1[M] += (a4[u][0] + a4[u][1]) + (a4[u][2] + a4[u][3]);
           f32x4 b4[2];
 #pragma unroll
@@ -502,25 +613,27 @@ __global__ __launch_bounds__(MShape<C>::kWaves * 64) void shade_bwd_mfma_kernel(
     // 128 products of the last three phases, ~4 K cycles, cover the latency -- asking one phase
     // earlier, 260 products ahead, measured the same within noise, 1.45-1.50 ms, and spills the WIDE
     // instantiation)
-    load_inputs(st + wave_count, eB, img, dir);
-    issue_fence();
+    if constexpr (TS == 4) {
+      load_inputs(st + wave_count, eB, img, dir);
+      issue_fence();
+    }
 
     phase_fence_v<V>();
     // ---- d_X rows 0..15 = w1[:, 0:16]^T . d_hid   (the SH inputs carry no gradient)
-    float g_logit[4];  // in flight during the products below
+    float g_logit[TS];  // in flight during the products below
 #pragma unroll
-    for (int T = 0; T < 4; T++) g_logit[T] = ld_row(d_logit, offS[T]);
+    for (int T = 0; T < TS; T++) g_logit[T] = ld_row(d_logit, offS[T]);
     issue_fence();
-    f32x4 dX[4];
+    f32x4 dX[TS];
 #pragma unroll
-    for (int T = 0; T < 4; T++) dX[T] = zero4;
+    for (int T = 0; T < TS; T++) dX[T] = zero4;
 #pragma unroll
     for (int M = 0; M < 4; M++)
 #pragma unroll
       for (int r = 0; r < 4; r++) {
         const float a = W(S::oWA5 + M * 4 + r);
 #pragma unroll
-        for (int T = 0; T < 4; T++) dX[T] = mfma16(a, pre[M][T][r], dX[T]);
+        for (int T = 0; T < TS; T++) dX[T] = mfma16(a, pre[M][T][r], dX[T]);
       }
 
     phase_fence_v<V>();
@@ -530,15 +643,19 @@ __global__ __launch_bounds__(MShape<C>::kWaves * 64) void shade_bwd_mfma_kernel(
     // from every wave of the chip, serialises in L2: 6.9 ms instead of 1.7 ms per launch.)
     if (has_emb) {
       const int img0 = __builtin_amdgcn_readfirstlane(img_cur[0]);
-      if (__all(img_cur[0] == img0 && img_cur[1] == img0 && img_cur[2] == img0 && img_cur[3] == img0)) {
+      bool one_img = true;
+#pragma unroll
+      for (int T = 0; T < TS; T++) one_img = one_img && img_cur[T] == img0;
+      if (__all(one_img)) {
         if (img0 != emb_img) {
           flush_emb();
           emb_img = img0;
         }
-        acc_emb += (dX[0] + dX[1]) + (dX[2] + dX[3]);  // clamped samples carry zeros
+        if constexpr (TS == 4) acc_emb += (dX[0] + dX[1]) + (dX[2] + dX[3]);  // clamped samples carry zeros
+        else acc_emb += dX[0] + dX[1];
       } else {
 #pragma unroll
-        for (int T = 0; T < 4; T++)
+        for (int T = 0; T < TS; T++)
 #pragma unroll
           for (int r = 0; r < 4; r++)
             if (vT[T]) atomicAdd(g_emb + (int64_t)img_cur[T] * kOut1 + 4 * q + r, dX[T][r]);
@@ -546,9 +663,9 @@ __global__ __launch_bounds__(MShape<C>::kWaves * 64) void shade_bwd_mfma_kernel(
     }
 
     // ---- d_h: the head outputs' gradient; row 0 is the density logit's
-    f32x4 d_h[4];
+    f32x4 d_h[TS];
 #pragma unroll
-    for (int T = 0; T < 4; T++) {
+    for (int T = 0; T < TS; T++) {
       d_h[T] = dX[T];
       if (q == 0) d_h[T][0] = vT[T] ? g_logit[T] : 0.f;
       acc_bh += d_h[T];
@@ -560,17 +677,17 @@ __global__ __launch_bounds__(MShape<C>::kWaves * 64) void shade_bwd_mfma_kernel(
     // ---- d_enc[c][s] = w_h^T . d_h
 #pragma unroll
     for (int M = 0; M < kM6; M++) {
-      f32x4 de[4];
+      f32x4 de[TS];
 #pragma unroll
-      for (int T = 0; T < 4; T++) de[T] = zero4;
+      for (int T = 0; T < TS; T++) de[T] = zero4;
 #pragma unroll
       for (int r = 0; r < 4; r++) {
         const float a = W(S::oWA6 + M * 4 + r);
 #pragma unroll
-        for (int T = 0; T < 4; T++) de[T] = mfma16(a, d_h[T][r], de[T]);
+        for (int T = 0; T < TS; T++) de[T] = mfma16(a, d_h[T][r], de[T]);
       }
 #pragma unroll
-      for (int T = 0; T < 4; T++)
+      for (int T = 0; T < TS; T++)
         if (vT[T]) {
 #pragma unroll
           for (int r = 0; r < 4; r++)
@@ -583,7 +700,7 @@ __global__ __launch_bounds__(MShape<C>::kWaves * 64) void shade_bwd_mfma_kernel(
     // ---- d w_h[i][c] += sum_s d_h[i][s] enc[c][s]
     wave_lds_sync();
 #pragma unroll
-    for (int u = 0; u < 4; u++) {
+    for (int u = 0; u < TS; u++) {
       const f32x4 a4 = *reinterpret_cast<const f32x4 *>(PS + m * kP + 16 * u + 4 * q);
 #pragma unroll
       for (int N = 0; N < kM6; N++) {
@@ -595,8 +712,8 @@ __global__ __launch_bounds__(MShape<C>::kWaves * 64) void shade_bwd_mfma_kernel(
     wave_lds_sync();
   }
 
-  // ---- flush the accumulators: the four waves' sums meet in wave 0 first (its LDS tile regions are
-  // free now), so a workgroup sends one set of atomics instead of four -- with few strides per wave
+  // ---- flush the accumulators: the waves' sums meet in wave 0 first (the LDS is free now), so a
+  // workgroup sends one set of atomics instead of one per wave -- with few strides per wave
   // (a 512-ray training batch: 8) the 4 160 atomics of every wave on the same 2 400 addresses were a
   // third of the kernel
   if (has_emb) flush_emb();
@@ -609,12 +726,14 @@ __global__ __launch_bounds__(MShape<C>::kWaves * 64) void shade_bwd_mfma_kernel(
         for (int N = 0; N < 2; N++)
 #pragma unroll
           for (int r = 0; r < 4; r++) acc_w1[M][N][r] = fn(acc_w1[M][N][r], i++);
-#pragma unroll
-        for (int c = 0; c < 3; c++)
-#pragma unroll
-          for (int r = 0; r < 4; r++) acc_w2[c][M][r] = fn(acc_w2[c][M][r], i++);
         acc_b1[M] = fn(acc_b1[M], i++);
       }
+#pragma unroll
+      for (int c = 0; c < 3; c++)
+#pragma unroll
+        for (int M = 0; M < kW2M; M++)
+#pragma unroll
+          for (int r = 0; r < kW2R; r++) acc_w2[c][M][r] = fn(acc_w2[c][M][r], i++);
 #pragma unroll
       for (int N = 0; N < kM6; N++)
 #pragma unroll
@@ -623,16 +742,42 @@ __global__ __launch_bounds__(MShape<C>::kWaves * 64) void shade_bwd_mfma_kernel(
       for (int r = 0; r < 4; r++) acc_bh[r] = fn(acc_bh[r], i++);
       acc_b2 = fn(acc_b2, i++);
     };
-    static_assert(S::kAccs * 64 <= S::kWaveFloats, "the accumulators fit a wave's tile region");
-    wave_lds_sync();
-    if (wave != 0) each_acc([&](float v, int i) { tile[i * 64 + lane] = v; return v; });
-    __syncthreads();
-    if (wave != 0) return;
+    if constexpr (TS == 4) {  // one round through the waves' own tiles
+      static_assert(S::kAccs * 64 <= S::kWaveFloats, "the accumulators fit a wave's tile region");
+      wave_lds_sync();
+      if (wave != 0) each_acc([&](float v, int i) { tile[i * 64 + lane] = v; return v; });
+      __syncthreads();
+      if (wave == 0) {
 #pragma unroll
-    for (int w = 1; w < S::kWaves; w++) {
-      const float * other = lds_all + S::kWFloats + w * S::kWaveFloats;
-      each_acc([&](float v, int i) { return v + other[i * 64 + lane]; });
+        for (int w = 1; w < S::kWaves; w++) {
+          const float * other = lds_all + S::kWFloats + w * S::kWaveFloats;
+          each_acc([&](float v, int i) { return v + other[i * 64 + lane]; });
+        }
+      }
+    } else {
+      // in rounds of kMeetRegs registers through the whole LDS (the weights are dead too); the sums
+      // meet in the order wave 1, 2, .. as in one round
+      constexpr int R = S::kMeetRegs;
+#pragma unroll
+      for (int rd = 0; rd < S::kMeetRounds; rd++) {
+        const int lo = rd * R, hi = lo + R;
+        __syncthreads();  // every wave is out of its loop / wave 0 has read the previous round
+        if (wave != 0)
+          each_acc([&](float v, int i) {
+            if (i >= lo && i < hi) lds_all[((wave - 1) * R + i - lo) * 64 + lane] = v;
+            return v;
+          });
+        __syncthreads();
+        if (wave == 0) {
+#pragma unroll
+          for (int w = 1; w < S::kWaves; w++)
+            each_acc([&](float v, int i) {
+              return (i >= lo && i < hi) ? v + lds_all[((w - 1) * R + i - lo) * 64 + lane] : v;
+            });
+        }
+      }
     }
+    if (wave != 0) return;
   }
 #pragma unroll
   for (int M = 0; M < 4; M++) {
@@ -642,12 +787,19 @@ __global__ __launch_bounds__(MShape<C>::kWaves * 64) void shade_bwd_mfma_kernel(
       for (int r = 0; r < 4; r++)
         atomicAdd(g_w1 + (16 * M + 4 * q + r) * kIn2 + 16 * N + m, acc_w1[M][N][r]);
 #pragma unroll
-    for (int c = 0; c < 3; c++)
+    for (int c = 0; c < 3; c++) {
+      if constexpr (kW2R == 4) {
 #pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const float t = quarter_sum(acc_w2[c][M][r]);  // over the quarter's 16 sample columns
-        if (m == 0) atomicAdd(g_w2 + c * kHid + 16 * M + 4 * q + r, t);
+        for (int r = 0; r < 4; r++) {
+          const float t = quarter_sum(acc_w2[c][M][r]);  // over the quarter's 16 sample columns
+          if (m == 0) atomicAdd(g_w2 + c * kHid + 16 * M + 4 * q + r, t);
+        }
+      } else if (M % 2 == 0) {  // lanes m and m ^ 1 hold M-tile M + [m & 3 >= 2], row m >> 2
+        float t = acc_w2[c][M / 2][0];
+        t += __shfl_xor(t, 1);
+        if ((m & 1) == 0) atomicAdd(g_w2 + c * kHid + 16 * (M + ((m >> 1) & 1)) + 4 * q + (m >> 2), t);
       }
+    }
     {
       float t = acc_b1[M];  // lane (q, m): neuron 16M+m, this quarter's samples
       t += __shfl_xor(t, 16);
@@ -861,6 +1013,10 @@ __global__ __launch_bounds__(W * 64) void shade_fwd_mfma_kernel(
 namespace f2n_detail
 {
 
+// Below this many samples per launch the one-wave form is faster (few strides per wave; measured
+// in NOTES.md section 6)
+constexpr int64_t kShadeBwdTwoWavesMinSamples = F2N_SHADE_BWD_TWO_WAVES_MIN_SAMPLES;
+
 bool shade_bwd_mfma_supports(int C, int64_t n)
 {
   // (per-sample offsets such as 12 s for d_rgb stay 32-bit: n < 2^28; the row offsets C n 4 are
@@ -875,27 +1031,34 @@ int launch_shade_bwd_mfma(
   float * g_w_h, float * g_b_h, float * g_w1, float * g_b1, float * g_w2, float * g_b2,
   float * g_app_emb, int64_t n, hipStream_t stream)
 {
-  const int64_t n_strides = (n + 63) / 64;
   // the embedding rows are read as float4
   if (app_emb && (reinterpret_cast<uintptr_t>(app_emb) & 15u)) return F2N_E_INVALID_ARG;
   if (n >= ((int64_t)1 << 28)) return F2N_E_UNSUPPORTED;  // 32-bit per-sample offsets
   const bool wide = (int64_t)C * n >= ((int64_t)1 << 30);   // row offsets beyond 32 bits
-  const int variant = f2n_get_option(F2N_OPT_SHADE_VARIANT);
-#define F2N_LAUNCH_MFMA_V(CC, VV, WW)                                                                \
+  // form: 0 by size, 1 one wave per SIMD, 2 / 3 two waves (phase-fenced / phases mixed)
+  const int waves = f2n_get_option(F2N_OPT_SHADE_BWD_WAVES);
+  const int ts = (waves == 1 || (waves == 0 && n < kShadeBwdTwoWavesMinSamples)) ? 4 : 2;
+  // scheduling (V & 1: phases may mix).  One wave: mixed unless F2N_OPT_SHADE_VARIANT = 1, as in
+  // round 3.  Two waves: fenced (1.30 against 1.33 ms per 8.2 M samples) unless SHADE_BWD_WAVES = 3;
+  // the WIDE kernels are always fenced there (mixed, they spill).
+  const bool mixed = (ts == 4) ? f2n_get_option(F2N_OPT_SHADE_VARIANT) != 1 : waves == 3;
+#define F2N_LAUNCH_MFMA_V(CC, VV, WW, TT)                                                            \
   {                                                                                                  \
-    constexpr int kW = MShape<CC>::kWaves;                                                             \
-    const unsigned grid = (unsigned)std::min<int64_t>(256, (n_strides + kW - 1) / kW);               \
+    using MS = MShape<CC, TT>;                                                                       \
+    const int64_t n_strides = (n + MS::kStride - 1) / MS::kStride;                                   \
+    const unsigned grid = (unsigned)std::min<int64_t>(256, (n_strides + MS::kWaves - 1) / MS::kWaves); \
     hipLaunchKernelGGL(                                                                              \
-      (shade_bwd_mfma_kernel<CC, VV, WW>), dim3(grid), dim3(kW * 64), 0, stream, enc_cm, dirs,        \
-      sample_img, w_h, b_h, w1, b1, w2, b2, app_emb, d_logit, d_rgb, d_enc_cm, g_w_h, g_b_h, g_w1,    \
-      g_b1, g_w2, g_b2, g_app_emb, n);                                                               \
+      (shade_bwd_mfma_kernel<CC, VV, WW, TT>), dim3(grid), dim3(MS::kWaves * 64), 0, stream, enc_cm, \
+      dirs, sample_img, w_h, b_h, w1, b1, w2, b2, app_emb, d_logit, d_rgb, d_enc_cm, g_w_h, g_b_h,   \
+      g_w1, g_b1, g_w2, g_b2, g_app_emb, n);                                                         \
   }
+#define F2N_LAUNCH_MFMA_T(CC, TT)                            \
+  if (wide) F2N_LAUNCH_MFMA_V(CC, (TT == 2 ? 0 : 1), true, TT) \
+  else if (mixed) F2N_LAUNCH_MFMA_V(CC, 1, false, TT)        \
+  else F2N_LAUNCH_MFMA_V(CC, 0, false, TT)
 #define F2N_LAUNCH_MFMA(CC)                                \
-  if (wide) F2N_LAUNCH_MFMA_V(CC, 1, true)                 \
-  else switch (variant) {                                  \
-      case 1: F2N_LAUNCH_MFMA_V(CC, 0, false) break;       \
-      default: F2N_LAUNCH_MFMA_V(CC, 1, false) break;      \
-    }
+  if (ts == 2) { F2N_LAUNCH_MFMA_T(CC, 2) }                \
+  else { F2N_LAUNCH_MFMA_T(CC, 4) }
   switch (C) {
     case 8: F2N_LAUNCH_MFMA(8) break;
     case 16: F2N_LAUNCH_MFMA(16) break;
@@ -904,6 +1067,7 @@ int launch_shade_bwd_mfma(
     default: return F2N_E_UNSUPPORTED;
   }
 #undef F2N_LAUNCH_MFMA
+#undef F2N_LAUNCH_MFMA_T
 #undef F2N_LAUNCH_MFMA_V
   return f2n_launch_status();
 }

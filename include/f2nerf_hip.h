@@ -49,7 +49,8 @@ const char * f2n_status_string(int status);
  * f2n_set_option returns the previous value, or F2N_E_INVALID_ARG for an unknown key / value. */
 #define F2N_OPT_SHADE_FWD 0     /* 0 matrix-core forward, 1 one-sample-per-lane vector kernel       */
 #define F2N_OPT_SHADE_BWD 1     /* 0 matrix-core backward, 1 vector (VALU + LDS) backward           */
-#define F2N_OPT_SHADE_VARIANT 2 /* matrix-core backward: 0 phases may overlap, 1 phase-fenced; the
+#define F2N_OPT_SHADE_VARIANT 2 /* matrix-core backward at one wave per SIMD: 0 phases may overlap, 1
+                                  phase-fenced (the two-wave form: F2N_OPT_SHADE_BWD_WAVES); the
                                   matrix-core FORWARD: 0 four waves per SIMD, 3 three, 2 two          */
 #define F2N_OPT_RAYTILE 3       /* samples per ray tile of f2n_hash_fwd_raytile: 0 auto, 16, 32     */
 #define F2N_OPT_HASH_BWD 4      /* f2n_hash_bwd route: 0 auto, 1 global atomics, 2 LDS-sliced       */
@@ -67,7 +68,14 @@ const char * f2n_status_string(int status);
 #define F2N_OPT_RAY_ORDER 9     /* Renderer dense first pass: 0 rays bucketed into pixel-compact bundles
                                   (f2n_ray_keys) and results handed back in caller order, 1 rays
                                   rendered in the caller's order; same results bit for bit          */
-#define F2N_OPT_COUNT 10
+#define F2N_OPT_SHADE_BWD_WAVES 10 /* matrix-core backward: 0 chosen by size (two waves per SIMD in
+                                  32-sample strides from F2N_SHADE_BWD_TWO_WAVES_MIN_SAMPLES samples
+                                  per launch, one below), 1 one wave per SIMD in 64-sample strides
+                                  (round 3), 2 two waves per SIMD, 3 two waves with the phases of a
+                                  stride mixed (not fenced; WIDE kernels stay fenced); same d_enc bit
+                                  for bit, parameter gradients within the order of float sums       */
+#define F2N_SHADE_BWD_TWO_WAVES_MIN_SAMPLES (3 << 19)
+#define F2N_OPT_COUNT 11
 int f2n_set_option(int key, int value);
 int f2n_get_option(int key);
 
