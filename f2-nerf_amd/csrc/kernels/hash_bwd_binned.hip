@@ -304,7 +304,9 @@ __global__ __launch_bounds__(kBinBlock) void hash_bwd_bin_kernel(
   auto comb_slot = [](uint32_t r) { return (r ^ (r >> __builtin_ctz(kSlots))) & (kSlots - 1u); };
   auto comb_index = [](uint32_t slot, int k) { return (uint32_t)k * (kSlots + (F > 1 ? 1u : 0u)) + slot; };
   __shared__ __attribute__((aligned(16))) uint32_t queue[kBinQueueWords];
-  __shared__ uint32_t qcount[kMaxBuckets];
+  // queue counters, one set per level parity: the set of level l + 1 is zeroed during level l, so
+  // that no barrier is needed between the zeroing and the first enqueue of a level
+  __shared__ uint32_t qcount[2][kMaxBuckets];
   __shared__ unsigned long long sat_acc[8 * F];  // cell (0,0,0): exact sums per corner and channel
   // [0] combine the coming level, [1] non-zero contributions of this level, [2] lanes of the tile
   // whose level-0 cell equals the previous sample's, [3] lanes that have a previous sample,
@@ -329,13 +331,25 @@ __global__ __launch_bounds__(kBinBlock) void hash_bwd_bin_kernel(
   const uint32_t bmask = (1u << a.bshift) - 1u;
   const int64_t n_tiles_g = a.n_tiles * a.groups;
 
-  float g_cur[F], g_nxt[F];
+  // A point's gradient channels are addressed with a 32-bit element offset from a wave-uniform level
+  // base (the host keeps a launch's offsets below 2^32): a 64-bit per-lane pointer kept across the
+  // level loop was the pair of registers that spilled.  (Laundered at every use: the compiler would
+  // otherwise form the 64-bit address once, before the level loop, and keep it.)
+  uint32_t goff = (uint32_t)pc * (uint32_t)a.g_ld_point;
+  auto load_grad = [&](int lv, float * g) {
+    uint32_t o = goff;
+    asm volatile("" : "+v"(o));
 #pragma unroll
-  for (int k = 0; k < F; k++) g_cur[k] = grad_out[pc * a.g_ld_point + (int64_t)k * a.g_ld_chan];
+    for (int k = 0; k < F; k++) g[k] = (grad_out + (int64_t)(lv * F + k) * a.g_ld_chan)[o];
+  };
+  float g_cur[F], g_a[F], g_b[F];
+  load_grad(0, g_cur);
 
   const bool comb_allowed = a.combine && a.groups == 1;
   if (threadIdx.x < 7) comb_state[threadIdx.x] = 0u;
   if (threadIdx.x < 32) queue[threadIdx.x] = 0u;  // prologue: bit set of the tile's level-0 cells
+  if (threadIdx.x < kMaxBuckets) qcount[0][threadIdx.x] = 0u;
+  if (SAT && threadIdx.x < 8 * F) sat_acc[threadIdx.x] = 0ull;  // (re-zeroed by its readers)
   __syncthreads();
   if (comb_allowed) {
     // how many consecutive samples share a level-0 cell?  (points are ray-major: the lanes of a wave
@@ -428,19 +442,29 @@ __global__ __launch_bounds__(kBinBlock) void hash_bwd_bin_kernel(
       x = pts[3 * pc + 0];
       y = pts[3 * pc + 1];
       z = pts[3 * pc + 2];
-#pragma unroll
-      for (int k = 0; k < F; k++) g_cur[k] = grad_out[pc * a.g_ld_point + (int64_t)k * a.g_ld_chan];
+      goff = (uint32_t)pc * (uint32_t)a.g_ld_point;
+      load_grad(0, g_cur);
     }
   }
-
-
-  for (int l = 0; l < a.L; l++) {
-    {
-      const int ln = (l + 1 < a.L) ? l + 1 : l;  // clamped: the last prefetch re-reads level L-1
+  // The gradient ring is two levels deep: level l + 2's channels are requested at the top of level l
+  // and taken over just before level l + 1's flush, so a wait for them never includes the stores of
+  // the flush just issued.  The two buffers swap roles from level to level, hence the level body
+  // below is instantiated twice (a register copy of a load in flight would wait for it).  Everything
+  // loaded before the loop is waited for here, once: a value still in flight at the loop entry makes
+  // the compiler wait for it at the loop header of every level -- behind the last flush's stores.
+  load_grad(a.L > 1 ? 1 : 0, g_a);
+  asm volatile("" : "+v"(x), "+v"(y), "+v"(z));
 #pragma unroll
-      for (int k = 0; k < F; k++)
-        g_nxt[k] = grad_out[pc * a.g_ld_point + (int64_t)(ln * F + k) * a.g_ld_chan];
-    }
+  for (int k = 0; k < F; k++) asm volatile("" : "+v"(g_cur[k]));
+  // (one round of plain binning per level: only F = 8 ever needs more, see bin_plan)
+  const int n_groups = F >= 8 ? a.groups : 1;
+
+
+  // g_n1: level l + 1's gradient, requested at the top of level l - 1; g_n2: free until the top of l
+  // qc: this level's queue counters (zero), qc_next: the next level's (zeroed here)
+  auto level = [&](const int l, float (&g_n1)[F], float (&g_n2)[F], uint32_t * qc, uint32_t * qc_next)
+                 __attribute__((always_inline)) {
+    load_grad(l + 2 < a.L ? l + 2 : a.L - 1, g_n2);  // clamped: the last requests re-read level L-1
     float gk[F];
     bool any = false;
 #pragma unroll
@@ -448,14 +472,14 @@ __global__ __launch_bounds__(kBinBlock) void hash_bwd_bin_kernel(
       gk[k] = round_f16(g_cur[k] * a.grad_scale);
       any |= (gk[k] != 0.f);
     }
-    // The prefetched gradient is taken over BEFORE this level's flush issues its stores.  vmcnt counts
-    // loads and stores alike, in order: left at the top of the next level, the wait for these
-    // loads was a wait for every store of the flush as well.
+    // Level l + 1's gradient is taken over BEFORE this level's flush issues its stores.  vmcnt counts
+    // loads and stores alike, in issue order; the compiler's wait here is vmcnt(F) for the last of
+    // these loads: level l + 2's loads stay in flight, and the stores it retires are level l - 1's,
+    // issued a whole level body ago -- never those of the flush just issued.
     auto take_prefetch = [&]() {
-      __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): only the prefetch (and older stores) are out
 #pragma unroll
       for (int k = 0; k < F; k++) {
-        g_cur[k] = g_nxt[k];
+        g_cur[k] = g_n1[k];
         asm volatile("" : "+v"(g_cur[k]));  // (the copy happens here, not after the stores)
       }
     };
@@ -486,7 +510,7 @@ __global__ __launch_bounds__(kBinBlock) void hash_bwd_bin_kernel(
     // stage one record in its bucket's LDS queue (layout capacity `cap`), or apply it directly
     auto enqueue = [&](uint32_t r, const uint32_t * val, int cap) {
       const uint32_t bucket = r >> a.bshift;
-      const uint32_t slot = atomicAdd(&qcount[bucket], 1u);
+      const uint32_t slot = atomicAdd(&qc[bucket], 1u);
       if (slot < (uint32_t)cap)
         // (bucket < 64, cap * KW <= 32768: a 24-bit multiply is full rate, v_mul_lo_u32 a quarter)
         store_record<F>(queue + __umul24(bucket, (uint32_t)(cap * KW)), cap, slot, r & bmask, val);
@@ -522,7 +546,7 @@ __global__ __launch_bounds__(kBinBlock) void hash_bwd_bin_kernel(
           const uint32_t b = (uint32_t)wave + (uint32_t)kWaves * u;
           const uint2 * src = reinterpret_cast<const uint2 *>(queue) + __umul24(b, (uint32_t)cap);
           uint2 * dst = reinterpret_cast<uint2 *>(region0) + __umul24(b, (uint32_t)a.qcap);
-          const uint32_t asked = qcount[b];
+          const uint32_t asked = qc[b];
           const uint2 r0 = src[i0], r1 = src[min(i0 + 16u, (uint32_t)cap - 1u)];  // (inside the queue)
           const uint32_t c = min(asked, (uint32_t)cap);
           // a queue overflowed (its records left as global atomics): this tile's contributions pile
@@ -550,7 +574,7 @@ __global__ __launch_bounds__(kBinBlock) void hash_bwd_bin_kernel(
 #pragma unroll
           for (int u = 0; u < 4; u++) {
             const int b = b0 + u * kWaves;
-            cnt[u] = b < a.n_buckets ? min(qcount[b], (uint32_t)cap) : 0u;
+            cnt[u] = b < a.n_buckets ? min(qc[b], (uint32_t)cap) : 0u;
             const uint2 * q = reinterpret_cast<const uint2 *>(queue + (size_t)b * cap * KW);
 #pragma unroll
             for (int k = 0; k < 4; k++)
@@ -569,7 +593,7 @@ __global__ __launch_bounds__(kBinBlock) void hash_bwd_bin_kernel(
         }
       } else {
         for (int b = wave; b < a.n_buckets; b += kWaves) {
-          const uint32_t cnt = min(qcount[b], (uint32_t)cap);
+          const uint32_t cnt = min(qc[b], (uint32_t)cap);
           copy_records<F, true>(
             queue + (size_t)b * cap * KW, cap, region0 + (size_t)b * a.qcap * KW, a.qcap, 0u, cnt, lane);
         }
@@ -578,16 +602,14 @@ __global__ __launch_bounds__(kBinBlock) void hash_bwd_bin_kernel(
       if (lane < kMaxBuckets / kWaves) {
         const int b = wave + kWaves * lane;
         if (b < a.n_buckets)
-          ws_counts[((size_t)l * a.n_buckets + b) * n_tiles_g + tile_g] = min(qcount[b], (uint32_t)cap);
+          ws_counts[((size_t)l * a.n_buckets + b) * n_tiles_g + tile_g] = min(qc[b], (uint32_t)cap);
       }
     };
 
-    __syncthreads();  // the previous level's flush has read the queues and counters
+    __syncthreads();  // the previous level's flush has read the queues and its counters
     const bool comb = comb_state[0] != 0u;
-    if (threadIdx.x < kMaxBuckets) qcount[threadIdx.x] = 0u;
-    if (SAT && threadIdx.x < 8 * F) sat_acc[threadIdx.x] = 0ull;
-    if (threadIdx.x == 0) comb_state[1] = 0u;
-    __syncthreads();
+    // (qc, sat_acc and comb_state[1] are zero already: zeroed a level ahead, or by their last reader)
+    if (threadIdx.x < kMaxBuckets) qc_next[threadIdx.x] = 0u;  // last read by the previous level
 
     if (comb) {
       // ---- combine: equal rows of this tile are summed in LDS before they become records --------
@@ -678,10 +700,11 @@ __global__ __launch_bounds__(kBinBlock) void hash_bwd_bin_kernel(
       // while the records saved (measured here, scaled by the ~1.6x more distinct rows a finer level
       // has) outweigh the cost of the mode.  Finer levels only get worse: once off, it stays off.
       if (wave == 0) {
-        uint32_t e = (lane < a.n_buckets) ? qcount[lane] : 0u;
+        uint32_t e = (lane < a.n_buckets) ? qc[lane] : 0u;
         e = (uint32_t)__builtin_amdgcn_readlane(wave_incl_scan_i32((int)e), 63);
         if (lane == 0) {
           const uint32_t n_nz_tile = comb_state[1];
+          comb_state[1] = 0u;  // (for the next combined level)
           if (a.stats) {
             atomicAdd(a.stats + 4 * l + 0, 1u);
             atomicAdd(a.stats + 4 * l + 1, n_nz_tile);
@@ -710,16 +733,16 @@ __global__ __launch_bounds__(kBinBlock) void hash_bwd_bin_kernel(
       // instead and leave as a handful of f16 pieces per tile and level.  (Only for tables that take the
       // split pass: the extra barrier and checks cost the single-level bench workload 0.3 ms per chunk,
       // and there a hot slice merely fills its regions.)
-      for (int g = 0; g < a.groups; g++) {
+      for (int g = 0; g < n_groups; g++) {
         if (g > 0) {
           __syncthreads();  // the previous round's flush has read the queues
-          if (threadIdx.x < kMaxBuckets) qcount[threadIdx.x] = 0u;
+          if (threadIdx.x < kMaxBuckets) qc[threadIdx.x] = 0u;
           __syncthreads();
         }
         // (the tile's POINTS take turns; letting its corners take turns instead -- every thread busy
         // in every round, the hash computed once per round -- was measured and lost: 59.8 vs 58.1 ms
         // per 2^24 points of config C5)
-        if (active && (int)((threadIdx.x * (unsigned)a.groups) / kBinBlock) == g) {
+        if (active && (int)((threadIdx.x * (unsigned)n_groups) / kBinBlock) == g) {
           const LevelParams lp = load_level(primes, bias, mul, l);
           corner_rows_and_weights<POW2>(x, y, z, lp, a.T, row, w);
           const bool sat3 = SAT && fmaf(x, lp.mul, lp.bx) < 0.f && fmaf(y, lp.mul, lp.by) < 0.f &&
@@ -747,7 +770,7 @@ __global__ __launch_bounds__(kBinBlock) void hash_bwd_bin_kernel(
           }
         }
         __syncthreads();
-        if (SAT && g == a.groups - 1) {
+        if (SAT && g == n_groups - 1) {
           // corner d of cell (0,0,0): thread d re-expresses its F sums as f16 pieces
           if (threadIdx.x < 8) {
             const int d = (int)threadIdx.x;
@@ -756,6 +779,7 @@ __global__ __launch_bounds__(kBinBlock) void hash_bwd_bin_kernel(
 #pragma unroll
             for (int k = 0; k < F; k++) {
               S[k] = (long long)sat_acc[d * F + k];
+              sat_acc[d * F + k] = 0ull;  // (for the next level)
               nz |= (S[k] != 0);
             }
             if (nz) {
@@ -789,9 +813,13 @@ __global__ __launch_bounds__(kBinBlock) void hash_bwd_bin_kernel(
           __syncthreads();
         }
         if (g == 0) take_prefetch();
-        flush(a.qcap, tile * a.groups + g, comb_allowed);
+        flush(a.qcap, tile * n_groups + g, comb_allowed);
       }
     }
+  };
+  for (int l = 0; l < a.L; l += 2) {
+    level(l, g_a, g_b, qcount[0], qcount[1]);
+    if (l + 1 < a.L) level(l + 1, g_b, g_a, qcount[1], qcount[0]);
   }
 }
 
@@ -1396,6 +1424,15 @@ extern "C" int f2n_hash_bwd_binned(
   if (workspace_bytes <= 0) return F2N_E_INVALID_ARG;
   BinPlan pl = bin_plan(n, L, F, T, workspace_bytes);
   if (!pl.ok) return F2N_E_UNSUPPORTED;
+  if (F <= 4 && pl.groups != 1) return F2N_E_UNSUPPORTED;  // pass A assumes one round (n_groups)
+  // pass A addresses a point's gradient with a 32-bit element offset: a launch's points may span at
+  // most 2^32 - 1 elements of it (point-major gradients of L F floats per point: 2^32 / (L F) points)
+  if (g_ld_point < 0 || g_ld_chan < 0) return F2N_E_UNSUPPORTED;
+  if (g_ld_point > 0) {
+    const int64_t max_tiles = (int64_t)(0xffffffffull / (uint64_t)g_ld_point) / kBinBlock;
+    if (max_tiles < 1) return F2N_E_UNSUPPORTED;
+    pl.chunk_tiles = std::min(pl.chunk_tiles, max_tiles);
+  }
   hipStream_t s = (hipStream_t)stream;
   const bool p2 = is_pow2(T);
   const float inv = 1.f / grad_scale;
