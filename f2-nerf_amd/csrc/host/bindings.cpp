@@ -249,6 +249,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def("set_dense_first_pass", [](Renderer & r, int m) { r.options_.dense_first_pass = m; })
     .def("set_speculate_dense", [](Renderer & r, bool f) { r.options_.speculate_dense = f; })
     .def("set_pixel_tiles", [](Renderer & r, int b) { r.options_.pixel_tiles = b; })
+    .def("set_fused_ray_grad", [](Renderer & r, bool f) { r.options_.fused_ray_grad = f; },
+         "rays that require grad take the fused path: see RendererOptions::fused_ray_grad")
     .def("set_margin_min_samples", [](Renderer & r, int64_t n) { r.options_.margin_min_samples = n; })
     .def("set_deferred_check", [](Renderer & r, bool f) { r.options_.deferred_check = f; },
          "no host read in render(): see RendererOptions::deferred_check")

@@ -38,6 +38,65 @@ Rays launch_gen_rays(
   return rays;
 }
 
+// launch_gen_rays with a backward to the pose (the intrinsics are constants, as in the reference's
+// pose optimisation, src/localizer.cpp:142-167).  ij empty = pixel first_pixel + r of a `width`-wide
+// image (undefined tensors cannot pass through apply()).  No cam_idx: every ray uses pose 0, or ray
+// r pose r.
+class GenRaysFn : public torch::autograd::Function<GenRaysFn>
+{
+public:
+  static torch::autograd::variable_list forward(
+    torch::autograd::AutogradContext * ctx, Tensor pose, Tensor intrinsic, Tensor ij,
+    int64_t first_pixel, int64_t width, int64_t n)
+  {
+    if (ij.numel() == 0) ij = Tensor();
+    Rays rays = launch_gen_rays(pose, intrinsic, Tensor(), ij, first_pixel, (int)width, n);
+    ctx->save_for_backward({f2n::dev_f32(intrinsic, "intrinsic"), ij});
+    ctx->saved_data["first_pixel"] = first_pixel;
+    ctx->saved_data["width"] = width;
+    ctx->saved_data["pose_shape"] = pose.sizes().vec();
+    return {rays.origins, rays.dirs};
+  }
+
+  static torch::autograd::variable_list backward(
+    torch::autograd::AutogradContext * ctx, torch::autograd::variable_list grad)
+  {
+    auto saved = ctx->get_saved_variables();
+    const Tensor & K = saved[0];
+    const Tensor & ij = saved[1];
+    const auto shape = ctx->saved_data["pose_shape"].toIntVector();
+    const int64_t n_cams = shape[0];
+    const int pose_ld = (int)(shape[1] * 4);
+    const auto opt = K.options();
+    const Tensor & ref = grad[0].defined() ? grad[0] : grad[1];
+    const int64_t n = ref.defined() ? ref.size(0) : 0;
+    Tensor d_o = grad[0].defined() ? f2n::dev_f32(grad[0], "grad rays_o") : torch::zeros({n, 3}, opt);
+    Tensor d_d = grad[1].defined() ? f2n::dev_f32(grad[1], "grad rays_d") : torch::zeros({n, 3}, opt);
+    Tensor d_pose = torch::empty(shape, opt);
+    Tensor ws = torch::empty({f2n_gen_rays_bwd_workspace_floats(n)}, opt);
+    f2n::check(
+      f2n_gen_rays_bwd(
+        K.data_ptr<float>(), n_cams, f2n::iptr(ij), ctx->saved_data["first_pixel"].toInt(),
+        (int)ctx->saved_data["width"].toInt(), d_o.data_ptr<float>(), d_d.data_ptr<float>(),
+        d_pose.data_ptr<float>(), pose_ld, ws.data_ptr<float>(), n, f2n::current_stream(K)),
+      "f2n_gen_rays_bwd");
+    return {d_pose, Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+  }
+};
+
+// rays of one view (ij undefined) or of the given pixels, through GenRaysFn when the pose wants a
+// gradient
+Rays gen_rays(
+  const Tensor & pose, const Tensor & intrinsic, const Tensor & ij, int64_t first_pixel, int width,
+  int64_t n)
+{
+  if (!(torch::GradMode::is_enabled() && pose.requires_grad()))
+    return launch_gen_rays(pose, intrinsic, Tensor(), ij, first_pixel, width, n);
+  const Tensor pixels = ij.defined() ? ij : torch::empty({0}, f2n::int_on(pose.device()));
+  auto out = GenRaysFn::apply(pose, intrinsic.detach(), pixels, first_pixel, (int64_t)width, n);
+  return {out[0], out[1]};
+}
+
 }  // namespace
 
 Rays get_rays_from_pose(const Tensor & pose, const Tensor & intrinsic, const Tensor & ij)
@@ -48,7 +107,7 @@ Rays get_rays_from_pose(const Tensor & pose, const Tensor & intrinsic, const Ten
     pose.size(0) == 1 || pose.size(0) == n, "pose batch must be 1 or N (src/rays.cpp broadcast)");
   // the reference converts whatever ij holds with .to(kFloat32); pixel indices are exact either way
   Tensor ij32 = f2n::dev_i32(ij.to(torch::kInt32), "ij");
-  return launch_gen_rays(pose, intrinsic, Tensor(), ij32, 0, 1, n);
+  return gen_rays(pose, intrinsic, ij32, 0, 1, n);
 }
 
 Rays get_view_rays(const Tensor & pose, const Tensor & intrinsic, int h, int w)
@@ -56,7 +115,7 @@ Rays get_view_rays(const Tensor & pose, const Tensor & intrinsic, int h, int w)
   Tensor p = pose.dim() == 2 ? pose.unsqueeze(0) : pose;
   Tensor k = intrinsic.dim() == 2 ? intrinsic.unsqueeze(0) : intrinsic;
   TORCH_CHECK(p.size(0) == 1 && h > 0 && w > 0, "get_view_rays: one pose, a positive image size");
-  return launch_gen_rays(p, k, Tensor(), Tensor(), 0, w, (int64_t)h * w);
+  return gen_rays(p, k, Tensor(), 0, w, (int64_t)h * w);
 }
 
 std::tuple<Rays, Tensor, Tensor> sample_random_rays(

@@ -13,6 +13,12 @@ struct alignas(32) Rays
   torch::Tensor dirs;
 };
 
+// Gradients: get_rays_from_pose and get_view_rays are differentiable in the pose when grad mode is on
+// and pose.requires_grad() (the reference's Localizer optimises a [3,4] pose through render_image,
+// src/localizer.cpp:142-167): the backward (f2n_gen_rays_bwd) returns d(pose) in the pose's own shape
+// ([B,3,4] / [B,4,4], or [3,4] / [4,4] through get_view_rays), row 3 of a [4,4] pose zero, the sum
+// over the rays in a fixed order.  The intrinsics are constants: they never receive a gradient.
+
 // pose [B,3,4] (or [B,4,4]), intrinsic [B,3,3], ij [N,2] = (row, col), float or integer; B == 1 or
 // B == N.  Pixel centres (+0.5), camera looks down -z, y up.  One kernel (f2n_gen_rays).
 Rays get_rays_from_pose(
@@ -25,6 +31,7 @@ Rays get_view_rays(const torch::Tensor & pose, const torch::Tensor & intrinsic, 
 // Dataset::sample_random_rays (src/dataset.cpp:150-171) with everything on the device: camera and
 // pixel indices are drawn there, each ray reads its own camera from the pose / intrinsic tables
 // (no index_select, no host randint + copy).  images: optional [E, h, w, 3] for the ground truth.
+// Not differentiated: the rays carry no gradient to `poses` (training samples are data).
 // Returns {rays, gt_colors [n,3] (undefined without images), cam_indices [n] i32}.
 std::tuple<Rays, torch::Tensor, torch::Tensor> sample_random_rays(
   const torch::Tensor & poses, const torch::Tensor & intrinsics, int h, int w, int64_t batch_size,

@@ -95,7 +95,10 @@ RenderResult Renderer::render(
   }
   const bool rays_need_grad =
     torch::GradMode::is_enabled() && (rays_o.requires_grad() || rays_d.requires_grad());
-  RenderResult res = (options_.fused && !rays_need_grad)
+  const int64_t C = scene_field_->options_.n_levels * scene_field_->options_.n_channels;
+  const bool fused_grad = options_.fused_ray_grad && options_.fused_shade &&
+                          f2n::shade_supported(C) && scene_field_->options_.mlp_out_dim == 16;
+  RenderResult res = (options_.fused && (!rays_need_grad || fused_grad))
                        ? render_fused(rays_o, rays_d, emb_idx, mode, noise, bg_color)
                        : render_op_by_op(rays_o, rays_d, emb_idx, mode, noise, bg_color);
   if (options_.check_finite) CHECK(std::isfinite(res.colors.mean().item<float>()));
@@ -120,6 +123,11 @@ RenderResult Renderer::render_fused(
   void * stream = f2n::current_stream(rays_o);
   Hash3DAnchored & field = *scene_field_;
   const int L = (int)field.options_.n_levels, F = (int)field.options_.n_channels;
+  // rays that carry a gradient (options_.fused_ray_grad): the kernels work on the detached copies
+  // above, shade_and_composite hands the encoding's gradient back to these
+  const bool rays_need_grad =
+    torch::GradMode::is_enabled() && (rays_o_raw.requires_grad() || rays_d_raw.requires_grad());
+  const Rays grad_rays = rays_need_grad ? Rays{rays_o_raw, rays_d_raw} : Rays{};
 
   const int64_t C = (int64_t)L * F;
   const bool dense_ok = options_.fused_shade && f2n::shade_supported(C) &&
@@ -127,12 +135,13 @@ RenderResult Renderer::render_fused(
   const bool dense = dense_ok && (options_.dense_first_pass == 1 ||
                                   (options_.dense_first_pass < 0 && last_kept_fraction_ > 0.4f));
   if (dense) {
-    // bg_color that carries a gradient stays on the caller's order (the bucketed route detaches it)
+    // bg_color or rays that carry a gradient stay on the caller's order (the bucketed route
+    // detaches them)
     const bool bucket = n_rays >= options_.ray_order_min_rays &&
-                        f2n_get_option(F2N_OPT_RAY_ORDER) == 0 &&
+                        f2n_get_option(F2N_OPT_RAY_ORDER) == 0 && !rays_need_grad &&
                         !(torch::GradMode::is_enabled() && bg_color.requires_grad());
     return bucket ? render_dense_bucketed(rays_o, rays_d, emb_idx, mode, noise, bg_color)
-                  : render_dense(rays_o, rays_d, emb_idx, mode, noise, bg_color);
+                  : render_dense(rays_o, rays_d, emb_idx, mode, noise, bg_color, grad_rays);
   }
 
   SampleResultFlex kept;
@@ -176,7 +185,7 @@ RenderResult Renderer::render_fused(
         step, stream),
       "f2n_sample_compact");
   }
-  return shade_and_composite(kept, emb_idx, mode, bg_color);
+  return shade_and_composite(kept, emb_idx, mode, bg_color, grad_rays);
 }
 
 // ---- bucketed dense pass ---------------------------------------------------------------------------
@@ -247,6 +256,84 @@ private:
         f2n_gather_segments(
           f2n::fptr(w), f2n::iptr(src_b), w_out.data_ptr<float>(), f2n::iptr(dst_b), m, n, s),
         "f2n_gather_segments");
+  }
+};
+
+// Identity on the encoding of the kept samples whose backward also forms the rays' gradient from
+// the encoding's (f2n_hash_rays_grad).  The encoding's gradient is handed on untouched, so the table
+// gradient (Hash3DAnchoredFunction) and everything else upstream see exactly what they see without
+// it.  pts / t / bounds: the kept samples (raw positions) and their segments, as the sampler made
+// them from these rays.
+class RayGradFn : public torch::autograd::Function<RayGradFn>
+{
+public:
+  static torch::autograd::variable_list forward(
+    torch::autograd::AutogradContext * ctx, Tensor enc, Tensor rays_o, Tensor rays_d, Tensor pts,
+    Tensor t, Tensor bounds, torch::IValue hash3d_info)
+  {
+    Hash3DAnchored * field = hash3d_info.toCustomClass<Hash3DAnchoredInfo>()->hash3d_;
+    ctx->saved_data["hash3d_info"] = hash3d_info;
+    ctx->saved_data["n_rays"] = rays_o.size(0);
+    ctx->save_for_backward(
+      {f2n::dev_f32(pts.detach(), "kept pts"), f2n::dev_f32(t.detach(), "kept t"),
+       f2n::dev_i32(bounds, "kept bounds"), f2n::dev_f32(rays_d.detach(), "rays_d"),
+       field->table_f16()});
+    return {enc};
+  }
+
+  static torch::autograd::variable_list backward(
+    torch::autograd::AutogradContext * ctx, torch::autograd::variable_list grad)
+  {
+    const Tensor & g_enc = grad[0];
+    const bool want_o = ctx->needs_input_grad(1), want_d = ctx->needs_input_grad(2);
+    Tensor d_o, d_d;
+    if (want_o || want_d) {
+      auto sv = ctx->get_saved_variables();
+      const Tensor &pts = sv[0], &t = sv[1], &bounds = sv[2], &rays_d = sv[3], &table16 = sv[4];
+      const int64_t n_rays = ctx->saved_data["n_rays"].toInt();
+      d_o = torch::empty({n_rays, 3}, rays_d.options());
+      d_d = torch::empty({n_rays, 3}, rays_d.options());
+      if (!g_enc.defined()) {
+        d_o.zero_();
+        d_d.zero_();
+      } else {
+        Hash3DAnchored * field =
+          ctx->saved_data["hash3d_info"].toCustomClass<Hash3DAnchoredInfo>()->hash3d_;
+        const int64_t n = pts.size(0);
+        const int L = (int)field->options_.n_levels, F = (int)field->options_.n_channels;
+        const int64_t C = (int64_t)L * F;
+        // (point, channel) strides of the incoming [n, C] gradient, read as Hash3DAnchoredFunction
+        // reads it (the shade backward hands over a view of channel-major storage)
+        Tensor g = g_enc;
+        TORCH_CHECK(g.is_cuda() && g.scalar_type() == torch::kFloat32, "encoding grad dtype");
+        int64_t ld_point, ld_chan;
+        if (g.stride(1) == 1 && g.stride(0) >= C) {
+          ld_point = g.stride(0);
+          ld_chan = 1;
+        } else if (g.stride(0) == 1 && g.stride(1) >= n) {
+          ld_point = 1;
+          ld_chan = g.stride(1);
+        } else {
+          g = g.contiguous();
+          ld_point = C;
+          ld_chan = 1;
+        }
+        void * stream = f2n::current_stream(pts);
+        f2n::ScopedKernelTimer timer("hash_rays_grad", stream, (double)n);
+        f2n::check(
+          f2n_hash_rays_grad(
+            pts.data_ptr<float>(), t.data_ptr<float>(), bounds.data_ptr<int32_t>(),
+            rays_d.data_ptr<float>(), reinterpret_cast<const uint16_t *>(table16.data_ptr()),
+            field->prim_pool_.data_ptr<int32_t>(), field->bias_pool_.data_ptr<float>(),
+            field->level_mul_.data_ptr<float>(), g.data_ptr<float>(), ld_point, ld_chan,
+            d_o.data_ptr<float>(), d_d.data_ptr<float>(), (int)n_rays, L, F,
+            (uint32_t)field->local_size_, field->level_stride_, 128.f /* hash_3d_anchored.cu:190 */,
+            stream),
+          "f2n_hash_rays_grad");
+      }
+    }
+    return {g_enc, want_o ? d_o : Tensor(), want_d ? d_d : Tensor(), Tensor(), Tensor(), Tensor(),
+            Tensor()};
   }
 };
 
@@ -324,7 +411,7 @@ RenderResult Renderer::render_dense_bucketed(
 
 RenderResult Renderer::render_dense(
   const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-  const Tensor & noise, const Tensor & bg_color)
+  const Tensor & noise, const Tensor & bg_color, const Rays & grad_rays)
 {
   const int n_rays = (int)rays_o.size(0);
   const int S = pts_sampler_->options_.max_samples;
@@ -386,13 +473,14 @@ RenderResult Renderer::render_dense(
     last_kept_fraction_ = 1.f;
   }
   if (options_.deferred_check && options_.fused_shade)
-    return shade_and_composite(all, emb_idx, mode, bg_color, enc_all_cm, contracted_all);
+    return shade_and_composite(
+      all, emb_idx, mode, bg_color, grad_rays, enc_all_cm, contracted_all);
   const bool may_guess = options_.speculate_dense && last_kept_fraction_ >= 1.f && n_all > 0;
   const int64_t kMarginMinSamples = options_.margin_min_samples;
   if (may_guess && n_all >= kMarginMinSamples) {
     Tensor near_threshold = torch::zeros({1}, iopt);
     RenderResult guess = shade_and_composite(
-      all, emb_idx, mode, bg_color, enc_all_cm, contracted_all, &near_threshold, S);
+      all, emb_idx, mode, bg_color, grad_rays, enc_all_cm, contracted_all, &near_threshold, S);
     if (survivors_.wait() == 0) {
       last_n_samples_ = n_all;
       last_kept_fraction_ = 1.f;
@@ -424,7 +512,8 @@ RenderResult Renderer::render_dense(
   bool guessed = false;
   if (may_guess && n_all < kMarginMinSamples) {
     // enqueued BEFORE the host waits for the count: the GPU does not idle across the read
-    guess = shade_and_composite(all, emb_idx, mode, bg_color, enc_all_cm, contracted_all);
+    guess =
+      shade_and_composite(all, emb_idx, mode, bg_color, grad_rays, enc_all_cm, contracted_all);
     guessed = true;
   }
   const int64_t n_kept = survivors_.wait();
@@ -462,7 +551,8 @@ RenderResult Renderer::render_dense(
         "f2n_compact_rows_cm");
     }
   }
-  return shade_and_composite(kept, emb_idx, mode, bg_color, enc_kept_cm, contracted_kept);
+  return shade_and_composite(
+    kept, emb_idx, mode, bg_color, grad_rays, enc_kept_cm, contracted_kept);
 }
 
 bool Renderer::deferred_check_ok()
@@ -476,7 +566,8 @@ bool Renderer::deferred_check_ok()
 // Second pass on the survivors (renderer.cpp:92-118).
 RenderResult Renderer::shade_and_composite(
   const SampleResultFlex & kept, const Tensor & emb_idx, RunningMode mode, const Tensor & bg_color,
-  const Tensor & enc_cm, const Tensor & contracted, Tensor * near_threshold, int64_t grid_samples)
+  const Rays & grad_rays, const Tensor & enc_cm, const Tensor & contracted, Tensor * near_threshold,
+  int64_t grid_samples)
 {
   const int64_t n_kept = kept.pts.size(0);
   const int64_t C = scene_field_->options_.n_levels * scene_field_->options_.n_channels;
@@ -484,6 +575,15 @@ RenderResult Renderer::shade_and_composite(
     // hash encode -> one kernel for field head + embedding + SH + colour MLP -> composite
     Tensor enc = enc_cm.defined() ? scene_field_->encode_cached(kept.pts, enc_cm, contracted)
                                   : scene_field_->encode(kept.pts);
+    if (grad_rays.origins.defined()) {
+      // enc passes through; the backward turns d(enc) into d(rays) (and, with the field frozen,
+      // is what makes the shade backward form d(enc) at all)
+      auto info = torch::make_intrusive<Hash3DAnchoredInfo>();
+      info->hash3d_ = scene_field_.get();
+      enc = RayGradFn::apply(
+        enc, grad_rays.origins, grad_rays.dirs, kept.pts, kept.t, kept.pts_idx_bounds,
+        torch::IValue(info))[0];
+    }
     Tensor sample_img;
     if (mode == RunningMode::TRAIN)
       sample_img = CustomOps::ScatterIdx((int)n_kept, kept.pts_idx_bounds, emb_idx);

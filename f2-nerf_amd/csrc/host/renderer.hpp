@@ -11,7 +11,8 @@
 //                     samples, and compositing is one kernel per direction;
 //   op-by-op          the reference's own sequence (sample all, query all, AccumulateSum, where,
 //                     4x index, query survivors, Sum...) on the drop-in operators.  Used when rays
-//                     carry gradients (pose optimisation) and as the cross-check of the fused path.
+//                     carry gradients (pose optimisation; unless RendererOptions::fused_ray_grad)
+//                     and as the cross-check of the fused path.
 #pragma once
 
 #include <memory>
@@ -20,6 +21,7 @@
 
 #include "hash_3d_anchored.hpp"
 #include "points_sampler.hpp"
+#include "rays.hpp"
 #include "sh_shader.hpp"
 
 namespace f2n
@@ -89,6 +91,13 @@ struct RendererOptions
   // (F2N_OPT_RAY_ORDER = 1 switches it off).  The sort, permutes and gathers cost ~0.1 ms per chunk
   // (measured: +3.5 % at 65536-ray chunks of S = 128, L = 16; -15 % at 8192-ray chunks of S = 64, L = 4).
   int64_t ray_order_min_rays = 65536;
+  // Rays that require grad (pose optimisation, reference src/localizer.cpp:142-167) take the fused
+  // path too when the fused per-sample network applies (fused_shade, L*F in {8,16,32,64}, a 16-wide
+  // field head): the kernels run on detached copies, the encoding's gradient d(enc) that the shade
+  // backward forms anyway is turned into d(rays_o), d(rays_d) by one kernel (f2n_hash_rays_grad), and
+  // the table, MLP and embedding gradients take exactly the kernels they take without it.  Off: such
+  // rays go op by op.  The bucketed dense route is not used for them.
+  bool fused_ray_grad = false;
 };
 
 class Renderer : public torch::nn::Module
@@ -136,9 +145,10 @@ private:
   RenderResult render_fused(
     const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
     const Tensor & noise, const Tensor & bg_color);
+  // grad_rays: the caller's rays when they carry a gradient (fused_ray_grad), else undefined
   RenderResult render_dense(
     const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-    const Tensor & noise, const Tensor & bg_color);
+    const Tensor & noise, const Tensor & bg_color, const Rays & grad_rays = {});
   RenderResult render_dense_bucketed(
     const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
     const Tensor & noise, const Tensor & bg_color);
@@ -147,8 +157,9 @@ private:
     const Tensor & noise, const Tensor & bg_color);
   RenderResult shade_and_composite(
     const SampleResultFlex & kept, const Tensor & emb_idx, RunningMode mode,
-    const Tensor & bg_color, const Tensor & enc_cm = Tensor(), const Tensor & contracted = Tensor(),
-    Tensor * near_threshold = nullptr, int64_t grid_samples = 0);
+    const Tensor & bg_color, const Rays & grad_rays, const Tensor & enc_cm = Tensor(),
+    const Tensor & contracted = Tensor(), Tensor * near_threshold = nullptr,
+    int64_t grid_samples = 0);
 };
 
 namespace f2n

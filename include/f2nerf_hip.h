@@ -160,6 +160,28 @@ int f2n_hash_bwd_binned(
 int f2n_contract_fwd(const float * pts, float * x, int64_t n, void * stream);
 int f2n_contract_bwd(const float * pts, const float * dx, float * dpts, int64_t n, void * stream);
 
+/* Gradient of the rays from the gradient of their samples' encoding, for rays that carry one (pose
+ * optimisation, src/localizer.cpp:142-167): the point gradient of Hash3DAnchoredBackwardKernel
+ * (quirk Q5, src/hash_3d_anchored.cu:138-143, same per-term f16 roundings as f2n_hash_bwd), the
+ * contraction's backward (f2n_contract_bwd) and the backward of pts = o + t d/|d|
+ * (src/points_sampler.cpp:24,44), summed per ray -- one launch, no table gradient, no atomics, the
+ * same bits on every run.
+ *   pts        [n,3] f32 RAW (uncontracted) positions of the kept samples, t [n] their depths
+ *   bounds     [n_rays, 2] segment of each ray in pts / t / grad_out
+ *   rays_d     [n_rays, 3] the ray directions as given to the sampler (not normalised)
+ *   table_f16 .. level_stride, grad_scale: as f2n_hash_bwd; grad_out element (p, c) at
+ *              grad_out[p*g_ld_point + c*g_ld_chan]
+ *   d_rays_o, d_rays_d [n_rays, 3] overwritten; a ray with an empty segment gets zeros.
+ * Not formed, as in the reference: the path through dt = |pts_k - pts_k-1| (quirk Q7; it depends on
+ * d only through |d/|d||, which the normalisation's Jacobian annihilates) and a gradient through the
+ * SH directions (src/sh_shader.cu:105-115 has no backward for them). */
+int f2n_hash_rays_grad(
+  const float * pts, const float * t, const int32_t * bounds, const float * rays_d,
+  const uint16_t * table_f16, const int32_t * primes, const float * bias, const float * mul,
+  const float * grad_out, int64_t g_ld_point, int64_t g_ld_chan, float * d_rays_o,
+  float * d_rays_d, int n_rays, int L, int F, uint32_t T, int64_t level_stride, float grad_scale,
+  void * stream);
+
 /* ------------------------------------------------------------------ SH encode (row A6) -------- */
 
 /* SHKernel<<<ceil(n/512), 512>>> -- src/sh_shader.cu:11-115.  dirs [n,3] -> out [n, degree^2],
@@ -220,6 +242,21 @@ int f2n_gen_rays(
   const float * poses, int pose_ld, const float * intrinsics, int64_t n_cams,
   const int32_t * cam_idx, const int32_t * ij, int64_t first_pixel, int width, float * rays_o,
   float * rays_d, int64_t n, void * stream);
+
+/* Backward of f2n_gen_rays with respect to the poses (the matmul and expand of src/rays.cpp:7-28,
+ * differentiated by autograd in the reference's pose optimisation, src/localizer.cpp:142-167), for
+ * constant intrinsics.  Addressing as f2n_gen_rays (no cam_idx: n_cams is 1 or n):
+ *   d_poses [n_cams] blocks of pose_ld floats, overwritten:
+ *     d_pose[i][3] = sum_r d_rays_o[r][i],  d_pose[i][j] = sum_r d_rays_d[r][i] * v_r[j] (j < 3),
+ *     v_r the camera-frame direction of ray r as f2n_gen_rays forms it; row 3 of a [4,4] block = 0.
+ *   n_cams == 1: a sum over all n rays in a fixed partition and order (the same bits on every run);
+ *   n_cams == n: one pose per ray, no sum.
+ *   workspace: f2n_gen_rays_bwd_workspace_floats(n) floats of device memory, contents undefined. */
+int64_t f2n_gen_rays_bwd_workspace_floats(int64_t n);
+int f2n_gen_rays_bwd(
+  const float * intrinsics, int64_t n_cams, const int32_t * ij, int64_t first_pixel, int width,
+  const float * d_rays_o, const float * d_rays_d, float * d_poses, int pose_ld, float * workspace,
+  int64_t n, void * stream);
 
 /* PtsSampler::get_samples (about 20 ATen launches) -- src/points_sampler.cpp:20-64.
  *   noise   [n_rays, S] f32 step multipliers (TRAIN: U[0.5,1.5)), or NULL for all-ones (VALIDATE)

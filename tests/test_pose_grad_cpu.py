@@ -1,0 +1,104 @@
+"""CPU-side checks of the pose-gradient entry points (f2n_hash_rays_grad, f2n_gen_rays_bwd): they
+parse from the header, are exported, reject NULL and negative arguments before touching a GPU, and
+every instantiation of their kernels compiles, with the project's own HIP flags, without scratch or
+spills.  Cross-compiled for gfx950; needs hipcc, not a GPU."""
+import ctypes
+import importlib
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+build = importlib.import_module("f2-nerf_amd._build")
+SRC = os.path.join(build.KERNEL_DIR, "pose_grad.hip")
+NEW = ("f2n_hash_rays_grad", "f2n_gen_rays_bwd", "f2n_gen_rays_bwd_workspace_floats")
+
+
+def test_entry_points_parse_and_export(capi):
+    decls = capi.parse_header()
+    for name in NEW:
+        assert name in decls, name
+    cdll = ctypes.CDLL(capi.LIB_PATH)
+    for name in NEW:
+        assert hasattr(cdll, name), name
+    # the additions are backward-compatible: the ABI version stays
+    assert capi.lib().cdll.f2n_abi_version() == 2
+    ret, params = decls["f2n_gen_rays_bwd_workspace_floats"]
+    assert ret is ctypes.c_int64 and [t for t, _ in params] == [ctypes.c_int64]
+
+
+def test_workspace_is_positive_and_bounded(capi):
+    fn = capi.lib().cdll.f2n_gen_rays_bwd_workspace_floats
+    assert fn(0) >= 12 and fn(0) % 12 == 0
+    assert fn(1) >= 12
+    assert fn(1 << 16) >= 12 and fn(1 << 16) % 12 == 0
+    assert fn(1 << 30) <= 12 * 4096  # the partition is capped: the workspace stays small
+
+
+def test_null_and_negative_arguments_rejected(capi):
+    cdll = capi.lib().cdll
+    fake = ctypes.c_void_p(0x1000)  # never dereferenced: validation answers first
+    null = None
+    # f2n_hash_rays_grad(pts, t, bounds, rays_d, table, primes, bias, mul, g, ld_p, ld_c, d_o, d_d,
+    #                    n_rays, L, F, T, level_stride, grad_scale, stream)
+    good = [fake] * 9 + [1, 1 << 10, fake, fake, 4, 16, 2, 1 << 19, 1 << 19, 128.0, None]
+    for i in list(range(9)) + [11, 12]:
+        args = list(good)
+        args[i] = null
+        assert cdll.f2n_hash_rays_grad(*args) == -1, i
+    for i, bad in ((9, -1), (10, -1), (13, -1), (14, 0), (14, 33), (17, -2), (18, 100.0),
+                   (18, 0.0)):
+        args = list(good)
+        args[i] = bad
+        assert cdll.f2n_hash_rays_grad(*args) == -1, (i, bad)
+    args = list(good)
+    args[15] = 3
+    assert cdll.f2n_hash_rays_grad(*args) == -3  # F not in 1, 2, 4, 8
+    # f2n_gen_rays_bwd(K, n_cams, ij, first_pixel, width, d_o, d_d, d_poses, pose_ld, ws, n, stream)
+    good = [fake, 1, null, 0, 8, fake, fake, fake, 12, fake, 64, None]
+    for i in (0, 5, 6, 7, 9):
+        args = list(good)
+        args[i] = null
+        assert cdll.f2n_gen_rays_bwd(*args) == -1, i
+    for i, bad in ((1, 0), (1, 5), (3, -1), (4, 0), (8, 9), (10, -1)):
+        args = list(good)
+        args[i] = bad
+        assert cdll.f2n_gen_rays_bwd(*args) == -1, (i, bad)
+
+
+def _resource_usage(tmp_path):
+    cmd = [build.HIPCC, *build.HIP_FLAGS, "-I", build.INCLUDE_DIR, "-I", build.KERNEL_DIR,
+           "--offload-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", SRC,
+           "-o", str(tmp_path / "pose_grad.o")]
+    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert res.returncode == 0, res.stdout[-4000:]
+    kernels, cur = {}, None
+    for line in res.stdout.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            cur = m.group(1)
+            kernels[cur] = {}
+            continue
+        m = re.search(r"remark: ([^:\[]+?)(?: \[[^\]]*\])?: (\d+)", line)
+        if cur and m:
+            kernels[cur][m.group(1).strip()] = int(m.group(2))
+    return kernels
+
+
+def test_kernels_have_no_scratch_or_spills(tmp_path):
+    if not os.path.exists(build.HIPCC) and shutil.which("hipcc") is None:
+        pytest.fail("hipcc not found: the build needs it too")
+    kernels = _resource_usage(tmp_path)
+    rays_grad = [k for k in kernels if "hash_rays_grad_kernel" in k]
+    # F in {1, 2, 4, 8} x power-of-two T or not
+    shapes = {re.search(r"kernelILi(\d)ELb(\d)", k).groups() for k in rays_grad}
+    assert shapes == {(f, p) for f in "1248" for p in "01"}, sorted(shapes)
+    pose = [k for k in kernels if "gen_rays_bwd" in k]
+    assert len(pose) == 3, pose
+    for name in rays_grad + pose:
+        r = kernels[name]
+        assert r.get("ScratchSize") == 0, (name, r)
+        assert r.get("VGPRs Spill") == 0 and r.get("AGPRs Spill", 0) == 0, (name, r)
+        assert r.get("SGPRs Spill", 0) == 0, (name, r)
