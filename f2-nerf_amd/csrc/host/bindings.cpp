@@ -6,6 +6,7 @@
 #include "fused_adam.hpp"
 #include "hash_3d_anchored.hpp"
 #include "kernel_timer.hpp"
+#include "localizer.hpp"
 #include "points_sampler.hpp"
 #include "ragged_ops.hpp"
 #include "rays.hpp"
@@ -67,6 +68,13 @@ struct AdamHandle
 {
   std::shared_ptr<torch::optim::Optimizer> opt;
 };
+
+py::list particle_list(const std::vector<Particle> & particles)
+{
+  py::list l;
+  for (const Particle & p : particles) l.append(py::make_tuple(p.pose, p.weight));
+  return l;
+}
 
 }  // namespace
 
@@ -307,6 +315,119 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     return py::make_tuple(
       p.n_images, p.height, p.width, p.intrinsic, p.normalizing_center, p.normalizing_radius);
   });
+
+  // ---- Localizer ---------------------------------------------------------------------------------
+  m.def(
+    "perturb_poses",
+    [](const Tensor & pose, const Tensor & noise, const std::array<float, 6> & sigmas) {
+      return f2n::perturb_poses(pose, noise, sigmas);
+    },
+    py::arg("pose"), py::arg("noise"), py::arg("sigmas"),
+    "f2n_perturb_poses: sigmas = (pos x, y, z in the NeRF frame, rot x, y, z in degrees)");
+  m.def("pose_scores", &f2n::pose_scores, py::arg("colors"), py::arg("image"), py::arg("ij"),
+        "f2n_pose_scores -> (loss [P], weights [P])");
+  m.def("average_pose", &f2n::average_pose, py::arg("poses"), py::arg("weights"),
+        "f2n_average_pose -> [3,4]");
+
+  py::class_<LocalizerParam>(m, "LocalizerParam")
+    .def(py::init<>())
+    .def_readwrite("train_result_dir", &LocalizerParam::train_result_dir)
+    .def_readwrite("render_pixel_num", &LocalizerParam::render_pixel_num)
+    .def_readwrite("noise_position_x", &LocalizerParam::noise_position_x)
+    .def_readwrite("noise_position_y", &LocalizerParam::noise_position_y)
+    .def_readwrite("noise_position_z", &LocalizerParam::noise_position_z)
+    .def_readwrite("noise_rotation_x", &LocalizerParam::noise_rotation_x)
+    .def_readwrite("noise_rotation_y", &LocalizerParam::noise_rotation_y)
+    .def_readwrite("noise_rotation_z", &LocalizerParam::noise_rotation_z)
+    .def_readwrite("resize_factor", &LocalizerParam::resize_factor);
+
+  py::class_<Localizer, std::shared_ptr<Localizer>>(m, "Localizer")
+    .def(py::init<const LocalizerParam &>(), py::arg("param"),
+         "from param.train_result_dir: inference_params.yaml + checkpoints/latest/renderer.pt")
+    .def(
+      py::init<const LocalizerParam &, std::shared_ptr<Renderer>, const Tensor &, int, int,
+               const Tensor &, float>(),
+      py::arg("param"), py::arg("renderer"), py::arg("intrinsic"), py::arg("height"),
+      py::arg("width"), py::arg("center"), py::arg("radius"))
+    .def("render_image", &Localizer::render_image, py::call_guard<py::gil_scoped_release>())
+    .def(
+      "optimize_pose_by_random_search",
+      [](Localizer & l, const Tensor & pose, const Tensor & image, int64_t n, float coeff,
+         const c10::optional<Tensor> & noise) {
+        std::vector<Particle> particles;
+        {
+          py::gil_scoped_release no_gil;
+          particles = l.optimize_pose_by_random_search(pose, image, n, coeff, opt_tensor(noise));
+        }
+        return particle_list(particles);
+      },
+      py::arg("initial_pose"), py::arg("image"), py::arg("particle_num"), py::arg("noise_coeff"),
+      py::arg("noise") = py::none(), "-> [(pose [3,4], weight)] * particle_num")
+    .def(
+      "random_search",
+      [](Localizer & l, const Tensor & pose, const Tensor & image, int64_t n, float coeff,
+         const c10::optional<Tensor> & noise) {
+        py::gil_scoped_release no_gil;
+        return l.random_search(pose, image, n, coeff, opt_tensor(noise));
+      },
+      py::arg("initial_pose"), py::arg("image"), py::arg("particle_num"), py::arg("noise_coeff"),
+      py::arg("noise") = py::none(), "-> (poses [P,3,4], weights [P]) on the device, no host read")
+    .def(
+      "optimize_pose_by_differential",
+      [](Localizer & l, const Tensor & pose, const Tensor & image, int64_t iterations) {
+        // loss.backward() runs the autograd engine, which must not be entered holding the GIL
+        py::gil_scoped_release no_gil;
+        return l.optimize_pose_by_differential(pose, image, iterations);
+      },
+      py::arg("initial_pose"), py::arg("image"), py::arg("iteration_num"))
+    .def(
+      "evaluate_poses",
+      [](Localizer & l, const Tensor & poses, const Tensor & image, const c10::optional<Tensor> & ij) {
+        py::gil_scoped_release no_gil;
+        return l.evaluate_poses(poses, image, opt_tensor(ij));
+      },
+      py::arg("poses"), py::arg("image"), py::arg("ij") = py::none())
+    .def(
+      "evaluate_poses_full",
+      [](Localizer & l, const Tensor & poses, const Tensor & image, const c10::optional<Tensor> & ij) {
+        Localizer::PoseScores s;
+        {
+          py::gil_scoped_release no_gil;
+          s = l.evaluate_poses_full(poses, image, opt_tensor(ij));
+        }
+        return py::make_tuple(s.weights, s.loss, s.colors, s.ij);
+      },
+      py::arg("poses"), py::arg("image"), py::arg("ij") = py::none(),
+      "-> (weights [P], loss [P], colors [P,K,3], ij [K,2])")
+    .def(
+      "pose_rays",
+      [](Localizer & l, const Tensor & poses, const Tensor & ij) {
+        Rays r = l.pose_rays(poses, ij);
+        return py::make_tuple(r.origins, r.dirs);
+      },
+      "the rays evaluate_poses renders, pose-major")
+    .def_static(
+      "calc_average_pose",
+      [](const py::object & particles, const c10::optional<Tensor> & weights) {
+        if (weights.has_value())
+          return Localizer::calc_average_pose(particles.cast<Tensor>(), *weights);
+        std::vector<Particle> v;
+        for (py::handle h : particles) {
+          auto t = h.cast<py::tuple>();
+          v.push_back({t[0].cast<Tensor>(), t[1].cast<float>()});
+        }
+        return Localizer::calc_average_pose(v);
+      },
+      py::arg("particles"), py::arg("weights") = py::none(),
+      "calc_average_pose([(pose, weight), ...]) or calc_average_pose(poses [P,3,4], weights [P])")
+    .def("world2camera", &Localizer::world2camera)
+    .def("camera2world", &Localizer::camera2world)
+    .def("noise_sigmas", &Localizer::noise_sigmas)
+    .def("radius", &Localizer::radius)
+    .def("infer_height", &Localizer::infer_height)
+    .def("infer_width", &Localizer::infer_width)
+    .def_property_readonly("renderer", &Localizer::renderer)
+    .def_property_readonly("intrinsic", [](Localizer & l) { return l.intrinsic(); });
 
   py::class_<AdamHandle>(m, "Adam")
     .def("step", [](AdamHandle & h) { h.opt->step(); }, py::call_guard<py::gil_scoped_release>())

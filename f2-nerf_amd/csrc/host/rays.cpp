@@ -110,6 +110,17 @@ Rays get_rays_from_pose(const Tensor & pose, const Tensor & intrinsic, const Ten
   return gen_rays(pose, intrinsic, ij32, 0, 1, n);
 }
 
+Rays get_rays_from_poses(const Tensor & poses, const Tensor & intrinsic, const Tensor & ij)
+{
+  TORCH_CHECK(ij.dim() == 2 && ij.size(1) == 2, "ij must be [K,2]");
+  TORCH_CHECK(intrinsic.dim() == 2, "intrinsic must be [3,3]: the poses share one camera");
+  Tensor ij32 = f2n::dev_i32(ij, "ij");
+  const int64_t P = poses.size(0), K = ij32.size(0);
+  Tensor cam = torch::arange(P * K, f2n::int_on(ij32.device())).floor_divide_(K);
+  return launch_gen_rays(
+    poses, intrinsic.unsqueeze(0).expand({P, 3, 3}), cam, ij32.repeat({P, 1}), 0, 1, P * K);
+}
+
 Rays get_view_rays(const Tensor & pose, const Tensor & intrinsic, int h, int w)
 {
   Tensor p = pose.dim() == 2 ? pose.unsqueeze(0) : pose;

@@ -24,6 +24,13 @@ struct alignas(32) Rays
 Rays get_rays_from_pose(
   const torch::Tensor & pose, const torch::Tensor & intrinsic, const torch::Tensor & ij);
 
+// The same K pixels under each of P poses that share one camera, pose-major (ray p*K + k is pixel k
+// under pose p): what the reference's Localizer::evaluate_poses builds with one get_rays_from_pose
+// per pose and two cats (src/localizer.cpp:218-231), as one f2n_gen_rays launch with a per-ray
+// camera index.  poses [P,3,4] (or [P,4,4]), intrinsic [3,3], ij [K,2] int32.  Not differentiated.
+Rays get_rays_from_poses(
+  const torch::Tensor & poses, const torch::Tensor & intrinsic, const torch::Tensor & ij);
+
 // All h*w pixels of one view in row-major order, without materialising the pixel grid
 // (Dataset::get_rays_from_pose(idx) / Renderer::render_image of the reference).
 Rays get_view_rays(const torch::Tensor & pose, const torch::Tensor & intrinsic, int h, int w);

@@ -427,6 +427,59 @@ int f2n_loss_fwd(
   const float * colors, const float * gt, const float * var, int n_rays, float var_weight,
   float * d_colors, float * d_var, float * partial, float * out4, void * stream);
 
+/* ------------------------------------------------------------------ localiser ----------------- */
+
+/* The particle loop of Localizer::optimize_pose_by_random_search -- src/localizer.cpp:88-118 (per
+ * particle a clone, three Eigen rotations copied to the device and three mm launches).
+ *   pose    one pose, pose_ld floats (12 or 16, as f2n_gen_rays: rows 0..2 are [R | t])
+ *   noise   [P,6] f32 standard normals: positions x, y, z then rotations x, y, z (row 0 is unused)
+ *   sigma_pos_*  standard deviations of the position noise in the NeRF frame
+ *   sigma_rot_*  standard deviations of the rotation noise about the NeRF axes, in DEGREES
+ *   poses   [P,3,4]: particle 0 is the input pose unchanged; particle p > 0 has
+ *           t += sigma_pos * n and R' = Mz My Mx R with theta = sigma_rot * n * pi/180.
+ * As coded, not as intended: the reference builds each axis rotation as a column-major Eigen matrix
+ * and reads its storage with from_blob as row-major (:104-113), so every M is the TRANSPOSE of the
+ * textbook rotation, i.e. a rotation by -theta.  The noise is symmetric, so the distribution is the
+ * same; this entry keeps the transposes so that a given noise tensor reproduces the reference's
+ * poses.  One thread per particle. */
+int f2n_perturb_poses(
+  const float * pose, int pose_ld, const float * noise, float sigma_pos_x, float sigma_pos_y,
+  float sigma_pos_z, float sigma_rot_x, float sigma_rot_y, float sigma_rot_z, float * poses, int P,
+  void * stream);
+
+/* The scoring tail of Localizer::evaluate_poses -- src/localizer.cpp:236-248 (clip, index and the
+ * squared-error reduction as ATen launches on the image's device -- the GPU when the caller passes
+ * the image there, as the ROS node does -- then a copy of the P losses to the host, where pow and
+ * the normalisation run in f32).
+ *   colors  [P,K,3] as rendered (not yet clipped), pose-major
+ *   image   [h,w,3]; ij [K,2] i32 (row, col), clamped to the image
+ *   loss    [P]: loss_p = sum_k mean_ch (clip(colors, 0, 1) - image[i_k, j_k])^2
+ *   weights [P]: s_p = (K / (loss_p + 1e-6))^5, w_p = s_p / sum_q s_q
+ *   workspace  P doubles of device memory, 8-byte aligned, contents undefined on entry and exit
+ * One wavefront per pose walks the pixels in strides of 64 and reduces in a fixed order; the
+ * normaliser is the sum of the P scores in index order.  No atomics: the same bits on every run.
+ * Different from the reference: loss, s and the normaliser are accumulated in f64 and rounded once
+ * to f32, so the result is the exact formula to a rounding, and it stays finite where the
+ * reference's f32 pow overflows (loss below about 3e-6 gives s > 3e38, then inf / inf = NaN
+ * weights). */
+int f2n_pose_scores(
+  const float * colors, const float * image, const int32_t * ij, float * loss, float * weights,
+  double * workspace, int P, int K, int h, int w, void * stream);
+
+/* Localizer::calc_average_pose with compute_rotation_average -- src/localizer.cpp:254-316 (per
+ * particle a device-to-host copy of its rotation, Eigen on the host, a copy back).
+ *   poses [P,3,4], weights [P] -> pose_out [3,4]; P >= 1 (there is no mean of nothing: P == 0 is
+ *   F2N_E_INVALID_ARG here, where the two entries above accept it and do nothing)
+ * position = sum_p w_p t_p.  Rotation, as coded in the reference: every matrix to a quaternion by
+ * Eigen's branches (trace > 0, else the largest diagonal element); a quaternion whose dot product
+ * with particle 0's is negative is flipped; the mean is UNWEIGHTED (cumulative /= size; the weights
+ * vector is filled and never used, :288-304); the mean is normalised and turned back into a matrix.
+ * The reference's memcpy into a column-major Eigen matrix and from_blob out of one transpose twice
+ * (conjugate quaternions in, conjugate out), which cancels: this is the plain computation.
+ * f64 inside, as the reference; one workgroup, every sum in index order. */
+int f2n_average_pose(
+  const float * poses, const float * weights, float * pose_out, int P, void * stream);
+
 #ifdef __cplusplus
 }
 #endif
