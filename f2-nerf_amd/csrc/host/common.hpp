@@ -74,4 +74,20 @@ inline const int32_t * iptr(const Tensor & t)
   return t.defined() ? t.data_ptr<int32_t>() : nullptr;
 }
 
+// An incoming [n, C] gradient of the hash encoding as the kernels read it, through (point, channel)
+// strides: row-major storage and a transposed view of channel-major storage (what the shade backward
+// hands over) are both consumed in place, anything else is copied to row-major first.
+struct EncodingGrad
+{
+  Tensor grad;
+  int64_t ld_point, ld_chan;
+};
+inline EncodingGrad encoding_grad_strides(const Tensor & g, int64_t n, int64_t C)
+{
+  TORCH_CHECK(g.is_cuda() && g.scalar_type() == torch::kFloat32, "encoding grad dtype");
+  if (g.stride(1) == 1 && g.stride(0) >= C) return {g, g.stride(0), 1};
+  if (g.stride(0) == 1 && g.stride(1) >= n) return {g, 1, g.stride(1)};
+  return {g.contiguous(), C, 1};
+}
+
 }  // namespace f2n

@@ -275,21 +275,8 @@ variable_list Hash3DAnchoredFunction::backward(AutogradContext * ctx, variable_l
 
   // the incoming gradient may be row-major [n, C] or a transposed (channel-major) view; both are
   // consumed in place through the kernel's (point, channel) strides
-  Tensor grad_in = grad_output[0];
-  TORCH_CHECK(grad_in.is_cuda() && grad_in.scalar_type() == torch::kFloat32, "hash grad dtype");
-  const int64_t C = (int64_t)L * F;
-  int64_t ld_point, ld_chan;
-  if (grad_in.stride(1) == 1 && grad_in.stride(0) >= C) {
-    ld_point = grad_in.stride(0);
-    ld_chan = 1;
-  } else if (grad_in.stride(0) == 1 && grad_in.stride(1) >= n) {
-    ld_point = 1;
-    ld_chan = grad_in.stride(1);
-  } else {
-    grad_in = grad_in.contiguous();
-    ld_point = C;
-    ld_chan = 1;
-  }
+  const auto [grad_in, ld_point, ld_chan] =
+    f2n::encoding_grad_strides(grad_output[0], n, (int64_t)L * F);
   Tensor table16 = field->table_for(feat_pool);
   // points need a gradient only for pose optimisation; training rays are data
   const bool want_points = ctx->needs_input_grad(0);

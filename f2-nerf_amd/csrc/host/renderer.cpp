@@ -57,141 +57,22 @@ int64_t f2n::HostCount::wait()
   return (int64_t)*pinned_;
 }
 
-Renderer::Renderer(int n_images, const RendererOptions & opt) : options_(opt)
-{
-  pts_sampler_ = std::make_shared<PtsSampler>(opt.sampler);
-
-  scene_field_ = std::make_shared<Hash3DAnchored>(opt.field);
-  register_module("scene_field", scene_field_);
-
-  shader_ = std::make_shared<SHShader>(opt.field.device);
-  register_module("shader", shader_);
-
-  app_emb_ = torch::randn({n_images, 16}, f2n::float_on(opt.field.device)) * .1f;
-  app_emb_.requires_grad_(true);
-  register_parameter("app_emb", app_emb_);
-}
-
-RenderResult Renderer::render(
-  const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode)
-{
-  return render(rays_o, rays_d, emb_idx, mode, Tensor(), Tensor());
-}
-
-RenderResult Renderer::render(
-  const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-  const Tensor & noise_in, const Tensor & bg_in)
-{
-  const int64_t n_rays = rays_o.size(0);
-  const auto fopt = f2n::float_on(rays_o.device());
-  Tensor noise = noise_in.defined() ? noise_in
-                                    : pts_sampler_->draw_noise(n_rays, mode, rays_o.device());
-  Tensor bg_color = bg_in.defined() ? bg_in
-                    : (mode == RunningMode::TRAIN) ? torch::rand({n_rays, 3}, fopt)
-                                                   : torch::ones({n_rays, 3}, fopt) * .5f;
-  if (n_rays <= 0) {
-    last_n_samples_ = 0;
-    return {bg_color, torch::zeros({n_rays}, fopt), torch::full({n_rays}, 512.f, fopt), Tensor()};
-  }
-  const bool rays_need_grad =
-    torch::GradMode::is_enabled() && (rays_o.requires_grad() || rays_d.requires_grad());
-  const int64_t C = scene_field_->options_.n_levels * scene_field_->options_.n_channels;
-  const bool fused_grad = options_.fused_ray_grad && options_.fused_shade &&
-                          f2n::shade_supported(C) && scene_field_->options_.mlp_out_dim == 16;
-  RenderResult res = (options_.fused && (!rays_need_grad || fused_grad))
-                       ? render_fused(rays_o, rays_d, emb_idx, mode, noise, bg_color)
-                       : render_op_by_op(rays_o, rays_d, emb_idx, mode, noise, bg_color);
-  if (options_.check_finite) CHECK(std::isfinite(res.colors.mean().item<float>()));
-  return res;
-}
-
-// ---- fused path ----------------------------------------------------------------------------------
-
-RenderResult Renderer::render_fused(
-  const Tensor & rays_o_raw, const Tensor & rays_d_raw, const Tensor & emb_idx, RunningMode mode,
-  const Tensor & noise_raw, const Tensor & bg_color)
-{
-  Tensor rays_o = f2n::dev_f32(rays_o_raw.detach(), "rays_o");
-  Tensor rays_d = f2n::dev_f32(rays_d_raw.detach(), "rays_d");
-  Tensor noise = noise_raw.defined() ? f2n::dev_f32(noise_raw, "noise") : Tensor();
-  const int n_rays = (int)rays_o.size(0);
-  const int S = pts_sampler_->options_.max_samples;
-  const float step = pts_sampler_->options_.step;
-  TORCH_CHECK(!noise.defined() || noise.numel() == (int64_t)n_rays * S, "noise shape");
-  const auto fopt = rays_o.options();
-  const auto iopt = f2n::int_on(rays_o.device());
-  void * stream = f2n::current_stream(rays_o);
-  Hash3DAnchored & field = *scene_field_;
-  const int L = (int)field.options_.n_levels, F = (int)field.options_.n_channels;
-  // rays that carry a gradient (options_.fused_ray_grad): the kernels work on the detached copies
-  // above, shade_and_composite hands the encoding's gradient back to these
-  const bool rays_need_grad =
-    torch::GradMode::is_enabled() && (rays_o_raw.requires_grad() || rays_d_raw.requires_grad());
-  const Rays grad_rays = rays_need_grad ? Rays{rays_o_raw, rays_d_raw} : Rays{};
-
-  const int64_t C = (int64_t)L * F;
-  const bool dense_ok = options_.fused_shade && f2n::shade_supported(C) &&
-                        field.options_.mlp_out_dim == 16;
-  const bool dense = dense_ok && (options_.dense_first_pass == 1 ||
-                                  (options_.dense_first_pass < 0 && last_kept_fraction_ > 0.4f));
-  if (dense) {
-    // bg_color or rays that carry a gradient stay on the caller's order (the bucketed route
-    // detaches them)
-    const bool bucket = n_rays >= options_.ray_order_min_rays &&
-                        f2n_get_option(F2N_OPT_RAY_ORDER) == 0 && !rays_need_grad &&
-                        !(torch::GradMode::is_enabled() && bg_color.requires_grad());
-    return bucket ? render_dense_bucketed(rays_o, rays_d, emb_idx, mode, noise, bg_color)
-                  : render_dense(rays_o, rays_d, emb_idx, mode, noise, bg_color, grad_rays);
-  }
-
-  SampleResultFlex kept;
-  {
-    // First pass (renderer.cpp:58-90): density only, never differentiated by the loss.
-    torch::NoGradGuard no_grad;
-    Tensor table16 = field.table_f16();
-    auto head = field.density_head();
-    Tensor counts = torch::empty({n_rays}, iopt);
-    {
-      f2n::ScopedKernelTimer timer("density_march", stream, (double)n_rays);
-      f2n::check(
-      f2n_density_march(
-        rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), f2n::fptr(noise),
-        reinterpret_cast<const uint16_t *>(table16.data_ptr()), field.prim_pool_.data_ptr<int32_t>(),
-        field.bias_pool_.data_ptr<float>(), field.level_mul_.data_ptr<float>(),
-        head.first.data_ptr<float>(), head.second.data_ptr<float>(), counts.data_ptr<int32_t>(),
-        n_rays, S, step, L, F, (uint32_t)field.local_size_, field.level_stride_,
-        options_.early_stop_trans, 3.f, stream),
-      "f2n_density_march");
-    }
-    kept.pts_idx_bounds = torch::empty({n_rays, 2}, iopt);
-    Tensor total = torch::empty({1}, iopt);
-    f2n::check(
-      f2n_bounds_from_counts(
-        counts.data_ptr<int32_t>(), kept.pts_idx_bounds.data_ptr<int32_t>(),
-        total.data_ptr<int32_t>(), n_rays, stream),
-      "f2n_bounds_from_counts");
-    const int64_t n_kept = total.item<int>();  // the one host sync of the fused path (sizes tensors)
-    last_n_samples_ = n_kept;
-    last_kept_fraction_ = (float)n_kept / (float)((int64_t)n_rays * S);
-    kept.pts = torch::empty({n_kept, 3}, fopt);
-    kept.dirs = torch::empty({n_kept, 3}, fopt);
-    kept.dt = torch::empty({n_kept}, fopt);
-    kept.t = torch::empty({n_kept}, fopt);
-    f2n::check(
-      f2n_sample_compact(
-        rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), f2n::fptr(noise),
-        kept.pts_idx_bounds.data_ptr<int32_t>(), kept.pts.data_ptr<float>(),
-        kept.dirs.data_ptr<float>(), kept.dt.data_ptr<float>(), kept.t.data_ptr<float>(), n_rays, S,
-        step, stream),
-      "f2n_sample_compact");
-  }
-  return shade_and_composite(kept, emb_idx, mode, bg_color, grad_rays);
-}
-
-// ---- bucketed dense pass ---------------------------------------------------------------------------
+// ---- helpers and autograd nodes of the routes ----------------------------------------------------
 
 namespace
 {
+
+// Exclusive scan of per-ray counts: bounds [n, 2] and their total [1], both left on the device.
+std::pair<Tensor, Tensor> bounds_from_counts(const Tensor & counts, void * stream)
+{
+  const int n = (int)counts.size(0);
+  Tensor bounds = torch::empty({n, 2}, counts.options()), total = torch::empty({1}, counts.options());
+  f2n::check(
+    f2n_bounds_from_counts(
+      counts.data_ptr<int32_t>(), bounds.data_ptr<int32_t>(), total.data_ptr<int32_t>(), n, stream),
+    "f2n_bounds_from_counts");
+  return {bounds, total};
+}
 
 // colors [n,3], depths [n] and weights (ragged) of the bucketed order back into the caller's order:
 // row i of the caller is row inv[i] of the bucketed storage; the backward is the inverse gather
@@ -301,23 +182,7 @@ public:
           ctx->saved_data["hash3d_info"].toCustomClass<Hash3DAnchoredInfo>()->hash3d_;
         const int64_t n = pts.size(0);
         const int L = (int)field->options_.n_levels, F = (int)field->options_.n_channels;
-        const int64_t C = (int64_t)L * F;
-        // (point, channel) strides of the incoming [n, C] gradient, read as Hash3DAnchoredFunction
-        // reads it (the shade backward hands over a view of channel-major storage)
-        Tensor g = g_enc;
-        TORCH_CHECK(g.is_cuda() && g.scalar_type() == torch::kFloat32, "encoding grad dtype");
-        int64_t ld_point, ld_chan;
-        if (g.stride(1) == 1 && g.stride(0) >= C) {
-          ld_point = g.stride(0);
-          ld_chan = 1;
-        } else if (g.stride(0) == 1 && g.stride(1) >= n) {
-          ld_point = 1;
-          ld_chan = g.stride(1);
-        } else {
-          g = g.contiguous();
-          ld_point = C;
-          ld_chan = 1;
-        }
+        const auto [g, ld_point, ld_chan] = f2n::encoding_grad_strides(g_enc, n, (int64_t)L * F);
         void * stream = f2n::current_stream(pts);
         f2n::ScopedKernelTimer timer("hash_rays_grad", stream, (double)n);
         f2n::check(
@@ -352,6 +217,180 @@ Tensor f2n::ray_order(const Tensor & rays_d_in)
   return std::get<1>(keys.sort(/*stable=*/true, /*dim=*/0, /*descending=*/false));
 }
 
+Renderer::Renderer(int n_images, const RendererOptions & opt) : options_(opt)
+{
+  pts_sampler_ = std::make_shared<PtsSampler>(opt.sampler);
+
+  scene_field_ = std::make_shared<Hash3DAnchored>(opt.field);
+  register_module("scene_field", scene_field_);
+
+  shader_ = std::make_shared<SHShader>(opt.field.device);
+  register_module("shader", shader_);
+
+  app_emb_ = torch::randn({n_images, 16}, f2n::float_on(opt.field.device)) * .1f;
+  app_emb_.requires_grad_(true);
+  register_parameter("app_emb", app_emb_);
+}
+
+RenderResult Renderer::render(
+  const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode)
+{
+  return render(rays_o, rays_d, emb_idx, mode, Tensor(), Tensor());
+}
+
+RenderResult Renderer::render(
+  const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
+  const Tensor & noise_in, const Tensor & bg_in)
+{
+  const int64_t n_rays = rays_o.size(0);
+  const auto fopt = f2n::float_on(rays_o.device());
+  Tensor noise = noise_in.defined() ? noise_in
+                                    : pts_sampler_->draw_noise(n_rays, mode, rays_o.device());
+  Tensor bg_color = bg_in.defined() ? bg_in
+                    : (mode == RunningMode::TRAIN) ? torch::rand({n_rays, 3}, fopt)
+                                                   : torch::ones({n_rays, 3}, fopt) * .5f;
+  if (n_rays <= 0) {
+    record_kept(0);
+    return {bg_color, torch::zeros({n_rays}, fopt), torch::full({n_rays}, 512.f, fopt), Tensor()};
+  }
+  const Route route = choose_route(rays_o, rays_d, bg_color);
+  RenderResult res = route.first_pass == Route::OpByOp
+                       ? render_op_by_op(rays_o, rays_d, emb_idx, mode, noise, bg_color, route)
+                       : render_fused(rays_o, rays_d, emb_idx, mode, noise, bg_color, route);
+  if (options_.check_finite) CHECK(std::isfinite(res.colors.mean().item<float>()));
+  return res;
+}
+
+Renderer::Route Renderer::choose_route(
+  const Tensor & rays_o, const Tensor & rays_d, const Tensor & bg_color) const
+{
+  Route route;
+  const auto & field = scene_field_->options_;
+  route.fused_net = options_.fused_shade && f2n::shade_supported(field.n_levels * field.n_channels) &&
+                    field.mlp_out_dim == 16;
+  const bool rays_need_grad =
+    torch::GradMode::is_enabled() && (rays_o.requires_grad() || rays_d.requires_grad());
+  // the fused kernels work on detached copies; shade() hands the encoding's gradient back to these
+  if (rays_need_grad) route.grad_rays = Rays{rays_o, rays_d};
+  if (!options_.fused || (rays_need_grad && !(options_.fused_ray_grad && route.fused_net)))
+    route.first_pass = Route::OpByOp;
+  else if (route.fused_net && (options_.dense_first_pass == 1 ||
+                               (options_.dense_first_pass < 0 && last_kept_fraction_ > 0.4f)))
+    route.first_pass = Route::Dense;
+  else
+    route.first_pass = Route::March;
+  // bg_color or rays that carry a gradient stay on the caller's order (the bucketed route
+  // detaches them)
+  route.bucketed = route.first_pass == Route::Dense &&
+                   rays_o.size(0) >= options_.ray_order_min_rays &&
+                   f2n_get_option(F2N_OPT_RAY_ORDER) == 0 && !rays_need_grad &&
+                   !(torch::GradMode::is_enabled() && bg_color.requires_grad());
+  return route;
+}
+
+void Renderer::record_kept(int64_t n_kept, int64_t n_all)
+{
+  last_n_samples_ = n_kept;
+  if (n_all >= 0) last_kept_fraction_ = n_all > 0 ? (float)n_kept / (float)n_all : 0.f;
+}
+
+// ---- op-by-op route (the reference's own sequence on the drop-in operators) ----------------------
+
+RenderResult Renderer::render_op_by_op(
+  const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
+  const Tensor & noise, const Tensor & bg_color, const Route & route)
+{
+  const int64_t n_rays = rays_o.size(0);
+  const int64_t S = pts_sampler_->options_.max_samples;
+  SampleResultFlex all = route.grad_rays.origins.defined()
+                           ? pts_sampler_->get_samples_aten(rays_o, rays_d, noise)
+                           : pts_sampler_->get_samples(rays_o, rays_d, noise);
+
+  auto density_act = [](const Tensor & x) {
+    return torch::autograd::TruncExp::apply(x - 3.f)[0];
+  };
+
+  SampleResultFlex kept;
+  {
+    Tensor scene_feat = scene_field_->query(all.pts);
+    Tensor density = density_act(scene_feat.index({Slc(), Slc(0, 1)}));
+    Tensor sec = density.index({Slc(), 0}) * all.dt;
+    Tensor acc = FlexOps::AccumulateSum(sec, all.pts_idx_bounds, false);
+    Tensor mask = torch::exp(-acc) > options_.early_stop_trans;
+    Tensor mask_idx = torch::where(mask)[0];
+    kept.pts = all.pts.index({mask_idx}).contiguous();
+    kept.dirs = all.dirs.index({mask_idx}).contiguous();
+    kept.dt = all.dt.index({mask_idx}).contiguous();
+    kept.t = all.t.index({mask_idx}).contiguous();
+    Tensor num = mask.reshape({n_rays, S}).sum(1);
+    Tensor cum = torch::cumsum(num, 0);
+    kept.pts_idx_bounds = torch::stack({cum - num, cum}, 1).to(torch::kInt32).contiguous();
+  }
+  record_kept(kept.pts.size(0));
+
+  Tensor scene_feat = scene_field_->query(kept.pts);
+  Tensor density = density_act(scene_feat.index({Slc(), Slc(0, 1)}));
+  Tensor sampled_colors = shade_aten(scene_feat, kept, emb_idx, mode);
+  Tensor sampled_t = (kept.t + 1e-2f).contiguous();
+  Tensor sec = density.index({Slc(), 0}) * kept.dt;
+  Tensor alphas = 1.f - torch::exp(-sec);
+  Tensor idx = kept.pts_idx_bounds;
+  Tensor trans = torch::exp(-FlexOps::AccumulateSum(sec, idx, false));
+  Tensor weights = trans * alphas;
+  Tensor last_trans = torch::exp(-FlexOps::Sum(sec, idx));
+  Tensor colors = FlexOps::Sum(weights.unsqueeze(-1) * sampled_colors, idx) +
+                  last_trans.unsqueeze(-1) * bg_color;
+  Tensor depths = FlexOps::Sum(weights * sampled_t, idx) / (1.f - last_trans + 1e-4f);
+  return {colors, depths, weights, idx};
+}
+
+// ---- fused routes --------------------------------------------------------------------------------
+
+RenderResult Renderer::render_fused(
+  const Tensor & rays_o_raw, const Tensor & rays_d_raw, const Tensor & emb_idx, RunningMode mode,
+  const Tensor & noise_raw, const Tensor & bg_color, const Route & route)
+{
+  Tensor rays_o = f2n::dev_f32(rays_o_raw.detach(), "rays_o");
+  Tensor rays_d = f2n::dev_f32(rays_d_raw.detach(), "rays_d");
+  Tensor noise = noise_raw.defined() ? f2n::dev_f32(noise_raw, "noise") : Tensor();
+  const int n_rays = (int)rays_o.size(0);
+  const int S = pts_sampler_->options_.max_samples;
+  TORCH_CHECK(!noise.defined() || noise.numel() == (int64_t)n_rays * S, "noise shape");
+  if (route.first_pass == Route::Dense)
+    return route.bucketed
+             ? render_dense_bucketed(rays_o, rays_d, emb_idx, mode, noise, bg_color, route)
+             : render_dense(rays_o, rays_d, emb_idx, mode, noise, bg_color, route);
+
+  void * stream = f2n::current_stream(rays_o);
+  Hash3DAnchored & field = *scene_field_;
+  SampleResultFlex kept;
+  {
+    // First pass (renderer.cpp:58-90): density only, never differentiated by the loss.
+    torch::NoGradGuard no_grad;
+    Tensor table16 = field.table_f16();
+    auto head = field.density_head();
+    Tensor counts = torch::empty({n_rays}, f2n::int_on(rays_o.device()));
+    {
+      f2n::ScopedKernelTimer timer("density_march", stream, (double)n_rays);
+      f2n::check(
+      f2n_density_march(
+        rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), f2n::fptr(noise),
+        reinterpret_cast<const uint16_t *>(table16.data_ptr()), field.prim_pool_.data_ptr<int32_t>(),
+        field.bias_pool_.data_ptr<float>(), field.level_mul_.data_ptr<float>(),
+        head.first.data_ptr<float>(), head.second.data_ptr<float>(), counts.data_ptr<int32_t>(),
+        n_rays, S, pts_sampler_->options_.step, (int)field.options_.n_levels,
+        (int)field.options_.n_channels, (uint32_t)field.local_size_, field.level_stride_,
+        options_.early_stop_trans, 3.f, stream),
+      "f2n_density_march");
+    }
+    auto [bounds, total] = bounds_from_counts(counts, stream);
+    const int64_t n_kept = total.item<int>();  // the one host sync of this route (sizes tensors)
+    record_kept(n_kept, (int64_t)n_rays * S);
+    kept = compact_samples(rays_o, rays_d, noise, bounds, n_kept);
+  }
+  return shade_and_composite(kept, emb_idx, mode, bg_color, route);
+}
+
 // The dense pass on the rays sorted into pixel-compact bundles (f2n::ray_order): 64 consecutive rays
 // are one ray tile of the encode, and a compact blob of pixels touches fewer table lines per gather
 // than a row strip.  Every ray keeps its own noise row, background colour and image id, so each
@@ -359,7 +398,7 @@ Tensor f2n::ray_order(const Tensor & rays_d_in)
 // order differs, and the results are gathered back (bounds re-scanned in the caller's order).
 RenderResult Renderer::render_dense_bucketed(
   const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx_in, RunningMode mode,
-  const Tensor & noise, const Tensor & bg_in)
+  const Tensor & noise, const Tensor & bg_in, const Route & route)
 {
   const int n_rays = (int)rays_o.size(0);
   const int64_t S = pts_sampler_->options_.max_samples;
@@ -384,50 +423,39 @@ RenderResult Renderer::render_dense_bucketed(
       emb_idx.defined() ? emb_p.data_ptr<int32_t>() : nullptr, bg_p.data_ptr<float>(),
       f2n::fptr_mut(noise_p), inv.data_ptr<int32_t>(), stream),
     "f2n_ray_permute");
-  RenderResult r = render_dense(o_p, d_p, emb_p, mode, noise_p, bg_p);
+  RenderResult r = render_dense(o_p, d_p, emb_p, mode, noise_p, bg_p, route);
 
   // every ray kept all S samples (n_kept = n*S, counts <= S): the bounds {i*S, (i+1)*S} are the same
   // in both orders; otherwise the caller-order counts are scanned as the unbucketed route scans them
   const bool rows = r.weights.size(0) == (int64_t)n_rays * S;
   Tensor bounds = r.idx_start_end;
   if (!rows) {
-    Tensor counts = torch::empty({n_rays}, iopt), total = torch::empty({1}, iopt);
-    bounds = torch::empty({n_rays, 2}, iopt);
+    Tensor counts = torch::empty({n_rays}, iopt);
     f2n::check(
       f2n_counts_through(
         r.idx_start_end.data_ptr<int32_t>(), inv.data_ptr<int32_t>(), counts.data_ptr<int32_t>(),
         n_rays, stream),
       "f2n_counts_through");
-    f2n::check(
-      f2n_bounds_from_counts(
-        counts.data_ptr<int32_t>(), bounds.data_ptr<int32_t>(), total.data_ptr<int32_t>(), n_rays,
-        stream),
-      "f2n_bounds_from_counts");
+    bounds = bounds_from_counts(counts, stream).first;
   }
   auto out = RayUnpermuteFn::apply(
     r.colors, r.depths, r.weights, perm, inv, r.idx_start_end, bounds, S, rows);
   return {out[0], out[1], out[2], bounds};
 }
 
+// Dense first pass: every sample is encoded once (level-major kernel), the keep-prefix comes from
+// that encoding, and the shading pass reuses it -- same counts as the march, bit for bit.
 RenderResult Renderer::render_dense(
   const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-  const Tensor & noise, const Tensor & bg_color, const Rays & grad_rays)
+  const Tensor & noise, const Tensor & bg_color, const Route & route)
 {
   const int n_rays = (int)rays_o.size(0);
   const int S = pts_sampler_->options_.max_samples;
-  const float step = pts_sampler_->options_.step;
-  const auto fopt = rays_o.options();
-  const auto iopt = f2n::int_on(rays_o.device());
   void * stream = f2n::current_stream(rays_o);
   Hash3DAnchored & field = *scene_field_;
-  const int64_t C = field.options_.n_levels * field.options_.n_channels;
-  // Dense first pass: every sample is encoded once (level-major kernel), the keep-prefix comes
-  // from that encoding, and the shading pass reuses it -- same counts as the march, bit for bit.
   SampleResultFlex all = pts_sampler_->get_samples(rays_o, rays_d, noise);
   const int64_t n_all = all.pts.size(0);
-  SampleResultFlex kept;
-  Tensor enc_kept_cm, contracted_kept, contracted_all, enc_all_cm;
-  Tensor total = torch::empty({1}, iopt);
+  Tensor contracted_all, enc_all_cm;
   {
     torch::NoGradGuard no_grad;
     // all.pts is the dense [n_rays, S] grid of the sampler: ray-tile mapping of the encode
@@ -446,113 +474,55 @@ RenderResult Renderer::render_dense(
   // compositing runs) was paid.  Flag set = drop the guess, run the exact scan, compact.
   //   Small chunks (the 512-ray training batch) keep the exact scan instead -- there it costs
   // 20 us, less than the GPU would idle while the host waits for a flag that only exists after
-  // the shading pass -- and hide ITS read-back behind the same guess (further down).
-  if (options_.deferred_check && options_.fused_shade) {
-    // no host read: exact scan -> device-side "kept fewer than shaded" flag, all samples shaded
-    torch::NoGradGuard no_grad;
-    auto head = field.density_head();
-    Tensor counts = torch::empty({n_rays}, iopt);
-    {
-      f2n::ScopedKernelTimer timer("density_scan", stream, (double)n_rays);
-      f2n::check(
-        f2n_density_scan(
-          enc_all_cm.data_ptr<float>(), (int)C, all.dt.data_ptr<float>(),
-          head.first.data_ptr<float>(), head.second.data_ptr<float>(),
-          counts.data_ptr<int32_t>(), n_rays, S, options_.early_stop_trans, 3.f, stream),
-        "f2n_density_scan");
-    }
-    Tensor scratch_bounds = torch::empty({n_rays, 2}, iopt);
-    f2n::check(
-      f2n_bounds_from_counts(
-        counts.data_ptr<int32_t>(), scratch_bounds.data_ptr<int32_t>(), total.data_ptr<int32_t>(),
-        n_rays, stream),
-      "f2n_bounds_from_counts");
-    if (!deferred_bad_.defined()) deferred_bad_ = torch::zeros({1}, iopt);
-    deferred_bad_.add_(total.ne(n_all).to(torch::kInt32));
-    last_n_samples_ = n_all;
-    last_kept_fraction_ = 1.f;
+  // the shading pass -- and hide ITS read-back behind the same guess.
+  //   options_.deferred_check does without the read altogether.
+
+  if (options_.deferred_check) {
+    // (a) no host read: exact scan -> device-side "kept fewer than shaded" flag, all samples shaded
+    Tensor total = scan_survivors(all, enc_all_cm, n_rays).second;
+    if (!deferred_bad_.defined()) deferred_bad_ = torch::zeros({1}, total.options());
+    deferred_bad_.add_(total.ne(n_all).to(torch::kInt32));  // (integers: nothing autograd records)
+    record_kept(n_all, n_all);
+    return shade_and_composite(all, emb_idx, mode, bg_color, route, enc_all_cm, contracted_all);
   }
-  if (options_.deferred_check && options_.fused_shade)
-    return shade_and_composite(
-      all, emb_idx, mode, bg_color, grad_rays, enc_all_cm, contracted_all);
+
   const bool may_guess = options_.speculate_dense && last_kept_fraction_ >= 1.f && n_all > 0;
-  const int64_t kMarginMinSamples = options_.margin_min_samples;
-  if (may_guess && n_all >= kMarginMinSamples) {
-    Tensor near_threshold = torch::zeros({1}, iopt);
-    RenderResult guess = shade_and_composite(
-      all, emb_idx, mode, bg_color, grad_rays, enc_all_cm, contracted_all, &near_threshold, S);
-    if (survivors_.wait() == 0) {
-      last_n_samples_ = n_all;
-      last_kept_fraction_ = 1.f;
-      return guess;
+  const bool large = n_all >= options_.margin_min_samples;
+  if (may_guess && large) {
+    // (b) accepted on the density-margin flag; a set flag falls through to (c) without a second guess
+    if (auto guess = shade_all_unless_near_threshold(
+          all, emb_idx, mode, bg_color, route, enc_all_cm, contracted_all)) {
+      record_kept(n_all, n_all);
+      return *guess;
     }
   }
-  {
-    torch::NoGradGuard no_grad;
-    auto head = field.density_head();
-    Tensor counts = torch::empty({n_rays}, iopt);
-    {
-      f2n::ScopedKernelTimer timer("density_scan", stream, (double)n_rays);
-      f2n::check(
-        f2n_density_scan(
-          enc_all_cm.data_ptr<float>(), (int)C, all.dt.data_ptr<float>(),
-          head.first.data_ptr<float>(), head.second.data_ptr<float>(),
-          counts.data_ptr<int32_t>(), n_rays, S, options_.early_stop_trans, 3.f, stream),
-        "f2n_density_scan");
-    }
-    kept.pts_idx_bounds = torch::empty({n_rays, 2}, iopt);
-    f2n::check(
-      f2n_bounds_from_counts(
-        counts.data_ptr<int32_t>(), kept.pts_idx_bounds.data_ptr<int32_t>(),
-        total.data_ptr<int32_t>(), n_rays, stream),
-      "f2n_bounds_from_counts");
-  }
+
+  // (c) the exact scan and the read of its total
+  auto [bounds, total] = scan_survivors(all, enc_all_cm, n_rays);
   survivors_.request(total, stream);
   RenderResult guess;
-  bool guessed = false;
-  if (may_guess && n_all < kMarginMinSamples) {
-    // enqueued BEFORE the host waits for the count: the GPU does not idle across the read
-    guess =
-      shade_and_composite(all, emb_idx, mode, bg_color, grad_rays, enc_all_cm, contracted_all);
-    guessed = true;
-  }
+  const bool guessed = may_guess && !large;
+  if (guessed)  // enqueued BEFORE the host waits for the count: the GPU does not idle across the read
+    guess = shade_and_composite(all, emb_idx, mode, bg_color, route, enc_all_cm, contracted_all);
   const int64_t n_kept = survivors_.wait();
-  last_n_samples_ = n_kept;
-  last_kept_fraction_ = n_all > 0 ? (float)n_kept / (float)n_all : 0.f;
+  record_kept(n_kept, n_all);
   if (guessed && n_kept == n_all) return guess;
-  guess = RenderResult();
-  {
-    torch::NoGradGuard no_grad;
-    if (n_kept == n_all) {
-      // nothing terminated: the uncompacted arrays ARE the compacted ones
-      kept.pts = all.pts;
-      kept.dirs = all.dirs;
-      kept.dt = all.dt;
-      kept.t = all.t;
-      enc_kept_cm = enc_all_cm;
-      contracted_kept = contracted_all;  // ... and so are their contracted positions
-    } else {
-      kept.pts = torch::empty({n_kept, 3}, fopt);
-      kept.dirs = torch::empty({n_kept, 3}, fopt);
-      kept.dt = torch::empty({n_kept}, fopt);
-      kept.t = torch::empty({n_kept}, fopt);
-      f2n::check(
-        f2n_sample_compact(
-          rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), f2n::fptr(noise),
-          kept.pts_idx_bounds.data_ptr<int32_t>(), kept.pts.data_ptr<float>(),
-          kept.dirs.data_ptr<float>(), kept.dt.data_ptr<float>(), kept.t.data_ptr<float>(),
-          n_rays, S, step, stream),
-        "f2n_sample_compact");
-      enc_kept_cm = torch::empty({C, n_kept}, fopt);
-      f2n::check(
-        f2n_compact_rows_cm(
-          enc_all_cm.data_ptr<float>(), n_all, enc_kept_cm.data_ptr<float>(), n_kept, (int)C,
-          kept.pts_idx_bounds.data_ptr<int32_t>(), n_rays, S, stream),
-        "f2n_compact_rows_cm");
-    }
+  guess = RenderResult();  // a wrong guess is released before the compaction allocates
+  if (n_kept == n_all) {
+    // nothing terminated: the uncompacted arrays ARE the compacted ones, and so are their
+    // contracted positions
+    all.pts_idx_bounds = bounds;
+    return shade_and_composite(all, emb_idx, mode, bg_color, route, enc_all_cm, contracted_all);
   }
-  return shade_and_composite(
-    kept, emb_idx, mode, bg_color, grad_rays, enc_kept_cm, contracted_kept);
+  SampleResultFlex kept = compact_samples(rays_o, rays_d, noise, bounds, n_kept);
+  const int64_t C = enc_all_cm.size(0);
+  Tensor enc_kept_cm = torch::empty({C, n_kept}, rays_o.options());
+  f2n::check(
+    f2n_compact_rows_cm(
+      enc_all_cm.data_ptr<float>(), n_all, enc_kept_cm.data_ptr<float>(), n_kept, (int)C,
+      bounds.data_ptr<int32_t>(), n_rays, S, stream),
+    "f2n_compact_rows_cm");
+  return shade_and_composite(kept, emb_idx, mode, bg_color, route, enc_kept_cm);
 }
 
 bool Renderer::deferred_check_ok()
@@ -563,53 +533,117 @@ bool Renderer::deferred_check_ok()
   return ok;
 }
 
+// ---- steps of the fused routes -------------------------------------------------------------------
+
+// The exact keep-prefix of every ray from the dense encoding: {bounds [n_rays, 2], total [1]}.
+std::pair<Tensor, Tensor> Renderer::scan_survivors(
+  const SampleResultFlex & all, const Tensor & enc_all_cm, int n_rays)
+{
+  torch::NoGradGuard no_grad;
+  void * stream = f2n::current_stream(enc_all_cm);
+  auto head = scene_field_->density_head();
+  Tensor counts = torch::empty({n_rays}, f2n::int_on(enc_all_cm.device()));
+  {
+    f2n::ScopedKernelTimer timer("density_scan", stream, (double)n_rays);
+    f2n::check(
+      f2n_density_scan(
+        enc_all_cm.data_ptr<float>(), (int)enc_all_cm.size(0), all.dt.data_ptr<float>(),
+        head.first.data_ptr<float>(), head.second.data_ptr<float>(), counts.data_ptr<int32_t>(),
+        n_rays, pts_sampler_->options_.max_samples, options_.early_stop_trans, 3.f, stream),
+      "f2n_density_scan");
+  }
+  return bounds_from_counts(counts, stream);
+}
+
+// The n_kept samples inside `bounds`, generated again from the rays (positions, directions, dt, t).
+SampleResultFlex Renderer::compact_samples(
+  const Tensor & rays_o, const Tensor & rays_d, const Tensor & noise, const Tensor & bounds,
+  int64_t n_kept)
+{
+  const auto fopt = rays_o.options();
+  SampleResultFlex kept{
+    torch::empty({n_kept, 3}, fopt), torch::empty({n_kept, 3}, fopt), torch::empty({n_kept}, fopt),
+    torch::empty({n_kept}, fopt), bounds};
+  f2n::check(
+    f2n_sample_compact(
+      rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), f2n::fptr(noise),
+      bounds.data_ptr<int32_t>(), kept.pts.data_ptr<float>(), kept.dirs.data_ptr<float>(),
+      kept.dt.data_ptr<float>(), kept.t.data_ptr<float>(), (int)rays_o.size(0),
+      pts_sampler_->options_.max_samples, pts_sampler_->options_.step,
+      f2n::current_stream(rays_o)),
+    "f2n_sample_compact");
+  return kept;
+}
+
+// The large-chunk guess of render_dense: shade ALL samples (`all` is the sampler's dense
+// [n_rays, max_samples] grid), and take that as the result unless some ray comes near the early-stop
+// threshold.  The margin kernel sits between shade and composite so that its flag travels to the
+// host while compositing runs.
+std::optional<RenderResult> Renderer::shade_all_unless_near_threshold(
+  const SampleResultFlex & all, const Tensor & emb_idx, RunningMode mode, const Tensor & bg_color,
+  const Route & route, const Tensor & enc_cm, const Tensor & contracted)
+{
+  void * stream = f2n::current_stream(all.pts);
+  Tensor near_threshold = torch::zeros({1}, f2n::int_on(all.pts.device()));
+  Shaded shaded = shade(all, emb_idx, mode, route, enc_cm, contracted);
+  const int S = pts_sampler_->options_.max_samples;
+  const float limit = -std::log(options_.early_stop_trans) - 0.5f;
+  f2n::check(
+    f2n_density_margin(
+      shaded.field_out.data_ptr<float>(), all.dt.data_ptr<float>(),
+      near_threshold.data_ptr<int32_t>(), (int)(all.pts.size(0) / S), S, 3.f, limit, stream),
+    "f2n_density_margin");
+  survivors_.request(near_threshold, stream);
+  RenderResult guess = composite(all, shaded, bg_color, route);
+  if (survivors_.wait() != 0) return std::nullopt;
+  return guess;
+}
+
 // Second pass on the survivors (renderer.cpp:92-118).
 RenderResult Renderer::shade_and_composite(
   const SampleResultFlex & kept, const Tensor & emb_idx, RunningMode mode, const Tensor & bg_color,
-  const Rays & grad_rays, const Tensor & enc_cm, const Tensor & contracted, Tensor * near_threshold,
-  int64_t grid_samples)
+  const Route & route, const Tensor & enc_cm, const Tensor & contracted)
+{
+  return composite(kept, shade(kept, emb_idx, mode, route, enc_cm, contracted), bg_color, route);
+}
+
+Renderer::Shaded Renderer::shade(
+  const SampleResultFlex & kept, const Tensor & emb_idx, RunningMode mode, const Route & route,
+  const Tensor & enc_cm, const Tensor & contracted)
+{
+  if (!route.fused_net) {
+    Tensor scene_feat = scene_field_->query(kept.pts);  // [n, 16]: col 0 density logit, 1.. shading
+    return {scene_feat, shade_aten(scene_feat, kept, emb_idx, mode)};
+  }
+  // hash encode -> one kernel for field head + embedding + SH + colour MLP
+  const int64_t n_kept = kept.pts.size(0);
+  Tensor enc = enc_cm.defined() ? scene_field_->encode_cached(kept.pts, enc_cm, contracted)
+                                : scene_field_->encode(kept.pts);
+  if (route.grad_rays.origins.defined()) {
+    // enc passes through; the backward turns d(enc) into d(rays) (and, with the field frozen,
+    // is what makes the shade backward form d(enc) at all)
+    auto info = torch::make_intrusive<Hash3DAnchoredInfo>();
+    info->hash3d_ = scene_field_.get();
+    enc = RayGradFn::apply(
+      enc, route.grad_rays.origins, route.grad_rays.dirs, kept.pts, kept.t, kept.pts_idx_bounds,
+      torch::IValue(info))[0];
+  }
+  Tensor sample_img;
+  if (mode == RunningMode::TRAIN)
+    sample_img = CustomOps::ScatterIdx((int)n_kept, kept.pts_idx_bounds, emb_idx);
+  auto mlp = shader_->mlp_params();
+  f2n::ShadeOut sh = f2n::shade(
+    enc, kept.dirs, sample_img, scene_field_->mlp_->weight, scene_field_->mlp_->bias, mlp[0],
+    mlp[1], mlp[2], mlp[3], mode == RunningMode::TRAIN ? app_emb_ : Tensor());
+  return {sh.logit.unsqueeze(1), sh.rgb};
+}
+
+// The reference's per-sample colours from the field head's output (renderer.cpp:95-105): a ones
+// column in place of the density logit, the image's appearance embedding added in TRAIN, SH + MLP.
+Tensor Renderer::shade_aten(
+  const Tensor & scene_feat, const SampleResultFlex & kept, const Tensor & emb_idx, RunningMode mode)
 {
   const int64_t n_kept = kept.pts.size(0);
-  const int64_t C = scene_field_->options_.n_levels * scene_field_->options_.n_channels;
-  if (options_.fused_shade && f2n::shade_supported(C) && scene_field_->options_.mlp_out_dim == 16) {
-    // hash encode -> one kernel for field head + embedding + SH + colour MLP -> composite
-    Tensor enc = enc_cm.defined() ? scene_field_->encode_cached(kept.pts, enc_cm, contracted)
-                                  : scene_field_->encode(kept.pts);
-    if (grad_rays.origins.defined()) {
-      // enc passes through; the backward turns d(enc) into d(rays) (and, with the field frozen,
-      // is what makes the shade backward form d(enc) at all)
-      auto info = torch::make_intrusive<Hash3DAnchoredInfo>();
-      info->hash3d_ = scene_field_.get();
-      enc = RayGradFn::apply(
-        enc, grad_rays.origins, grad_rays.dirs, kept.pts, kept.t, kept.pts_idx_bounds,
-        torch::IValue(info))[0];
-    }
-    Tensor sample_img;
-    if (mode == RunningMode::TRAIN)
-      sample_img = CustomOps::ScatterIdx((int)n_kept, kept.pts_idx_bounds, emb_idx);
-    auto mlp = shader_->mlp_params();
-    f2n::ShadeOut sh = f2n::shade(
-      enc, kept.dirs, sample_img, scene_field_->mlp_->weight, scene_field_->mlp_->bias, mlp[0],
-      mlp[1], mlp[2], mlp[3], mode == RunningMode::TRAIN ? app_emb_ : Tensor());
-    if (near_threshold) {
-      // `kept` is the sampler's dense [n_rays, grid_samples] grid: see render_fused
-      torch::NoGradGuard no_grad;
-      void * stream = f2n::current_stream(sh.logit);
-      const float limit = -std::log(options_.early_stop_trans) - 0.5f;
-      f2n::check(
-        f2n_density_margin(
-          sh.logit.data_ptr<float>(), kept.dt.data_ptr<float>(), near_threshold->data_ptr<int32_t>(),
-          (int)(n_kept / grid_samples), (int)grid_samples, 3.f, limit, stream),
-        "f2n_density_margin");
-      survivors_.request(*near_threshold, stream);
-    }
-    // (kept.pts_idx_bounds comes from f2n_bounds_from_counts / the sampler: the ranges tile [0, n))
-    f2n::CompositeOut out = f2n::composite(
-      sh.logit.unsqueeze(1), sh.rgb, kept.dt, kept.t, kept.pts_idx_bounds, bg_color, true);
-    return {out.colors, out.depths, out.weights, kept.pts_idx_bounds};
-  }
-  Tensor scene_feat = scene_field_->query(kept.pts);  // [n, 16]: col 0 density logit, 1.. shading
-
   Tensor shading_feat = torch::cat(
     {torch::ones({n_kept, 1}, scene_feat.options()),
      scene_feat.index({Slc(), Slc(1, torch::indexing::None)})},
@@ -618,71 +652,17 @@ RenderResult Renderer::shade_and_composite(
     Tensor all_emb_idx = CustomOps::ScatterIdx((int)n_kept, kept.pts_idx_bounds, emb_idx);
     shading_feat = CustomOps::ScatterAdd(app_emb_, all_emb_idx, shading_feat);
   }
-  Tensor sampled_colors = shader_->query(shading_feat, kept.dirs);
-
-  f2n::CompositeOut out =
-    f2n::composite(scene_feat, sampled_colors, kept.dt, kept.t, kept.pts_idx_bounds, bg_color);
-  return {out.colors, out.depths, out.weights, kept.pts_idx_bounds};
+  return shader_->query(shading_feat, kept.dirs);
 }
 
-// ---- op-by-op path (the reference's own sequence on the drop-in operators) -----------------------
-
-RenderResult Renderer::render_op_by_op(
-  const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-  const Tensor & noise, const Tensor & bg_color)
+RenderResult Renderer::composite(
+  const SampleResultFlex & kept, const Shaded & shaded, const Tensor & bg_color, const Route & route)
 {
-  const int64_t n_rays = rays_o.size(0);
-  const int64_t S = pts_sampler_->options_.max_samples;
-  const bool rays_need_grad =
-    torch::GradMode::is_enabled() && (rays_o.requires_grad() || rays_d.requires_grad());
-  SampleResultFlex all = rays_need_grad ? pts_sampler_->get_samples_aten(rays_o, rays_d, noise)
-                                        : pts_sampler_->get_samples(rays_o, rays_d, noise);
-
-  auto density_act = [](const Tensor & x) {
-    return torch::autograd::TruncExp::apply(x - 3.f)[0];
-  };
-
-  SampleResultFlex kept;
-  {
-    Tensor scene_feat = scene_field_->query(all.pts);
-    Tensor density = density_act(scene_feat.index({Slc(), Slc(0, 1)}));
-    Tensor sec = density.index({Slc(), 0}) * all.dt;
-    Tensor acc = FlexOps::AccumulateSum(sec, all.pts_idx_bounds, false);
-    Tensor mask = torch::exp(-acc) > options_.early_stop_trans;
-    Tensor mask_idx = torch::where(mask)[0];
-    kept.pts = all.pts.index({mask_idx}).contiguous();
-    kept.dirs = all.dirs.index({mask_idx}).contiguous();
-    kept.dt = all.dt.index({mask_idx}).contiguous();
-    kept.t = all.t.index({mask_idx}).contiguous();
-    Tensor num = mask.reshape({n_rays, S}).sum(1);
-    Tensor cum = torch::cumsum(num, 0);
-    kept.pts_idx_bounds = torch::stack({cum - num, cum}, 1).to(torch::kInt32).contiguous();
-  }
-  last_n_samples_ = kept.pts.size(0);
-
-  Tensor scene_feat = scene_field_->query(kept.pts);
-  Tensor density = density_act(scene_feat.index({Slc(), Slc(0, 1)}));
-  Tensor shading_feat = torch::cat(
-    {torch::ones_like(scene_feat.index({Slc(), Slc(0, 1)})),
-     scene_feat.index({Slc(), Slc(1, torch::indexing::None)})},
-    1);
-  if (mode == RunningMode::TRAIN) {
-    Tensor all_emb_idx =
-      CustomOps::ScatterIdx((int)kept.pts.size(0), kept.pts_idx_bounds, emb_idx);
-    shading_feat = CustomOps::ScatterAdd(app_emb_, all_emb_idx, shading_feat);
-  }
-  Tensor sampled_colors = shader_->query(shading_feat, kept.dirs);
-  Tensor sampled_t = (kept.t + 1e-2f).contiguous();
-  Tensor sec = density.index({Slc(), 0}) * kept.dt;
-  Tensor alphas = 1.f - torch::exp(-sec);
-  Tensor idx = kept.pts_idx_bounds;
-  Tensor trans = torch::exp(-FlexOps::AccumulateSum(sec, idx, false));
-  Tensor weights = trans * alphas;
-  Tensor last_trans = torch::exp(-FlexOps::Sum(sec, idx));
-  Tensor colors = FlexOps::Sum(weights.unsqueeze(-1) * sampled_colors, idx) +
-                  last_trans.unsqueeze(-1) * bg_color;
-  Tensor depths = FlexOps::Sum(weights * sampled_t, idx) / (1.f - last_trans + 1e-4f);
-  return {colors, depths, weights, idx};
+  // (the fused routes' kept.pts_idx_bounds comes from f2n_bounds_from_counts / the sampler: the
+  // ranges tile [0, n))
+  f2n::CompositeOut out = f2n::composite(
+    shaded.field_out, shaded.rgb, kept.dt, kept.t, kept.pts_idx_bounds, bg_color, route.fused_net);
+  return {out.colors, out.depths, out.weights, kept.pts_idx_bounds};
 }
 
 // ---- whole-image helpers -------------------------------------------------------------------------

@@ -5,18 +5,27 @@
 // render_all_rays / render_image / optim_param_groups); registered names "scene_field", "shader",
 // "app_emb" kept so a reference checkpoint (renderer.pt) loads.
 //
-// render() has two implementations of the same arithmetic (reference src/renderer.cpp:33-123):
-//   fused (default)   one wavefront-per-ray march finds each ray's kept prefix (early termination
-//                     in-kernel), a scan turns counts into bounds, one kernel emits the compacted
-//                     samples, and compositing is one kernel per direction;
+// render() picks one of three routes through the same arithmetic (reference src/renderer.cpp:33-123);
+// Renderer::choose_route makes the choice once per call:
 //   op-by-op          the reference's own sequence (sample all, query all, AccumulateSum, where,
-//                     4x index, query survivors, Sum...) on the drop-in operators.  Used when rays
-//                     carry gradients (pose optimisation; unless RendererOptions::fused_ray_grad)
-//                     and as the cross-check of the fused path.
+//                     4x index, query survivors, Sum...) on the drop-in operators.  Used when
+//                     RendererOptions::fused is off, when rays carry gradients (pose optimisation;
+//                     unless RendererOptions::fused_ray_grad) and as the cross-check of the others;
+//   fused, march      one wavefront-per-ray march finds each ray's kept prefix (early termination
+//                     in-kernel), a scan turns counts into bounds, one kernel emits the compacted
+//                     samples, the survivors are encoded and shaded, compositing is one kernel per
+//                     direction;
+//   fused, dense      every sample is encoded once, the kept prefix comes from that encoding and the
+//                     shading pass reuses it (RendererOptions::dense_first_pass; the ways it avoids
+//                     waiting for the survivor count are told in Renderer::render_dense).  Large
+//                     chunks are rendered bucketed into pixel-compact ray bundles
+//                     (Renderer::render_dense_bucketed) and handed back in the caller's order.
 #pragma once
 
 #include <memory>
+#include <optional>
 #include <tuple>
+#include <utility>
 #include <vector>
 
 #include "hash_3d_anchored.hpp"
@@ -70,8 +79,8 @@ struct RendererOptions
   float early_stop_trans = 1e-4f;  // renderer.cpp:68
   int pixel_tiles = 8;             // render_image traverses the view in tiles of this many pixels squared (0: rows)
   // Dense first pass: when the previous chunk kept every sample, shade all samples first and accept
-  // that as the result if no ray comes near the early-stop threshold (see render_fused); results are
-  // identical either way.
+  // that as the result if no ray comes near the early-stop threshold (see Renderer::render_dense);
+  // results are identical either way.
   bool speculate_dense = true;
   // ... chunks of at least this many samples accept the guess on the density-margin flag (no exact
   // scan at all), smaller ones run the scan and only hide its read-back behind the guess
@@ -142,24 +151,63 @@ public:
   bool deferred_check_ok();
 
 private:
-  RenderResult render_fused(
-    const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-    const Tensor & noise, const Tensor & bg_color);
-  // grad_rays: the caller's rays when they carry a gradient (fused_ray_grad), else undefined
-  RenderResult render_dense(
-    const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-    const Tensor & noise, const Tensor & bg_color, const Rays & grad_rays = {});
-  RenderResult render_dense_bucketed(
-    const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-    const Tensor & noise, const Tensor & bg_color);
+  // Everything the routes branch on, decided once per render() call (choose_route).
+  struct Route
+  {
+    enum FirstPass { OpByOp, March, Dense };
+    FirstPass first_pass = OpByOp;
+    bool bucketed = false;   // Dense only: render_dense_bucketed instead of the caller's order
+    bool fused_net = false;  // the fused per-sample network (f2n::shade) applies
+    Rays grad_rays;          // the caller's rays when they carry a gradient, else undefined
+  };
+  // What the shading pass hands to compositing: the field head's output ([n, 1] density logit of the
+  // fused network, [n, 16] otherwise) and the colours [n, 3].
+  struct Shaded
+  {
+    Tensor field_out, rgb;
+  };
+
+  Route choose_route(const Tensor & rays_o, const Tensor & rays_d, const Tensor & bg_color) const;
+
+  // The routes.  render_fused: detached rays, then march / dense / dense bucketed.
   RenderResult render_op_by_op(
     const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-    const Tensor & noise, const Tensor & bg_color);
+    const Tensor & noise, const Tensor & bg_color, const Route & route);
+  RenderResult render_fused(
+    const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
+    const Tensor & noise, const Tensor & bg_color, const Route & route);
+  RenderResult render_dense(
+    const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
+    const Tensor & noise, const Tensor & bg_color, const Route & route);
+  RenderResult render_dense_bucketed(
+    const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
+    const Tensor & noise, const Tensor & bg_color, const Route & route);
+
+  // The steps.  enc_cm / contracted: the samples' encoding (channel-major) and contracted positions
+  // when a dense first pass has them already, else undefined (the shading pass encodes).
+  std::pair<Tensor, Tensor> scan_survivors(
+    const SampleResultFlex & all, const Tensor & enc_all_cm, int n_rays);
+  SampleResultFlex compact_samples(
+    const Tensor & rays_o, const Tensor & rays_d, const Tensor & noise, const Tensor & bounds,
+    int64_t n_kept);
+  std::optional<RenderResult> shade_all_unless_near_threshold(
+    const SampleResultFlex & all, const Tensor & emb_idx, RunningMode mode, const Tensor & bg_color,
+    const Route & route, const Tensor & enc_cm, const Tensor & contracted);
+  Shaded shade(
+    const SampleResultFlex & kept, const Tensor & emb_idx, RunningMode mode, const Route & route,
+    const Tensor & enc_cm, const Tensor & contracted);
+  Tensor shade_aten(
+    const Tensor & scene_feat, const SampleResultFlex & kept, const Tensor & emb_idx,
+    RunningMode mode);
+  RenderResult composite(
+    const SampleResultFlex & kept, const Shaded & shaded, const Tensor & bg_color,
+    const Route & route);
   RenderResult shade_and_composite(
     const SampleResultFlex & kept, const Tensor & emb_idx, RunningMode mode,
-    const Tensor & bg_color, const Rays & grad_rays, const Tensor & enc_cm = Tensor(),
-    const Tensor & contracted = Tensor(), Tensor * near_threshold = nullptr,
-    int64_t grid_samples = 0);
+    const Tensor & bg_color, const Route & route, const Tensor & enc_cm = Tensor(),
+    const Tensor & contracted = Tensor());
+  // n_all < 0: the kept fraction (what the adaptive first-pass choice reads) keeps its value
+  void record_kept(int64_t n_kept, int64_t n_all = -1);
 };
 
 namespace f2n
