@@ -7,6 +7,7 @@
 #include "hash_3d_anchored.hpp"
 #include "kernel_timer.hpp"
 #include "localizer.hpp"
+#include "occupancy_grid.hpp"
 #include "points_sampler.hpp"
 #include "ragged_ops.hpp"
 #include "rays.hpp"
@@ -192,6 +193,32 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def("encode", &SHShader::encode)
     .def("named_parameters", [](SHShader & s) { return named_params(s); });
 
+  // ---- OccupancyGrid -----------------------------------------------------------------------------
+  py::class_<OccupancyGrid, std::shared_ptr<OccupancyGrid>>(m, "OccupancyGrid")
+    .def(
+      py::init([](int64_t resolution, const std::string & dev) {
+        return std::make_shared<OccupancyGrid>(resolution, parse_device(dev));
+      }),
+      py::arg("resolution") = 128, py::arg("device") = "")
+    .def(
+      "update",
+      [](OccupancyGrid & g, Hash3DAnchored & field, float threshold, float decay,
+         const c10::optional<Tensor> & probe) { g.update(field, threshold, decay, opt_tensor(probe)); },
+      py::arg("field"), py::arg("threshold") = OccupancyGrid::kDefaultThreshold,
+      py::arg("decay") = OccupancyGrid::kDefaultDecay, py::arg("probe") = py::none(),
+      "density = max(density * decay, sigma(probe)); bit = density > threshold")
+    .def("set_bits", &OccupancyGrid::set_bits, "bool [G,G,G], indexed [cz][cy][cx]")
+    .def("bits", &OccupancyGrid::bits)
+    .def("density", &OccupancyGrid::density)
+    .def("occupied", &OccupancyGrid::occupied, "raw points [n,3] -> bool [n]")
+    .def("fraction", &OccupancyGrid::fraction)
+    .def_property_readonly("resolution", &OccupancyGrid::resolution)
+    .def_property_readonly("words", &OccupancyGrid::words)
+    .def_property_readonly_static(
+      "DEFAULT_THRESHOLD", [](py::object) { return OccupancyGrid::kDefaultThreshold; })
+    .def_property_readonly_static(
+      "DEFAULT_DECAY", [](py::object) { return OccupancyGrid::kDefaultDecay; });
+
   // ---- Renderer ----------------------------------------------------------------------------------
   py::class_<Renderer, std::shared_ptr<Renderer>>(m, "Renderer")
     .def(
@@ -252,6 +279,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
         for (auto & kv : r.named_parameters()) d[py::str(kv.key())] = grad_or_none(kv.value());
         return d;
       })
+    .def(
+      "set_occupancy",
+      [](Renderer & r, std::shared_ptr<OccupancyGrid> g) { r.set_occupancy(std::move(g)); },
+      py::arg("grid").none(true), "attach an occupancy grid (None = off): see Renderer::set_occupancy")
+    .def_property_readonly("occupancy", [](Renderer & r) { return r.occupancy(); })
     .def("set_fused", [](Renderer & r, bool f) { r.options_.fused = f; })
     .def("set_fused_shade", [](Renderer & r, bool f) { r.options_.fused_shade = f; })
     .def("set_dense_first_pass", [](Renderer & r, int m) { r.options_.dense_first_pass = m; })

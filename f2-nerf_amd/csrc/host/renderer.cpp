@@ -274,6 +274,8 @@ Renderer::Route Renderer::choose_route(
   if (rays_need_grad) route.grad_rays = Rays{rays_o, rays_d};
   if (!options_.fused || (rays_need_grad && !(options_.fused_ray_grad && route.fused_net)))
     route.first_pass = Route::OpByOp;
+  else if (occupancy_)
+    route.first_pass = Route::March;  // the dense pass encodes every sample: the cost a grid removes
   else if (route.fused_net && (options_.dense_first_pass == 1 ||
                                (options_.dense_first_pass < 0 && last_kept_fraction_ > 0.4f)))
     route.first_pass = Route::Dense;
@@ -315,8 +317,14 @@ RenderResult Renderer::render_op_by_op(
     Tensor scene_feat = scene_field_->query(all.pts);
     Tensor density = density_act(scene_feat.index({Slc(), Slc(0, 1)}));
     Tensor sec = density.index({Slc(), 0}) * all.dt;
+    Tensor occupied;
+    if (occupancy_) {
+      occupied = occupancy_->occupied(all.pts);
+      sec = sec * occupied.to(sec.scalar_type());
+    }
     Tensor acc = FlexOps::AccumulateSum(sec, all.pts_idx_bounds, false);
     Tensor mask = torch::exp(-acc) > options_.early_stop_trans;
+    if (occupancy_) mask = mask.logical_and(occupied);
     Tensor mask_idx = torch::where(mask)[0];
     kept.pts = all.pts.index({mask_idx}).contiguous();
     kept.dirs = all.dirs.index({mask_idx}).contiguous();
@@ -370,7 +378,24 @@ RenderResult Renderer::render_fused(
     Tensor table16 = field.table_f16();
     auto head = field.density_head();
     Tensor counts = torch::empty({n_rays}, f2n::int_on(rays_o.device()));
-    {
+    Tensor len;  // with a grid: the prefix lengths the counts were thinned from
+    if (occupancy_) {
+      TORCH_CHECK(
+        occupancy_->words().device() == rays_o.device(), "the occupancy grid lives on another device");
+      len = torch::empty_like(counts);
+      f2n::ScopedKernelTimer timer("density_march_occ", stream, (double)n_rays);
+      f2n::check(
+        f2n_density_march_occ(
+          rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), f2n::fptr(noise),
+          reinterpret_cast<const uint16_t *>(table16.data_ptr()),
+          field.prim_pool_.data_ptr<int32_t>(), field.bias_pool_.data_ptr<float>(),
+          field.level_mul_.data_ptr<float>(), head.first.data_ptr<float>(),
+          head.second.data_ptr<float>(), occupancy_->words_ptr(), (int)occupancy_->resolution(),
+          counts.data_ptr<int32_t>(), len.data_ptr<int32_t>(), n_rays, S,
+          pts_sampler_->options_.step, (int)field.options_.n_levels, (int)field.options_.n_channels,
+          (uint32_t)field.local_size_, field.level_stride_, options_.early_stop_trans, 3.f, stream),
+        "f2n_density_march_occ");
+    } else {
       f2n::ScopedKernelTimer timer("density_march", stream, (double)n_rays);
       f2n::check(
       f2n_density_march(
@@ -386,7 +411,7 @@ RenderResult Renderer::render_fused(
     auto [bounds, total] = bounds_from_counts(counts, stream);
     const int64_t n_kept = total.item<int>();  // the one host sync of this route (sizes tensors)
     record_kept(n_kept, (int64_t)n_rays * S);
-    kept = compact_samples(rays_o, rays_d, noise, bounds, n_kept);
+    kept = compact_samples(rays_o, rays_d, noise, bounds, n_kept, len);
   }
   return shade_and_composite(kept, emb_idx, mode, bg_color, route);
 }
@@ -558,12 +583,24 @@ std::pair<Tensor, Tensor> Renderer::scan_survivors(
 // The n_kept samples inside `bounds`, generated again from the rays (positions, directions, dt, t).
 SampleResultFlex Renderer::compact_samples(
   const Tensor & rays_o, const Tensor & rays_d, const Tensor & noise, const Tensor & bounds,
-  int64_t n_kept)
+  int64_t n_kept, const Tensor & len)
 {
   const auto fopt = rays_o.options();
   SampleResultFlex kept{
     torch::empty({n_kept, 3}, fopt), torch::empty({n_kept, 3}, fopt), torch::empty({n_kept}, fopt),
     torch::empty({n_kept}, fopt), bounds};
+  if (len.defined()) {
+    f2n::check(
+      f2n_sample_compact_occ(
+        rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), f2n::fptr(noise),
+        bounds.data_ptr<int32_t>(), len.data_ptr<int32_t>(), occupancy_->words_ptr(),
+        (int)occupancy_->resolution(), kept.pts.data_ptr<float>(), kept.dirs.data_ptr<float>(),
+        kept.dt.data_ptr<float>(), kept.t.data_ptr<float>(), (int)rays_o.size(0),
+        pts_sampler_->options_.max_samples, pts_sampler_->options_.step,
+        f2n::current_stream(rays_o)),
+      "f2n_sample_compact_occ");
+    return kept;
+  }
   f2n::check(
     f2n_sample_compact(
       rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), f2n::fptr(noise),

@@ -20,6 +20,10 @@
 //                     waiting for the survivor count are told in Renderer::render_dense).  Large
 //                     chunks are rendered bucketed into pixel-compact ray bundles
 //                     (Renderer::render_dense_bucketed) and handed back in the caller's order.
+// With an occupancy grid attached (Renderer::set_occupancy) the density of every sample in an
+// unoccupied cell counts as exactly zero and those samples are dropped: the march skips them
+// (f2n_density_march_occ / f2n_sample_compact_occ), op-by-op masks them, the dense route is not
+// taken (it encodes everything, which is the cost the grid removes).
 #pragma once
 
 #include <memory>
@@ -29,6 +33,7 @@
 #include <vector>
 
 #include "hash_3d_anchored.hpp"
+#include "occupancy_grid.hpp"
 #include "points_sampler.hpp"
 #include "rays.hpp"
 #include "sh_shader.hpp"
@@ -134,6 +139,12 @@ public:
 
   std::vector<torch::optim::OptimizerParamGroup> optim_param_groups(float lr);
 
+  // Empty-space skipping: null = off (the default; same routes, same kernels, same bits as without
+  // this call).  Not a parameter or buffer: renderer.pt keeps the reference's layout, the grid is
+  // rebuilt from the field (OccupancyGrid::update).  The caller keeps it current.
+  void set_occupancy(std::shared_ptr<OccupancyGrid> grid) { occupancy_ = std::move(grid); }
+  const std::shared_ptr<OccupancyGrid> & occupancy() const { return occupancy_; }
+
   RendererOptions options_;
   std::shared_ptr<PtsSampler> pts_sampler_;
   std::shared_ptr<Hash3DAnchored> scene_field_;
@@ -187,9 +198,10 @@ private:
   // when a dense first pass has them already, else undefined (the shading pass encodes).
   std::pair<Tensor, Tensor> scan_survivors(
     const SampleResultFlex & all, const Tensor & enc_all_cm, int n_rays);
+  // len: with an occupancy grid, the per-ray prefix lengths the bounds were thinned from
   SampleResultFlex compact_samples(
     const Tensor & rays_o, const Tensor & rays_d, const Tensor & noise, const Tensor & bounds,
-    int64_t n_kept);
+    int64_t n_kept, const Tensor & len = Tensor());
   std::optional<RenderResult> shade_all_unless_near_threshold(
     const SampleResultFlex & all, const Tensor & emb_idx, RunningMode mode, const Tensor & bg_color,
     const Route & route, const Tensor & enc_cm, const Tensor & contracted);
@@ -208,6 +220,8 @@ private:
     const Tensor & contracted = Tensor());
   // n_all < 0: the kept fraction (what the adaptive first-pass choice reads) keeps its value
   void record_kept(int64_t n_kept, int64_t n_all = -1);
+
+  std::shared_ptr<OccupancyGrid> occupancy_;
 };
 
 namespace f2n

@@ -11,6 +11,7 @@
 // strides; the keep-mask is a wave ballot; a ray whose transmittance has dropped to <= t_thresh
 // stops issuing strides, so a terminated ray costs ceil(kept/64) strides, not S/64.
 #include "hash_grid.hiph"
+#include "occupancy.hiph"
 
 namespace
 {
@@ -158,6 +159,49 @@ __global__ __launch_bounds__(F2N_BLOCK) void sample_compact_kernel(
   }
 }
 
+// ---- f2n_sample_compact_occ ---------------------------------------------------------------------
+// f2n_sample_compact for a ray list thinned by the occupancy bitfield: the ray's samples are
+// {k < len_r : occupied(p_k)} in order of k.  Walks the same strides as the march, tests the same bit
+// on the same point, and writes sample k at start + rank (rank = occupied samples before it).
+
+__global__ __launch_bounds__(F2N_BLOCK) void sample_compact_occ_kernel(
+  const float * __restrict__ rays_o, const float * __restrict__ rays_d,
+  const float * __restrict__ noise, const int32_t * __restrict__ bounds,
+  const int32_t * __restrict__ len, const uint32_t * __restrict__ bits, int G,
+  float * __restrict__ pts, float * __restrict__ dirs, float * __restrict__ dt,
+  float * __restrict__ t, int n_rays, int S, float step)
+{
+  const int r = ray_of_wave();
+  if (r >= n_rays) return;
+  const int lane = lane_id();
+  const int start = bounds[2 * r];
+  const int cnt = bounds[2 * r + 1] - start;
+  const int n_len = min(len[r], S);
+  if (cnt <= 0 || n_len <= 0) return;
+  const RayFrame rf = load_ray(rays_o, rays_d, r);
+  const float * nrow = noise ? noise + (int64_t)r * S : nullptr;
+  StrideCarry carry = {0.f, 0.f, 0.f, 0.f};
+  int base = 0;  // occupied samples of the earlier strides
+  for (int k0 = 0; k0 < n_len && base < cnt; k0 += F2N_WAVE) {
+    const StrideSample sm = make_stride(rf, nrow, k0, S, step, carry, lane);
+    const bool occ = (k0 + lane < n_len) && occ_test_point(sm.px, sm.py, sm.pz, bits, G);
+    const unsigned long long m = __ballot(occ);
+    const int rank = base + __popcll(m & ((1ull << lane) - 1ull));
+    if (occ && rank < cnt) {  // (rank < cnt always when bounds and len come from the same grid)
+      const int64_t i = (int64_t)start + rank;
+      pts[3 * i] = sm.px;
+      pts[3 * i + 1] = sm.py;
+      pts[3 * i + 2] = sm.pz;
+      dirs[3 * i] = rf.dx;
+      dirs[3 * i + 1] = rf.dy;
+      dirs[3 * i + 2] = rf.dz;
+      dt[i] = sm.dt;
+      t[i] = sm.t;
+    }
+    base += __popcll(m);
+  }
+}
+
 // ---- f2n_density_march --------------------------------------------------------------------------
 
 template <int F, bool POW2>
@@ -206,6 +250,72 @@ __global__ __launch_bounds__(F2N_BLOCK) void density_march_kernel(
     depth_carry += wave_bcast_last(incl);
   }
   if (lane == 0) kept[r] = n_kept;
+}
+
+// ---- f2n_density_march_occ ----------------------------------------------------------------------
+// density_march_kernel with the density of every sample in an unoccupied cell set to exactly zero:
+// the lane tests its bit before the level loop, a stride without an occupied sample skips the level
+// loop as a whole (wave-uniform) and only advances make_stride's carries, and unoccupied lanes feed
+// 0.f into the same wave scan -- the scan's additions stay those of density_march_kernel, so an
+// all-ones grid gives its counts bit for bit.  len[r] = leading samples with T > t_thresh (still a
+// prefix), kept[r] = the occupied ones among them.
+template <int F, bool POW2>
+__global__ __launch_bounds__(F2N_BLOCK) void density_march_occ_kernel(
+  const float * __restrict__ rays_o, const float * __restrict__ rays_d,
+  const float * __restrict__ noise, const uint16_t * __restrict__ table,
+  const int32_t * __restrict__ primes, const float * __restrict__ bias,
+  const float * __restrict__ mul, const float * __restrict__ w0, const float * __restrict__ b0,
+  const uint32_t * __restrict__ bits, int G, int32_t * __restrict__ kept,
+  int32_t * __restrict__ len, int n_rays, int S, float step, int L, uint32_t T,
+  int64_t level_stride, float t_thresh, float density_shift)
+{
+  const int r = ray_of_wave();
+  if (r >= n_rays) return;
+  const int lane = lane_id();
+  const RayFrame rf = load_ray(rays_o, rays_d, r);
+  const float * nrow = noise ? noise + (int64_t)r * S : nullptr;
+  const float bias0 = b0[0];
+  StrideCarry carry = {0.f, 0.f, 0.f, 0.f};
+  float depth_carry = 0.f;
+  int n_kept = 0, n_len = 0;
+  for (int k0 = 0; k0 < S; k0 += F2N_WAVE) {
+    const StrideSample sm = make_stride(rf, nrow, k0, S, step, carry, lane);
+    float x = sm.px, y = sm.py, z = sm.pz;
+    contract_point(x, y, z);
+    const bool occ = sm.valid && occ_test_contracted(x, y, z, bits, G);
+    const unsigned long long om = __ballot(occ);
+    float sec = 0.f;
+    if (om != 0ull) {  // (wave-uniform: an empty stride costs no gathers at all)
+      if (occ) {       // (no cross-lane move inside: the scan below runs with every lane on)
+        float logit = bias0;
+        for (int l = 0; l < L; l++) {
+          const LevelParams lp = load_level(primes, bias, mul, l);
+          uint32_t row[8];
+          float w[8], acc[F];
+          corner_rows_and_weights<POW2>(x, y, z, lp, T, row, w);
+          gather_blend<F>(table + level_stride * l, row, w, acc);
+#pragma unroll
+          for (int k = 0; k < F; k++) logit = fmaf(round_f16(acc[k]), w0[l * F + k], logit);
+        }
+        const float sigma = expf(logit - density_shift);
+        sec = sigma * sm.dt;
+      }
+    }
+    const float incl = wave_incl_scan(sec);
+    const float depth = depth_carry + wave_shift_up1(incl, 0.f);
+    const float trans = expf(-depth);
+    const bool keep = sm.valid && (trans > t_thresh);
+    const unsigned long long m = __ballot(keep);
+    n_len += __popcll(m);
+    n_kept += __popcll(m & om);
+    const int n_valid = min(F2N_WAVE, S - k0);
+    if (__popcll(m) < n_valid) break;  // the mask is a prefix: nothing later survives
+    depth_carry += wave_bcast_last(incl);
+  }
+  if (lane == 0) {
+    kept[r] = n_kept;
+    len[r] = n_len;
+  }
 }
 
 // Four rays per wavefront, one per 16-lane DPP row, strides of 16 samples: a ray that stops after a
@@ -769,6 +879,55 @@ extern "C" int f2n_density_march(
     default: if (p2) F2N_MARCH(8, true); else F2N_MARCH(8, false); break;
   }
 #undef F2N_MARCH
+  return f2n_launch_status();
+}
+
+extern "C" int f2n_density_march_occ(
+  const float * rays_o, const float * rays_d, const float * noise, const uint16_t * table_f16,
+  const int32_t * primes, const float * bias, const float * mul, const float * w0, const float * b0,
+  const uint32_t * bits, int G, int32_t * kept, int32_t * len, int n_rays, int S, float step, int L,
+  int F, uint32_t T, int64_t level_stride, float t_thresh, float density_shift, void * stream)
+{
+  if (n_rays < 0 || S < 1 || L < 1 || L > F2N_MAX_LEVELS || T < 1 || level_stride < 0 ||
+      !f2n_occ_res_ok(G))
+    return F2N_E_INVALID_ARG;
+  if (F != 1 && F != 2 && F != 4 && F != 8) return F2N_E_UNSUPPORTED;
+  if (level_stride % F) return F2N_E_INVALID_ARG;
+  if (n_rays == 0) return F2N_OK;
+  if (!rays_o || !rays_d || !table_f16 || !primes || !bias || !mul || !w0 || !b0 || !bits ||
+      !kept || !len)
+    return F2N_E_INVALID_ARG;
+  if (reinterpret_cast<uintptr_t>(table_f16) % (2u * F)) return F2N_E_INVALID_ARG;
+  const dim3 grid(f2n_div_up(n_rays, F2N_WAVES_PER_BLOCK)), block(F2N_BLOCK);
+  hipStream_t s = (hipStream_t)stream;
+  const bool p2 = is_pow2(T);
+#define F2N_MARCH_OCC(FF, P2)                                                                     \
+  hipLaunchKernelGGL(                                                                             \
+    (density_march_occ_kernel<FF, P2>), grid, block, 0, s, rays_o, rays_d, noise, table_f16,      \
+    primes, bias, mul, w0, b0, bits, G, kept, len, n_rays, S, step, L, T, level_stride, t_thresh, \
+    density_shift)
+  switch (F) {
+    case 1: if (p2) F2N_MARCH_OCC(1, true); else F2N_MARCH_OCC(1, false); break;
+    case 2: if (p2) F2N_MARCH_OCC(2, true); else F2N_MARCH_OCC(2, false); break;
+    case 4: if (p2) F2N_MARCH_OCC(4, true); else F2N_MARCH_OCC(4, false); break;
+    default: if (p2) F2N_MARCH_OCC(8, true); else F2N_MARCH_OCC(8, false); break;
+  }
+#undef F2N_MARCH_OCC
+  return f2n_launch_status();
+}
+
+extern "C" int f2n_sample_compact_occ(
+  const float * rays_o, const float * rays_d, const float * noise, const int32_t * bounds,
+  const int32_t * len, const uint32_t * bits, int G, float * pts, float * dirs, float * dt,
+  float * t, int n_rays, int S, float step, void * stream)
+{
+  if (n_rays < 0 || S < 1 || !f2n_occ_res_ok(G)) return F2N_E_INVALID_ARG;
+  if (n_rays == 0) return F2N_OK;
+  if (!rays_o || !rays_d || !bounds || !len || !bits) return F2N_E_INVALID_ARG;
+  hipLaunchKernelGGL(
+    sample_compact_occ_kernel, dim3(f2n_div_up(n_rays, F2N_WAVES_PER_BLOCK)), dim3(F2N_BLOCK), 0,
+    (hipStream_t)stream, rays_o, rays_d, noise, bounds, len, bits, G, pts, dirs, dt, t, n_rays, S,
+    step);
   return f2n_launch_status();
 }
 

@@ -316,6 +316,63 @@ int f2n_sample_compact(
   const float * rays_o, const float * rays_d, const float * noise, const int32_t * bounds,
   float * pts, float * dirs, float * dt, float * t, int n_rays, int S, float step, void * stream);
 
+/* ------------------------------------------------------------------ occupancy bitfield -------- */
+
+/* Empty-space skipping for the early-stop march.  The reference fork stripped upstream's occupancy
+ * grid and kept only its trace (src/main_functions/train_manager.cpp:102, "output colors have no
+ * grad due to the occupancy grid"), so its first pass (src/renderer.cpp:58-90) evaluates the field on
+ * every sample in front of the first surface.  The grid: G x G x G bits over the contracted space
+ * [-2, 2)^3 (src/hash_3d_anchored.cpp:79-82), G a power of two in 32..256; per axis
+ *   c = (int)floorf((x + 2.f) * (0.25f * (float)G)) clamped to [0, G-1],
+ * bit i = (cz*G + cy)*G + cx in bit (i & 31) of uint32 word (i >> 5); bits is [G^3 / 32] words.  A
+ * point with a non-finite contracted coordinate (|p| = 0, quirk Q6) reads as occupied.
+ * Rendering with a grid is the reference's render with the density of every sample in an unoccupied
+ * cell set to exactly zero and those samples dropped; with an all-ones grid it is today's render. */
+
+/* One maintenance pass over all G^3 cells, one thread per cell, no atomics (the same bits on every
+ * run).  Per cell the density sigma = exp(w0 . f16(enc(x)) + b0 - density_shift) at ONE probe point
+ * x = ((float)c + u) * (4.f / G) - 2.f per axis -- a contracted-space point, so no contraction --
+ * with the gather, f16 rounding and level-ordered FMA chain of f2n_density_march (the field
+ * evaluation of src/renderer.cpp:61-62); then
+ *   density[i] = max(density[i] * decay, sigma),  bit i = density[i] > threshold.
+ *   probe_u    [G^3, 3] f32 in [0,1), cell i's offsets (x, y, z), or NULL for the cell centre (0.5)
+ *   density    [G^3] f32, read and written; bits [G^3/32] overwritten
+ * A sample whose density equals the threshold carries at most threshold * 1.5 * step of optical depth
+ * under TRAIN jitter (src/points_sampler.cpp:31-36).  A probe is one point, not a bound on its cell:
+ * hence the decay (a cell seen dense stays on for a while) and the caller-supplied jitter u. */
+int f2n_occ_update(
+  const uint16_t * table_f16, const int32_t * primes, const float * bias, const float * mul,
+  const float * w0, const float * b0, const float * probe_u, float * density, uint32_t * bits, int G,
+  int L, int F, uint32_t T, int64_t level_stride, float density_shift, float threshold, float decay,
+  void * stream);
+
+/* The lookup every kernel below uses, on its own: raw (uncontracted) points [n,3] in, out[i] = 1 if
+ * the cell of contract(pts[i]) (src/hash_3d_anchored.cpp:79-82) is occupied, else 0. */
+int f2n_occ_lookup(
+  const float * pts, int64_t n, const uint32_t * bits, int G, uint8_t * out, void * stream);
+
+/* f2n_density_march (src/renderer.cpp:58-90 with src/points_sampler.cpp:20-64) with a grid: the
+ * sampler is unchanged (sample k keeps the t, p, dt of the full sequence),
+ *   sec_k = occupied(p_k) ? sigma_k * dt_k : 0,  T_k = exp(-exclusive_scan(sec)),
+ *   len[r]  = number of leading samples with T_k > t_thresh (a prefix, as at :68),
+ *   kept[r] = number of occupied samples among them: the ray's sample list is
+ *             {k < len[r] : occupied(p_k)} in order of k.
+ * One wavefront per ray in 64-sample strides; a stride without an occupied sample is not encoded.
+ * The scan adds what f2n_density_march's adds: with an all-ones grid kept = len = its kept. */
+int f2n_density_march_occ(
+  const float * rays_o, const float * rays_d, const float * noise, const uint16_t * table_f16,
+  const int32_t * primes, const float * bias, const float * mul, const float * w0, const float * b0,
+  const uint32_t * bits, int G, int32_t * kept, int32_t * len, int n_rays, int S, float step, int L,
+  int F, uint32_t T, int64_t level_stride, float t_thresh, float density_shift, void * stream);
+
+/* f2n_sample_compact (src/renderer.cpp:69-74) for that list: bounds from f2n_bounds_from_counts on
+ * kept, len from f2n_density_march_occ with the same grid; sample k of the list is written at
+ * bounds[r].start + (number of occupied samples before k).  Outputs as f2n_sample_compact. */
+int f2n_sample_compact_occ(
+  const float * rays_o, const float * rays_d, const float * noise, const int32_t * bounds,
+  const int32_t * len, const uint32_t * bits, int G, float * pts, float * dirs, float * dt,
+  float * t, int n_rays, int S, float step, void * stream);
+
 /* ------------------------------------------------------------------ ray order --------------- */
 
 /* Bucketing of a ray batch for the gather locality of f2n_hash_fwd_raytile (no reference
