@@ -32,6 +32,15 @@
 // arena costs 1-3 ms per 8.4 M dense samples on single-level tables and 9 % of pass A on config C5).
 // A direct add is order-dependent in the last bit, like the reference's own atomics, and counted
 // (f2n_hash_bwd_set_overflow_counter).
+//
+// What "exact" covers, element by element (tests/util.py: assert_table_grad): the sum of one level and
+// one round is exact and rounded to f32 once, in flush_slice.  An element of the gradient is that
+// correctly rounded sum, bit for bit, when the counter reads 0, the call fits one round (a workspace
+// of f2n_hash_bwd_workspace_bytes) and at most two levels cover the element -- always on a disjoint
+// level stride, and at F <= 2 on the reference's stride (0 + a + b commutes).  Three or more
+// covering levels (F >= 4 at the reference's stride), several rounds over overlapping windows, or an
+// existing gradient under overlapping windows put three or more float adds on one element: their
+// order shows in its last bit (F2N_OPT_BWD_PHASES = 1 removes that, see f2n_hash_bwd_binned).
 #include "hash_grid.hiph"
 
 #include <algorithm>

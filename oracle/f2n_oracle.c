@@ -271,6 +271,52 @@ void f2no_hash_bwd(
   }
 }
 
+/* The table gradient as EXACT integer sums.  Every contribution c = f16(f16(grad_scale*g) * w_d) of
+ * hash_bwd_point is an integer multiple of 2^-24 below 2^16, so c * 2^24 is an integer below 2^40
+ * and a 64-bit sum of them has no rounding and no order.  Per (level, row, channel), arrays of
+ * shape [L, T*F] (levels kept apart: the caller composes overlapping level windows, quirk Q2):
+ *   S : sum of c * 2^24            A : sum of |c| * 2^24            N : number of non-zero c
+ * Integer adds commute, so the parallel loop is deterministic.  A non-finite c is not summed;
+ * the return value counts them (0 = S, A, N describe the whole gradient).  The caller zeroes. */
+int64_t f2no_hash_bwd_fixed(
+  const float * pts, const int32_t * primes, const float * bias, const float * mul,
+  const float * grad_out, int64_t * S, int64_t * A, int32_t * N, int64_t n, int L, int F,
+  uint32_t T, float grad_scale)
+{
+  int64_t nonfinite = 0;
+#pragma omp parallel for schedule(static) reduction(+ : nonfinite)
+  for (int64_t p = 0; p < n; p++) {
+    for (int l = 0; l < L; l++) {
+      const int64_t lbase = (int64_t)l * T * F;
+      float pt[3], w[8];
+      uint32_t pos[8];
+      scale_point(pts + 3 * p, mul[l], bias + 3 * l, pt);
+      pos_and_w(pt, T, primes + 3 * l, pos, w);
+      const float * g = grad_out + p * (int64_t)(L * F) + l * F;
+      for (int d = 0; d < 8; d++) {
+        for (int k = 0; k < F; k++) {
+          const float gk = round_f16(g[k] * grad_scale);
+          const float c = round_f16(gk * w[d]);
+          if (!isfinite(c)) {
+            nonfinite++;
+            continue;
+          }
+          if (c == 0.f) continue;
+          const int64_t q = (int64_t)(c * 16777216.f); /* exact: 11 significant bits, |q| < 2^40 */
+          const int64_t i = lbase + (int64_t)pos[d] * F + k;
+#pragma omp atomic
+          S[i] += q;
+#pragma omp atomic
+          A[i] += (q < 0 ? -q : q);
+#pragma omp atomic
+          N[i] += 1;
+        }
+      }
+    }
+  }
+  return nonfinite;
+}
+
 /* embeds_grad.to(f32) / grad_scale: src/hash_3d_anchored.cu:215 */
 void f2no_div_inplace(float * x, int64_t n, float div)
 {

@@ -19,6 +19,7 @@ _SIGS = {
     "f2no_level_mul": (None, [c_i, c_p]),
     "f2no_hash_fwd": (None, [c_p] * 7 + [c_i64, c_i, c_i, c_u32, c_i64]),
     "f2no_hash_bwd": (None, [c_p] * 8 + [c_i64, c_i, c_i, c_u32, c_i64, c_f, c_i]),
+    "f2no_hash_bwd_fixed": (c_i64, [c_p] * 8 + [c_i64, c_i, c_i, c_u32, c_f]),
     "f2no_div_inplace": (None, [c_p, c_i64, c_f]),
     "f2no_sh_encode": (None, [c_p, c_p, c_i64, c_i]),
     "f2no_seg_sum_fwd": (None, [c_p, c_p, c_p, c_i]),
@@ -116,6 +117,25 @@ def hash_bwd(pts, table_f16, primes, bias, mul, grad_out, table_numel, L, F, T, 
                         grad_scale, int(parallel))
     lib().f2no_div_inplace(_p(tg), tg.numel(), grad_scale)
     return tg, pg
+
+
+def hash_bwd_exact(pts, primes, bias, mul, grad_out, L, F, T, grad_scale=128.0):
+    """The table gradient as exact integer sums per (level, row, channel), each of shape [L, T*F]:
+    S = sum of the contributions * 2^24 (int64), A = sum of their magnitudes * 2^24 (int64),
+    N = number of non-zero contributions (int32).  No rounding, no summation order; the levels stay
+    apart so the caller can compose any level stride.  A non-finite contribution is an error here."""
+    pts = _f32(pts)
+    n = pts.shape[0]
+    g = _f32(grad_out)
+    assert g.shape == (n, L * F)
+    S = torch.zeros(L, T * F, dtype=torch.int64)
+    A = torch.zeros(L, T * F, dtype=torch.int64)
+    N = torch.zeros(L, T * F, dtype=torch.int32)
+    bad = lib().f2no_hash_bwd_fixed(_p(pts), _p(_i32(primes)), _p(_f32(bias)), _p(_f32(mul)), _p(g),
+                                    _p(S), _p(A), _p(N), n, L, F, T, grad_scale)
+    if bad:
+        raise ValueError("%d non-finite contributions: the exact sum is not defined" % bad)
+    return S, A, N
 
 
 def sh_encode(dirs, degree=4):

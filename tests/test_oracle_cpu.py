@@ -127,6 +127,193 @@ def test_hash_bwd_oracle_vs_autograd():
     assert (tg.double() - ref).abs().max() <= 5e-3 * ref.abs().max()
 
 
+# ---------------------------------------------------------- exact table gradient (integer sums) ---
+
+
+@pytest.mark.parametrize("stride_mode", ["ref", "disjoint"])
+@pytest.mark.parametrize("F", [1, 2, 8])
+def test_hash_bwd_exact_vs_per_point_tables(stride_mode, F):
+    """K.hash_bwd_exact against a formulation that shares no accumulation code with it: the f32
+    oracle run on ONE point at a time into a fresh zero table, the per-point tables added in float64.
+    Gradients are clamped so that |f16(128 g)| <= 1/4: a point then contributes at most 8 values per
+    level whose magnitudes sum to about 1/4 (the weights sum to 1), at most L = 3 levels overlap, so
+    every partial sum of a per-point table is a multiple of 2^-24 below 1 -- 24 bits, exact in f32
+    whatever collides.  (Unclamped sums could reach 1 and lose a subnormal-f16 contribution's last
+    bit.)  T is not a power of two."""
+    L, T, n, scale = 3, 1000, 48, 128.0
+    fld = util.make_field(L, F, 10, None if stride_mode == "ref" else T * F, seed=40 + F)
+    st = T if stride_mode == "ref" else T * F
+    numel = st * (L - 1) + T * F
+    pts = util.ball_points(n, seed=44)
+    pts[0] = torch.tensor([-1.99, -1.99, -1.99])            # saturating cell (quirk Q1)
+    g = torch.Generator().manual_seed(45)
+    grad = (torch.randn(n, L * F, generator=g) * 1e-3).clamp(-0.25 / scale, 0.25 / scale)
+    grad[torch.rand(n, L * F, generator=g) < 0.1] = 0.0
+    grad[1] = 3e-7                                          # f16 subnormal contributions
+    S, A, N = K.hash_bwd_exact(pts, fld["primes"], fld["bias"], fld["mul"], grad, L, F, T, scale)
+    ex = util.table_grad_expectation(S, A, N, L, F, T, st, scale, numel)
+    total = torch.zeros(numel, dtype=torch.float64)
+    count = torch.zeros(numel, dtype=torch.int64)
+    for p in range(n):
+        tg, _ = K.hash_bwd(pts[p:p + 1], fld["table16"], fld["primes"], fld["bias"], fld["mul"],
+                           grad[p:p + 1], numel, L, F, T, st, scale)
+        total += tg.double()
+        count += (tg != 0)
+    assert torch.equal(total, ex["exact"])
+    assert int(N.sum()) > 0 and int(S.abs().sum()) > 0
+    assert bool(((count == 0) | (ex["cover"] > 0)).all())   # nothing lands outside the cover
+    assert bool((A >= S.abs()).all()) and bool(((N == 0) == (A == 0)).all())
+    if stride_mode == "ref" and F > 1:
+        assert int(ex["cover"].max()) >= 2                  # the level windows did overlap
+
+
+def test_hash_bwd_exact_reports_nonfinite():
+    L, F, T = 2, 2, 64
+    fld = util.make_field(L, F, 6, None, seed=1)
+    pts = util.ball_points(4, seed=1)
+    grad = torch.full((4, L * F), 1e-3)
+    grad[2, 1] = 1e3                                        # 128e3 is beyond the f16 range
+    with pytest.raises(ValueError):
+        K.hash_bwd_exact(pts, fld["primes"], fld["bias"], fld["mul"], grad, L, F, T, 128.0)
+
+
+BINNED_CONFIGS = [(16, 2, 19, "ref", 70000), (4, 4, 17, "disjoint", 66000),
+                  (3, 8, 18, "disjoint", 70000)]
+
+
+@pytest.fixture(scope="module")
+def binned_case():
+    cache = {}
+
+    def get(cfg):
+        if cfg not in cache:
+            L, F, log2_T, stride_mode, n = cfg
+            T = 1 << log2_T
+            fld, pts, grad = util.binned_path_inputs(L, F, log2_T, stride_mode, n)
+            numel = fld["table"].numel()
+            S, A, N = K.hash_bwd_exact(pts, fld["primes"], fld["bias"], fld["mul"], grad, L, F, T)
+            ex = util.table_grad_expectation(S, A, N, L, F, T, fld["stride"], 128.0, numel)
+            ref, _ = K.hash_bwd(pts, fld["table16"], fld["primes"], fld["bias"], fld["mul"], grad,
+                                numel, L, F, T, fld["stride"], 128.0, parallel=False)
+            cache[cfg] = dict(ex=ex, ref=ref, F=F)
+        return cache[cfg]
+    return get
+
+
+@pytest.mark.parametrize("cfg", BINNED_CONFIGS)
+def test_f32_oracle_is_within_the_exact_bound(binned_case, cfg, capsys):
+    """The serial f32 oracle sum on the inputs of test_hash_bwd_binned_path: untouched elements
+    stay zero and every element lies within the any-order bound of the exact sum -- with room (the
+    largest err/bound seen is below 0.01).  It is NOT the correctly rounded exact sum everywhere:
+    a few elements in 10^5 differ from rne, which is why the device tests need the exact reference
+    and cannot assert bit-equality against this oracle."""
+    c = binned_case(cfg)
+    stats = util.assert_table_grad(c["ref"], c["ex"])
+    touched = c["ex"]["cover"] > 0
+    differ = (c["ref"].view(torch.int32) != c["ex"]["rne"].view(torch.int32)) & touched
+    share = float(differ.sum()) / float(touched.sum())
+    with capsys.disabled():
+        print("\n[table-grad] config %s: f32 oracle != rne on %d of %d touched elements (%.2e), "
+              "max err/bound %.4f" % (cfg, int(differ.sum()), int(touched.sum()), share,
+                                      stats["max_ratio"]))
+    assert share > 0
+
+
+def _sub_tolerance_single(c):
+    """Elements that exactly one non-zero contribution reaches and whose whole value is below the
+    old global tolerance 2e-5 max|ref|, with room for the next row."""
+    ex, ref, F = c["ex"], c["ref"], c["F"]
+    tol = 2e-5 * ref.abs().max().item()
+    cand = torch.nonzero((ex["count"] == 1) & (ex["rne"].abs() < 0.5 * tol))
+    cand = cand[cand < ex["rne"].numel() - F]
+    return cand.reshape(-1)
+
+
+@pytest.mark.parametrize("cfg", BINNED_CONFIGS)
+def test_assert_table_grad_catches_what_the_old_criterion_misses(binned_case, cfg):
+    c = binned_case(cfg)
+    ex, ref, F = c["ex"], c["ref"], c["F"]
+    rne = ex["rne"]
+    util.assert_table_grad(rne, ex, exact_elements=True)        # the expectation accepts itself
+    util.old_table_grad_criterion(rne, ref)
+    cand = _sub_tolerance_single(c)
+    assert cand.numel() > 1000, cand.numel()                    # they exist, in numbers
+    e = int(cand[cand.numel() // 2])
+
+    # (i) one single-contribution element below the old tolerance is lost
+    lost = rne.clone()
+    lost[e] = 0.0
+    util.old_table_grad_criterion(lost, ref)
+    with pytest.raises(AssertionError, match=r"\(b\)"):
+        util.assert_table_grad(lost, ex)
+
+    # (ii) ... or lands on the next row
+    moved = rne.clone()
+    moved[e + F] += moved[e]
+    moved[e] = 0.0
+    util.old_table_grad_criterion(moved, ref)
+    with pytest.raises(AssertionError, match=r"\((a|b)\)"):
+        util.assert_table_grad(moved, ex)
+
+    # (iii) one f32 ulp on the element with the most contributions (well inside its bound)
+    big = int(ex["bound"].argmax())
+    assert ex["bound"][big] > 4 * float(util.f32_ulp(rne[big:big + 1]))
+    ulp = rne.clone()
+    ulp[big] = torch.nextafter(ulp[big], torch.tensor(float("inf")))
+    util.old_table_grad_criterion(ulp, ref)
+    util.assert_table_grad(ulp, ex)                             # (a), (b) alone do not see it
+    with pytest.raises(AssertionError, match=r"\(c\)"):
+        util.assert_table_grad(ulp, ex, exact_elements=True)
+    # ... and an allowance for exceptions is counted, not a blanket
+    assert util.assert_table_grad(ulp, ex, exact_elements=True, max_inexact=1)["inexact"] == 1
+    ulp[e] = torch.nextafter(ulp[e], torch.tensor(float("inf")))
+    with pytest.raises(AssertionError):
+        util.assert_table_grad(ulp, ex, exact_elements=True, max_inexact=1)
+
+    # ... and a two-contribution element off by one ulp is caught without being asked for:
+    # one or two f16-valued terms have one possible f32 sum on any route
+    two = torch.nonzero((ex["count"] == 2) & (ex["bound"] > 2 * util.f32_ulp(rne).double())).reshape(-1)
+    assert two.numel() > 0
+    off = rne.clone()
+    i2 = int(two[0])
+    off[i2] = torch.nextafter(off[i2], torch.tensor(float("inf")))
+    util.old_table_grad_criterion(off, ref)
+    util.assert_table_grad(off, ex, few_exact=False)            # within (a) and (b)
+    with pytest.raises(AssertionError, match=r"\(e\)"):
+        util.assert_table_grad(off, ex)
+
+    # (iv) a small value in an element nobody contributes to
+    free = torch.nonzero(ex["cover"] == 0).reshape(-1)
+    assert free.numel() > 0
+    stray = rne.clone()
+    stray[int(free[free.numel() // 2])] = 1e-12
+    with pytest.raises(AssertionError, match=r"\(a\)"):
+        util.assert_table_grad(stray, ex)
+
+
+def test_table_grad_expectation_with_base():
+    """Accumulating onto an existing gradient: untouched elements keep base's bits, rne is
+    fl32(base + add) on a disjoint stride, and the bound grows by an ulp per covering level."""
+    L, F, log2_T, n = 2, 2, 14, 300
+    T = 1 << log2_T
+    fld = util.make_field(L, F, log2_T, T * F, seed=2)
+    pts = util.ball_points(n, seed=3)
+    g = torch.Generator().manual_seed(4)
+    grad = torch.randn(n, L * F, generator=g) * 1e-3
+    numel = fld["table"].numel()
+    base = torch.randn(numel, generator=g) * 1e-3
+    S, A, N = K.hash_bwd_exact(pts, fld["primes"], fld["bias"], fld["mul"], grad, L, F, T)
+    ex0 = util.table_grad_expectation(S, A, N, L, F, T, fld["stride"], 128.0, numel)
+    ex = util.table_grad_expectation(S, A, N, L, F, T, fld["stride"], 128.0, numel, base=base)
+    assert torch.equal(ex["rne"], base + ex0["rne"])
+    assert bool((ex["bound"] >= ex0["bound"]).all())
+    util.assert_table_grad(ex["rne"], ex, exact_elements=True)
+    with pytest.raises(AssertionError, match=r"\(a\)"):
+        util.assert_table_grad(ex0["rne"], ex)                  # base was dropped
+    free = torch.nonzero(ex["cover"] == 0).reshape(-1)
+    assert free.numel() > 0 and torch.equal(ex["rne"][free], base[free])
+
+
 def test_sh_basis_is_orthonormal():
     """Convention-free check of the 16 SH basis functions: the Gram matrix over the sphere is I."""
     nt, npz = 64, 128
