@@ -61,7 +61,10 @@ __global__ __launch_bounds__(F2N_BLOCK) void ray_key_kernel(
   const int ax = (a[0] >= a[1] && a[0] >= a[2]) ? 0 : (a[1] >= a[2] ? 1 : 2);
   const float m = a[ax];
   uint32_t key = 0;
-  if (m > 0.f && m <= 3.4e38f) {  // zero, infinite or NaN directions: key 0 (the order is a hint)
+  // zero, infinite or NaN directions: key 0 (the order is a hint).  A NaN loses every >=, so it is
+  // never the component picked above: (NaN, 1, 0) has m = 1, and the sum is what sees it.
+  const float all3 = a[0] + a[1] + a[2];  // NaN exactly when a component is
+  if (m > 0.f && m <= 3.4e38f && all3 == all3) {
     const float u = d[(ax + 1) % 3] / m, v = d[(ax + 2) % 3] / m;
     const uint32_t face = 2u * (uint32_t)ax + (d[ax] < 0.f ? 1u : 0u);
     key = (face << (2 * kCellBits)) | hilbert_index(quantise(u), quantise(v));

@@ -379,7 +379,8 @@ int f2n_sample_compact_occ(
  * counterpart: Renderer::render, src/renderer.cpp:33-123, renders rays in the order it is given
  * them; its RenderResult, :122, is what the gathers below restore).  keys [n] int32 (>= 0) from
  * the direction alone (cube-face projection, 14 bits per face axis, Hilbert order): sorted stably,
- * 64 consecutive rays of one view become a compact pixel blob. */
+ * 64 consecutive rays of one view become a compact pixel blob.  A zero direction, or one with an
+ * infinite or NaN component, has key 0. */
 int f2n_ray_keys(const float * rays_d, int32_t * keys, int n, void * stream);
 
 /* Inputs of ray j of the sorted order from caller ray order[j] (order: the int64 indices of a
