@@ -337,6 +337,104 @@ public:
   }
 };
 
+// ShadeFn on the sampler's dense [n_rays, S] grid, S % 64 == 0 (f2n_shade_fwd_rays /
+// f2n_shade_bwd_rays): `ray_img` [n_rays] in place of the per-sample ids, the rest as above.
+class ShadeRaysFn : public torch::autograd::Function<ShadeRaysFn>
+{
+public:
+  static variable_list forward(
+    AutogradContext * ctx, Tensor enc, Tensor dirs, Tensor ray_img, int64_t S, Tensor w_h,
+    Tensor b_h, Tensor w1, Tensor b1, Tensor w2, Tensor b2, Tensor app_emb)
+  {
+    TORCH_CHECK(enc.is_cuda() && enc.scalar_type() == torch::kFloat32 && enc.dim() == 2, "enc");
+    const int64_t n = enc.size(0);
+    const int C = (int)enc.size(1);
+    TORCH_CHECK(S > 0 && S % 64 == 0 && n % S == 0 && n < ((int64_t)1 << 28), "shade_rays: n = n_rays * S, S % 64 == 0");
+    const int n_rays = (int)(n / S);
+    Tensor enc_cm = as_channel_major(enc);  // [C, n] contiguous
+    dirs = f2n::dev_f32(dirs.detach(), "shade dirs");
+    TORCH_CHECK(dirs.numel() == n * 3, "shade_rays: dirs [n, 3]");
+    const bool use_emb =
+      ray_img.defined() && app_emb.defined() && ray_img.numel() > 0 && app_emb.numel() > 0;
+    if (use_emb) {
+      ray_img = f2n::dev_i32(ray_img, "shade ray_img");
+      TORCH_CHECK(ray_img.numel() == n_rays, "shade_rays: ray_img [n_rays]");
+    }
+    w_h = f2n::dev_f32(w_h, "w_h");
+    b_h = f2n::dev_f32(b_h, "b_h");
+    w1 = f2n::dev_f32(w1, "w1");
+    b1 = f2n::dev_f32(b1, "b1");
+    w2 = f2n::dev_f32(w2, "w2");
+    b2 = f2n::dev_f32(b2, "b2");
+    Tensor emb = use_emb ? f2n::dev_f32(app_emb, "app_emb") : Tensor();
+    TORCH_CHECK(
+      w_h.size(0) == 16 && w_h.size(1) == C && w1.size(0) == 64 && w1.size(1) == 32 &&
+        w2.size(0) == 3 && w2.size(1) == 64,
+      "shade: layer shapes must be 16xC, 64x32, 3x64");
+    Tensor logit = torch::empty({n}, enc.options()), rgb = torch::empty({n, 3}, enc.options());
+    {
+    f2n::ScopedKernelTimer timer("shade_fwd", f2n::current_stream(enc_cm), (double)n);
+    f2n::check(
+      f2n_shade_fwd_rays(
+        enc_cm.data_ptr<float>(), C, dirs.data_ptr<float>(), use_emb ? f2n::iptr(ray_img) : nullptr,
+        f2n::fptr(w_h), f2n::fptr(b_h), f2n::fptr(w1), f2n::fptr(b1), f2n::fptr(w2), f2n::fptr(b2),
+        f2n::fptr(emb), logit.data_ptr<float>(), rgb.data_ptr<float>(), n_rays, (int)S,
+        f2n::current_stream(enc_cm)),
+      "f2n_shade_fwd_rays");
+    }
+    ctx->save_for_backward(
+      {enc_cm, dirs, use_emb ? ray_img : Tensor(), w_h, b_h, w1, b1, w2, b2, emb});
+    ctx->saved_data["S"] = S;
+    return {logit, rgb};
+  }
+
+  static variable_list backward(AutogradContext * ctx, variable_list grad_output)
+  {
+    auto sv = ctx->get_saved_variables();
+    Tensor &enc_cm = sv[0], &dirs = sv[1], &ray_img = sv[2], &w_h = sv[3], &b_h = sv[4],
+           &w1 = sv[5], &b1 = sv[6], &w2 = sv[7], &b2 = sv[8], &emb = sv[9];
+    const int C = (int)enc_cm.size(0);
+    const int64_t n = enc_cm.size(1), S = ctx->saved_data["S"].toInt();
+    auto opt = enc_cm.options();
+    Tensor d_logit = grad_output[0].defined() ? f2n::dev_f32(grad_output[0], "d_logit")
+                                              : torch::zeros({n}, opt);
+    Tensor d_rgb = grad_output[1].defined() ? f2n::dev_f32(grad_output[1], "d_rgb")
+                                            : torch::zeros({n, 3}, opt);
+    Tensor d_enc_cm = torch::empty({(int64_t)C, n}, opt);
+    // one zero-filled buffer behind the seven parameter gradients, as in ShadeFn
+    const bool use_emb = emb.defined() && ray_img.defined();
+    auto pad4 = [](int64_t v) { return (v + 3) / 4 * 4; };
+    const int64_t sizes[7] = {w_h.numel(), b_h.numel(), w1.numel(), b1.numel(),
+                              w2.numel(), b2.numel(), use_emb ? emb.numel() : 0};
+    int64_t total = 0;
+    for (int64_t v : sizes) total += pad4(v);
+    Tensor gbuf = torch::zeros({total}, opt);
+    int64_t off = 0;
+    auto take = [&](const Tensor & like, int64_t numel) {
+      Tensor v = gbuf.narrow(0, off, numel).view(like.sizes());
+      off += pad4(numel);
+      return v;
+    };
+    Tensor g_w_h = take(w_h, sizes[0]), g_b_h = take(b_h, sizes[1]), g_w1 = take(w1, sizes[2]),
+           g_b1 = take(b1, sizes[3]), g_w2 = take(w2, sizes[4]), g_b2 = take(b2, sizes[5]);
+    Tensor g_emb = use_emb ? take(emb, sizes[6]) : Tensor();  // undefined = no gradient
+    {
+    f2n::ScopedKernelTimer timer("shade_bwd", f2n::current_stream(enc_cm), (double)n);
+    f2n::check(
+      f2n_shade_bwd_rays(
+        enc_cm.data_ptr<float>(), C, dirs.data_ptr<float>(), use_emb ? f2n::iptr(ray_img) : nullptr,
+        f2n::fptr(w_h), f2n::fptr(b_h), f2n::fptr(w1), f2n::fptr(b1), f2n::fptr(w2), f2n::fptr(b2),
+        f2n::fptr(emb), f2n::fptr(d_logit), f2n::fptr(d_rgb), d_enc_cm.data_ptr<float>(),
+        g_w_h.data_ptr<float>(), g_b_h.data_ptr<float>(), g_w1.data_ptr<float>(),
+        g_b1.data_ptr<float>(), g_w2.data_ptr<float>(), g_b2.data_ptr<float>(),
+        use_emb ? g_emb.data_ptr<float>() : nullptr, (int)(n / S), (int)S,
+        f2n::current_stream(enc_cm)),
+      "f2n_shade_bwd_rays");
+    }
+    return {d_enc_cm.t(), Tensor(), Tensor(), Tensor(), g_w_h, g_b_h, g_w1, g_b1, g_w2, g_b2, g_emb};
+  }
+};
+
 
 class TrainLossFn : public torch::autograd::Function<TrainLossFn>
 {
@@ -420,6 +518,7 @@ Tensor CustomOps::ScatterIdx(int n_all_pts, Tensor idx_start_end, Tensor emb_idx
   idx_start_end = f2n::dev_i32(idx_start_end, "CustomOps::ScatterIdx idx_start_end");
   emb_idx = f2n::dev_i32(emb_idx, "CustomOps::ScatterIdx emb_idx");
   Tensor ret = torch::empty({n_all_pts}, idx_start_end.options());
+  f2n::ScopedKernelTimer timer("scatter_idx", f2n::current_stream(idx_start_end), (double)n_all_pts);
   f2n::check(
     f2n_scatter_idx(
       f2n::iptr(idx_start_end), f2n::iptr(emb_idx), ret.data_ptr<int32_t>(),
@@ -439,6 +538,26 @@ f2n::ShadeOut f2n::shade(
   auto out = ShadeFn::apply(
     enc, dirs, use_emb ? sample_img : no_img, w_h, b_h, w1, b1, w2, b2, use_emb ? app_emb : no_emb);
   return {out[0], out[1]};
+}
+
+f2n::ShadeOut f2n::shade_rays(
+  const Tensor & enc, const Tensor & dirs, const Tensor & ray_img, int64_t S, const Tensor & w_h,
+  const Tensor & b_h, const Tensor & w1, const Tensor & b1, const Tensor & w2, const Tensor & b2,
+  const Tensor & app_emb)
+{
+  const Tensor no_img = torch::empty({0}, f2n::int_on(enc.device()));
+  const Tensor no_emb = torch::empty({0, 16}, enc.options());
+  const bool use_emb = ray_img.defined() && app_emb.defined();
+  auto out = ShadeRaysFn::apply(
+    enc, dirs, use_emb ? ray_img : no_img, S, w_h, b_h, w1, b1, w2, b2, use_emb ? app_emb : no_emb);
+  return {out[0], out[1]};
+}
+
+bool f2n::shade_rays_applies(int64_t n, int64_t n_rays, int64_t S)
+{
+  return n_rays > 0 && S > 0 && S % 64 == 0 && n == n_rays * S && n < ((int64_t)1 << 28) &&
+         f2n_get_option(F2N_OPT_SHADE_RAYS) == 0 && f2n_get_option(F2N_OPT_SHADE_FWD) == 0 &&
+         f2n_get_option(F2N_OPT_SHADE_BWD) == 0;
 }
 
 f2n::CompositeOut f2n::composite(

@@ -71,6 +71,20 @@ ShadeOut shade(
   const Tensor & b_h, const Tensor & w1, const Tensor & b1, const Tensor & w2, const Tensor & b2,
   const Tensor & app_emb);
 
+// The same network on the sampler's dense grid: `enc` [n_rays * S, C] in ray-major order, S % 64
+// == 0, `dirs` the per-sample [n, 3] array holding the ray's direction in every sample of the ray,
+// `ray_img` [n_rays] int32 or undefined.  What is the same along a ray (SH(dirs), the embedding
+// row, the SH half of the hidden layer) is done once per 64 samples (f2n_shade_fwd_rays /
+// f2n_shade_bwd_rays).  logit equals shade()'s bit for bit, rgb and the gradients to rounding.
+ShadeOut shade_rays(
+  const Tensor & enc, const Tensor & dirs, const Tensor & ray_img, int64_t S, const Tensor & w_h,
+  const Tensor & b_h, const Tensor & w1, const Tensor & b1, const Tensor & w2, const Tensor & b2,
+  const Tensor & app_emb);
+
+// n samples form a dense [n_rays, S] grid that shade_rays serves, and no option asks for the
+// per-sample kernels (F2N_OPT_SHADE_RAYS = 1, or the vector kernels of F2N_OPT_SHADE_FWD / _BWD)
+bool shade_rays_applies(int64_t n, int64_t n_rays, int64_t S);
+
 // The loss of the training iteration (reference src/main_functions/train_manager.cpp:78-96) as one
 // autograd node over f2n_loss_fwd: returns [4] = {loss, color_loss, var_loss, sum of squared colour
 // error}; differentiable in colors [n_rays, 3] and var [n_rays] through element 0 (the others carry no

@@ -665,13 +665,24 @@ Renderer::Shaded Renderer::shade(
       enc, route.grad_rays.origins, route.grad_rays.dirs, kept.pts, kept.t, kept.pts_idx_bounds,
       torch::IValue(info))[0];
   }
+  auto mlp = shader_->mlp_params();
+  const Tensor emb = mode == RunningMode::TRAIN ? app_emb_ : Tensor();
+  // The sampler's whole [n_rays, max_samples] grid (the dense first pass, or a march that kept
+  // everything): the ray-uniform kernels, which take the image id per ray.  The rule looks at the
+  // shape of the samples alone, so every route that hands over the same samples gets the same bits.
+  const int64_t n_rays = kept.pts_idx_bounds.size(0), S = pts_sampler_->options_.max_samples;
+  if (f2n::shade_rays_applies(n_kept, n_rays, S)) {
+    f2n::ShadeOut sh = f2n::shade_rays(
+      enc, kept.dirs, mode == RunningMode::TRAIN ? emb_idx : Tensor(), S,
+      scene_field_->mlp_->weight, scene_field_->mlp_->bias, mlp[0], mlp[1], mlp[2], mlp[3], emb);
+    return {sh.logit.unsqueeze(1), sh.rgb};
+  }
   Tensor sample_img;
   if (mode == RunningMode::TRAIN)
     sample_img = CustomOps::ScatterIdx((int)n_kept, kept.pts_idx_bounds, emb_idx);
-  auto mlp = shader_->mlp_params();
   f2n::ShadeOut sh = f2n::shade(
     enc, kept.dirs, sample_img, scene_field_->mlp_->weight, scene_field_->mlp_->bias, mlp[0],
-    mlp[1], mlp[2], mlp[3], mode == RunningMode::TRAIN ? app_emb_ : Tensor());
+    mlp[1], mlp[2], mlp[3], emb);
   return {sh.logit.unsqueeze(1), sh.rgb};
 }
 

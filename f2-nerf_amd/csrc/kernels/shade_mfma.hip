@@ -189,6 +189,14 @@ __device__ __forceinline__ float dpp_move(float v)
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), kCtrl, 0xf, 0xf, false));
 }
 
+// i == 0 ? a : i == 1 ? b : i == 2 ? c : d, on values: written on array elements, that conditional is
+// an lvalue and becomes ONE load through a selected address, which keeps the array in scratch
+__device__ __forceinline__ float pick4(int i, float a, float b, float c, float d)
+{
+  const float lo = (i & 1) ? b : a, hi = (i & 1) ? d : c;
+  return (i & 2) ? hi : lo;
+}
+
 // sum over the 16 lanes of a quarter (a DPP row), result in every lane of the quarter
 __device__ __forceinline__ float quarter_sum(float v)
 {
@@ -199,8 +207,22 @@ __device__ __forceinline__ float quarter_sum(float v)
   return v;
 }
 
-template <int C, int V, bool WIDE, int TS>
-__global__ __launch_bounds__((MShape<C, TS>::kWaves * 64)) void shade_bwd_mfma_kernel(
+// The body of both backward kernels.  RAYS = false: the per-sample form, `sample_img` holds one image
+// id per sample.  RAYS = true: the ray-uniform form for a dense [n_rays, S] grid of samples with
+// S % 64 == 0 (n = n_rays * S), where every stride lies inside one ray: `sample_img` holds one image
+// id per RAY, and the direction, SH16(dir), the embedding row and the SH half of the hidden layer
+// c = b1 + w1[:, 16:32] . SH(dir) are wave-uniform inside a stride.  Per stride it then
+//   - loads the direction and the image id once, through wave-uniform addresses, and evaluates
+//     sh_basis once (no SH rows in the LDS tile, no per-sample dirs / image ids);
+//   - forms c with 16 products for ONE sample tile -- every column of the result is the same --
+//     and starts the accumulators of all TS sample tiles from it (16 TS products less);
+//   - adds the SH half of d w1 as ONE product per neuron tile: d w1[j][16+i] = sh[i] sum_s d_pre[j][s],
+//     and that sum is this stride's increment of acc_b1 (4 products instead of 16 TS).
+// The head layer is untouched (logit and d_h are the per-sample form's terms in the same order); pre,
+// d_enc and the parameter gradients are the same f32 terms added in another order (the SH part first
+// instead of last, d w1[:, 16:] summed per stride before the product).
+template <int C, int V, bool WIDE, int TS, bool RAYS>
+__device__ __forceinline__ void shade_bwd_mfma_body(
   const float * __restrict__ enc, const float * __restrict__ dirs,
   const int32_t * __restrict__ sample_img, const float * __restrict__ p_w_h,
   const float * __restrict__ p_b_h, const float * __restrict__ p_w1,
@@ -209,7 +231,7 @@ __global__ __launch_bounds__((MShape<C, TS>::kWaves * 64)) void shade_bwd_mfma_k
   const float * __restrict__ d_logit, const float * __restrict__ d_rgb, float * __restrict__ d_enc,
   float * __restrict__ g_w_h, float * __restrict__ g_b_h, float * __restrict__ g_w1,
   float * __restrict__ g_b1, float * __restrict__ g_w2, float * __restrict__ g_b2,
-  float * __restrict__ g_emb, int64_t n)
+  float * __restrict__ g_emb, int64_t n, int n_per_ray)
 {
   using S = MShape<C, TS>;
   constexpr int kS1 = S::kS1, kM6 = S::kM6, kP = S::kP, kStride = S::kStride;
@@ -245,7 +267,9 @@ __global__ __launch_bounds__((MShape<C, TS>::kWaves * 64)) void shade_bwd_mfma_k
   if (threadIdx.x < 4) lds_w[S::oB2 + threadIdx.x] = (threadIdx.x < 3) ? p_b2[threadIdx.x] : 0.f;
 
   const int lane = lane_id();
-  const int wave = (int)(threadIdx.x >> 6);
+  // RAYS: the wave index in a scalar register, so that the stride's ray, its direction and its
+  // image id are scalar loads
+  const int wave = RAYS ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6);
   const int q = lane >> 4, m = lane & 15;
   float * tile = lds_all + S::kWFloats + wave * S::kWaveFloats;
   float * XS = tile + S::oXS;
@@ -330,6 +354,21 @@ __global__ __launch_bounds__((MShape<C, TS>::kWaves * 64)) void shade_bwd_mfma_k
   const int lS = lane % kStride;
   auto load_inputs = [&](int64_t st_, float (&eB_)[kS1][TS], int (&img_)[TS], float (&dir_)[3]) {
     const int64_t s0_ = st_ * kStride;  // may lie beyond the end: every index is clamped to a real sample
+    if constexpr (RAYS) {  // every stride is whole (n % 64 == 0) and lies in one ray
+      const uint32_t sc = (uint32_t)((s0_ < n) ? s0_ : n - kStride);
+#pragma unroll
+      for (int t = 0; t < kS1; t++)
+#pragma unroll
+        for (int T = 0; T < TS; T++) eB_[t][T] = ld_row(enc + (int64_t)t * n, (sc + 16 * T + m) * 4 + cE);
+      if (has_emb) {
+        const int id = sample_img[sc / (uint32_t)n_per_ray];
+#pragma unroll
+        for (int T = 0; T < TS; T++) img_[T] = id;
+      }
+#pragma unroll
+      for (int k = 0; k < 3; k++) dir_[k] = dirs[(int64_t)sc * 3 + k];
+      return;
+    }
     uint32_t off_[TS];
 #pragma unroll
     for (int T = 0; T < TS; T++) off_[T] = (uint32_t)(((s0_ + 16 * T + m < n) ? s0_ + 16 * T + m : n - 1) * 4);
@@ -363,7 +402,7 @@ __global__ __launch_bounds__((MShape<C, TS>::kWaves * 64)) void shade_bwd_mfma_k
 #pragma unroll
     for (int T = 0; T < TS; T++) {
       const int64_t s = s0 + 16 * T + m;
-      vT[T] = s < n;
+      vT[T] = RAYS || s < n;
       offS[T] = (uint32_t)((vT[T] ? s : n - 1) * 4);
     }
 
@@ -389,18 +428,28 @@ __global__ __launch_bounds__((MShape<C, TS>::kWaves * 64)) void shade_bwd_mfma_k
     int img_cur[TS];
 #pragma unroll
     for (int T = 0; T < TS; T++) img_cur[T] = img[T];
+    float shq[4], shm = 0.f;  // RAYS: SH rows 4q+t' (the recompute's B operand) and row m (d w1's)
     {
       f32x4 e4[TS];
       if (has_emb) {
 #pragma unroll
         for (int T = 0; T < TS; T++)
-          e4[T] = *reinterpret_cast<const f32x4 *>(p_emb + (int64_t)img_cur[T] * kOut1 + 4 * q);
+          if (!RAYS || T == 0)
+            e4[T] = *reinterpret_cast<const f32x4 *>(p_emb + (int64_t)img_cur[T] * kOut1 + 4 * q);
       }
       // SH: lane l evaluates sample s0 + l % kStride and writes its column of the S-layout tile
       // directly (at TS = 2 the lower half of the wave rows 16..23, the upper half rows 24..31)
+      // RAYS: one direction per stride, every lane evaluates it and keeps the rows it supplies
       float sh[16];
       sh_basis<4>(dir[0], dir[1], dir[2], sh);
-      if constexpr (TS == 4) {
+      if constexpr (RAYS) {
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+          shq[t] = pick4(q, sh[t], sh[4 + t], sh[8 + t], sh[12 + t]);
+        shm = pick4(
+          m >> 2, pick4(m & 3, sh[0], sh[1], sh[2], sh[3]), pick4(m & 3, sh[4], sh[5], sh[6], sh[7]),
+          pick4(m & 3, sh[8], sh[9], sh[10], sh[11]), pick4(m & 3, sh[12], sh[13], sh[14], sh[15]));
+      } else if constexpr (TS == 4) {
 #pragma unroll
         for (int k = 0; k < 16; k++) XS[(16 + k) * kP + lane] = sh[k];
       } else {
@@ -412,17 +461,37 @@ __global__ __launch_bounds__((MShape<C, TS>::kWaves * 64)) void shade_bwd_mfma_k
       for (int T = 0; T < TS; T++) {
         Xh[T] = h[T];
         if (q == 0) Xh[T][0] = 1.f;
-        if (has_emb) Xh[T] += e4[T];
+        if (has_emb) Xh[T] += e4[RAYS ? 0 : T];
 #pragma unroll
         for (int r = 0; r < 4; r++) XS[(4 * q + r) * kP + 16 * T + m] = Xh[T][r];
       }
     }
-    wave_lds_sync();
+    if constexpr (!RAYS) wave_lds_sync();  // RAYS: XS is read in the d w1 phase only, behind two syncs
 
     phase_fence_v<V>();
     // ---- hidden layer: pre[16M+4q+r][s] = w1 . X + b1
     f32x4 pre[4][TS];
-    {
+    if constexpr (RAYS) {
+      // the SH half once for one sample tile (four independent chains), then the shading features
+#pragma unroll
+      for (int M = 0; M < 4; M++)
+        pre[M][0] = *reinterpret_cast<const f32x4 *>(lds_w + S::oB1 + 16 * M + 4 * q);
+#pragma unroll
+      for (int t = 4; t < 8; t++)
+#pragma unroll
+        for (int M = 0; M < 4; M++) pre[M][0] = mfma16(W(S::oWA2 + M * 8 + t), shq[t - 4], pre[M][0]);
+#pragma unroll
+      for (int M = 0; M < 4; M++) {
+#pragma unroll
+        for (int T = 1; T < TS; T++) pre[M][T] = pre[M][0];
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+          const float a = W(S::oWA2 + M * 8 + t);
+#pragma unroll
+          for (int T = 0; T < TS; T++) pre[M][T] = mfma16(a, Xh[T][t], pre[M][T]);
+        }
+      }
+    } else {
       float Xs[4][TS];  // SH rows 16+4q+t' of this lane's samples
 #pragma unroll
       for (int t = 0; t < 4; t++)
@@ -593,17 +662,26 @@ __global__ __launch_bounds__((MShape<C, TS>::kWaves * 64)) void shade_bwd_mfma_k
           put(M + 1);
           wave_lds_sync();
         }
+        constexpr int kN = RAYS ? 1 : 2;  // RAYS: the SH half is one product per neuron tile, below
+        float db = 0.f;                   // RAYS: this stride's increment of acc_b1[M]
 #pragma unroll
         for (int u = 0; u < TS; u++) {
-          acc_b1[M] += (a4[u][0] + a4[u][1]) + (a4[u][2] + a4[u][3]);
-          f32x4 b4[2];
+          const float su = (a4[u][0] + a4[u][1]) + (a4[u][2] + a4[u][3]);
+          if constexpr (RAYS) db += su;
+          else acc_b1[M] += su;
+          f32x4 b4[kN];
 #pragma unroll
-          for (int N = 0; N < 2; N++)
+          for (int N = 0; N < kN; N++)
             b4[N] = *reinterpret_cast<const f32x4 *>(XS + (16 * N + m) * kP + 16 * u + 4 * q);
 #pragma unroll
           for (int k = 0; k < 4; k++)
 #pragma unroll
-            for (int N = 0; N < 2; N++) acc_w1[M][N] = mfma16(a4[u][k], b4[N][k], acc_w1[M][N]);
+            for (int N = 0; N < kN; N++) acc_w1[M][N] = mfma16(a4[u][k], b4[N][k], acc_w1[M][N]);
+        }
+        if constexpr (RAYS) {
+          // lane (q, m): A[row m][k = q] = quarter q's part of d b1[16M+m], B[k = q][col m] = sh[m]
+          acc_b1[M] += db;
+          acc_w1[M][1] = mfma16(db, shm, acc_w1[M][1]);
         }
       }
     }
@@ -644,9 +722,11 @@ __global__ __launch_bounds__((MShape<C, TS>::kWaves * 64)) void shade_bwd_mfma_k
     if (has_emb) {
       const int img0 = __builtin_amdgcn_readfirstlane(img_cur[0]);
       bool one_img = true;
+      if constexpr (!RAYS) {
 #pragma unroll
-      for (int T = 0; T < TS; T++) one_img = one_img && img_cur[T] == img0;
-      if (__all(one_img)) {
+        for (int T = 0; T < TS; T++) one_img = one_img && img_cur[T] == img0;
+      }
+      if (RAYS || __all(one_img)) {
         if (img0 != emb_img) {
           flush_emb();
           emb_img = img0;
@@ -823,6 +903,37 @@ __global__ __launch_bounds__((MShape<C, TS>::kWaves * 64)) void shade_bwd_mfma_k
   }
 }
 
+#define F2N_SHADE_BWD_PARAMS(IMG)                                                                     \
+  const float * __restrict__ enc, const float * __restrict__ dirs, const int32_t * __restrict__ IMG,  \
+    const float * __restrict__ p_w_h, const float * __restrict__ p_b_h,                               \
+    const float * __restrict__ p_w1, const float * __restrict__ p_b1,                                 \
+    const float * __restrict__ p_w2, const float * __restrict__ p_b2,                                 \
+    const float * __restrict__ p_emb, const float * __restrict__ d_logit,                             \
+    const float * __restrict__ d_rgb, float * __restrict__ d_enc, float * __restrict__ g_w_h,         \
+    float * __restrict__ g_b_h, float * __restrict__ g_w1, float * __restrict__ g_b1,                 \
+    float * __restrict__ g_w2, float * __restrict__ g_b2, float * __restrict__ g_emb
+#define F2N_SHADE_BWD_ARGS(IMG)                                                                       \
+  enc, dirs, IMG, p_w_h, p_b_h, p_w1, p_b1, p_w2, p_b2, p_emb, d_logit, d_rgb, d_enc, g_w_h, g_b_h,    \
+    g_w1, g_b1, g_w2, g_b2, g_emb
+
+// per-sample form: any n, one image id per sample
+template <int C, int V, bool WIDE, int TS>
+__global__ __launch_bounds__((MShape<C, TS>::kWaves * 64)) void shade_bwd_mfma_kernel(
+  F2N_SHADE_BWD_PARAMS(sample_img), int64_t n)
+{
+  shade_bwd_mfma_body<C, V, WIDE, TS, false>(F2N_SHADE_BWD_ARGS(sample_img), n, 0);
+}
+
+// ray-uniform form: n = n_rays * S samples in ray-major order, S % 64 == 0, one image id per ray
+template <int C, int V, bool WIDE, int TS>
+__global__ __launch_bounds__((MShape<C, TS>::kWaves * 64)) void shade_bwd_mfma_rays_kernel(
+  F2N_SHADE_BWD_PARAMS(ray_img), int64_t n, int S)
+{
+  shade_bwd_mfma_body<C, V, WIDE, TS, true>(F2N_SHADE_BWD_ARGS(ray_img), n, S);
+}
+#undef F2N_SHADE_BWD_PARAMS
+#undef F2N_SHADE_BWD_ARGS
+
 
 // ---- forward on the matrix cores ------------------------------------------------------------------
 // The forward third of the kernel above (head, hidden and output layer in the Q-layout, no lane
@@ -847,18 +958,23 @@ struct FShape
   static constexpr int kLdsFloats = kWFloats + kWaves * kWaveFloats;
 };
 
-template <int C, bool WIDE, int W>
-__global__ __launch_bounds__(W * 64) void shade_fwd_mfma_kernel(
+//
+// RAYS (see shade_bwd_mfma_body): `sample_img` holds one image id per ray, the direction and the id
+// are loaded once per stride through wave-uniform addresses, sh_basis runs once, and the SH half of
+// the hidden layer is formed for one sample tile (16 products) and starts all four: 176 products
+// per stride instead of 224, no SH tile in LDS and none of its syncs.  No pre_out in that form.
+template <int C, bool WIDE, int W, bool RAYS>
+__device__ __forceinline__ void shade_fwd_mfma_body(
   const float * __restrict__ enc, const float * __restrict__ dirs,
   const int32_t * __restrict__ sample_img, const float * __restrict__ p_w_h,
   const float * __restrict__ p_b_h, const float * __restrict__ p_w1,
   const float * __restrict__ p_b1, const float * __restrict__ p_w2,
   const float * __restrict__ p_b2, const float * __restrict__ p_emb, float * __restrict__ logit,
-  float * __restrict__ rgb, float * __restrict__ pre_out, int64_t n)
+  float * __restrict__ rgb, float * __restrict__ pre_out, int64_t n, int n_per_ray)
 {
   using S = FShape<C, W>;
   constexpr int kS1 = S::kS1, kP = S::kP;
-  __shared__ __attribute__((aligned(16))) float lds_all[S::kLdsFloats];
+  __shared__ __attribute__((aligned(16))) float lds_all[RAYS ? S::kWFloats : S::kLdsFloats];
   float * lds_w = lds_all;
   for (int i = threadIdx.x; i < S::kSlots * 64; i += S::kWaves * 64) {
     const int slot = i >> 6, l = i & 63, q = l >> 4, m = l & 15;
@@ -880,9 +996,9 @@ __global__ __launch_bounds__(W * 64) void shade_fwd_mfma_kernel(
   __syncthreads();
 
   const int lane = lane_id();
-  const int wave = (int)(threadIdx.x >> 6);
+  const int wave = RAYS ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6);
   const int q = lane >> 4, m = lane & 15;
-  float * XS = lds_all + S::kWFloats + wave * S::kWaveFloats;  // SH rows 0..15 of this wave
+  float * XS = lds_all + (RAYS ? 0 : S::kWFloats + wave * S::kWaveFloats);  // SH rows 0..15 of this wave
   const float * wop = lds_w + lane;
   using Off = typename RowOffset<WIDE>::type;
   const Off cE = (Off)((int64_t)(q * kS1) * n * 4), cP = (Off)((int64_t)(4 * q) * n * 4);
@@ -898,7 +1014,7 @@ __global__ __launch_bounds__(W * 64) void shade_fwd_mfma_kernel(
 #pragma unroll
     for (int T = 0; T < 4; T++) {
       const int64_t s = s0 + 16 * T + m;
-      vT[T] = s < n;
+      vT[T] = RAYS || s < n;
       offS[T] = (uint32_t)((vT[T] ? s : n - 1) * 4);
     }
     float eB[kS1][4];
@@ -907,12 +1023,16 @@ __global__ __launch_bounds__(W * 64) void shade_fwd_mfma_kernel(
 #pragma unroll
       for (int T = 0; T < 4; T++) eB[t][T] = ld_row(enc + (int64_t)t * n, offS[T] + cE);
     int img[4] = {0, 0, 0, 0};
-    if (has_emb) {
-#pragma unroll
-      for (int T = 0; T < 4; T++) img[T] = ld_row(sample_img, offS[T]);
-    }
     float dir[3];
-    {
+    if constexpr (RAYS) {
+      if (has_emb) img[0] = sample_img[(uint32_t)s0 / (uint32_t)n_per_ray];
+#pragma unroll
+      for (int k = 0; k < 3; k++) dir[k] = dirs[s0 * 3 + k];
+    } else {
+      if (has_emb) {
+#pragma unroll
+        for (int T = 0; T < 4; T++) img[T] = ld_row(sample_img, offS[T]);
+      }
       const uint32_t offL = (uint32_t)(((s0 + lane < n) ? s0 + lane : n - 1) * 12);
 #pragma unroll
       for (int k = 0; k < 3; k++) dir[k] = ld_row(dirs + k, offL);
@@ -937,31 +1057,40 @@ __global__ __launch_bounds__(W * 64) void shade_fwd_mfma_kernel(
 
     // ---- shader input
     f32x4 Xh[4];
+    float Xs[4][4];  // SH rows 4q+t of this lane's samples; RAYS: Xs[t][0] alone, the stride's
     {
       f32x4 e4[4];
       if (has_emb) {
 #pragma unroll
         for (int T = 0; T < 4; T++)
-          e4[T] = *reinterpret_cast<const f32x4 *>(p_emb + (int64_t)img[T] * kOut1 + 4 * q);
+          if (!RAYS || T == 0)
+            e4[T] = *reinterpret_cast<const f32x4 *>(p_emb + (int64_t)img[T] * kOut1 + 4 * q);
       }
       float sh[16];
       sh_basis<4>(dir[0], dir[1], dir[2], sh);
+      if constexpr (RAYS) {
 #pragma unroll
-      for (int k = 0; k < 16; k++) XS[k * kP + lane] = sh[k];
+        for (int t = 0; t < 4; t++)
+          Xs[t][0] = pick4(q, sh[t], sh[4 + t], sh[8 + t], sh[12 + t]);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 16; k++) XS[k * kP + lane] = sh[k];
+      }
 #pragma unroll
       for (int T = 0; T < 4; T++) {
         Xh[T] = h[T];
         if (q == 0) Xh[T][0] = 1.f;
-        if (has_emb) Xh[T] += e4[T];
+        if (has_emb) Xh[T] += e4[RAYS ? 0 : T];
       }
     }
-    wave_lds_sync();
-    float Xs[4][4];
+    if constexpr (!RAYS) {
+      wave_lds_sync();
 #pragma unroll
-    for (int t = 0; t < 4; t++)
+      for (int t = 0; t < 4; t++)
 #pragma unroll
-      for (int T = 0; T < 4; T++) Xs[t][T] = XS[(4 * q + t) * kP + 16 * T + m];
-    wave_lds_sync();
+        for (int T = 0; T < 4; T++) Xs[t][T] = XS[(4 * q + t) * kP + 16 * T + m];
+      wave_lds_sync();
+    }
 
     // ---- hidden layer, then the output layer on rows 0, 4, 8
     f32x4 o[4];
@@ -973,17 +1102,32 @@ __global__ __launch_bounds__(W * 64) void shade_fwd_mfma_kernel(
 #pragma unroll
     for (int M = 0; M < 4; M++) {
       f32x4 pre[4];
+      if constexpr (RAYS) {
+        // c = b1 + w1[:, 16:32] . SH(dir) for one sample tile: the same in every column
+        f32x4 c = *reinterpret_cast<const f32x4 *>(lds_w + S::oB1 + 16 * M + 4 * q);
 #pragma unroll
-      for (int T = 0; T < 4; T++)
-        pre[T] = *reinterpret_cast<const f32x4 *>(lds_w + S::oB1 + 16 * M + 4 * q);
+        for (int t = 4; t < 8; t++) c = mfma16(wop[(S::oWA2 + M * 8 + t) * 64], Xs[t - 4][0], c);
 #pragma unroll
-      for (int t = 0; t < 8; t++) {
-        const float a = wop[(S::oWA2 + M * 8 + t) * 64];
+        for (int T = 0; T < 4; T++) pre[T] = c;
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+          const float a = wop[(S::oWA2 + M * 8 + t) * 64];
+#pragma unroll
+          for (int T = 0; T < 4; T++) pre[T] = mfma16(a, Xh[T][t], pre[T]);
+        }
+      } else {
 #pragma unroll
         for (int T = 0; T < 4; T++)
-          pre[T] = mfma16(a, (t < 4) ? Xh[T][t] : Xs[t - 4][T], pre[T]);
+          pre[T] = *reinterpret_cast<const f32x4 *>(lds_w + S::oB1 + 16 * M + 4 * q);
+#pragma unroll
+        for (int t = 0; t < 8; t++) {
+          const float a = wop[(S::oWA2 + M * 8 + t) * 64];
+#pragma unroll
+          for (int T = 0; T < 4; T++)
+            pre[T] = mfma16(a, (t < 4) ? Xh[T][t] : Xs[t - 4][T], pre[T]);
+        }
       }
-      if (pre_out) {
+      if (!RAYS && pre_out) {
 #pragma unroll
         for (int T = 0; T < 4; T++)
           if (vT[T]) {
@@ -1008,6 +1152,31 @@ __global__ __launch_bounds__(W * 64) void shade_fwd_mfma_kernel(
   }
 }
 
+#define F2N_SHADE_FWD_PARAMS(IMG)                                                                     \
+  const float * __restrict__ enc, const float * __restrict__ dirs, const int32_t * __restrict__ IMG,  \
+    const float * __restrict__ p_w_h, const float * __restrict__ p_b_h,                               \
+    const float * __restrict__ p_w1, const float * __restrict__ p_b1,                                 \
+    const float * __restrict__ p_w2, const float * __restrict__ p_b2,                                 \
+    const float * __restrict__ p_emb, float * __restrict__ logit, float * __restrict__ rgb
+
+template <int C, bool WIDE, int W>
+__global__ __launch_bounds__(W * 64) void shade_fwd_mfma_kernel(
+  F2N_SHADE_FWD_PARAMS(sample_img), float * __restrict__ pre_out, int64_t n)
+{
+  shade_fwd_mfma_body<C, WIDE, W, false>(
+    enc, dirs, sample_img, p_w_h, p_b_h, p_w1, p_b1, p_w2, p_b2, p_emb, logit, rgb, pre_out, n, 0);
+}
+
+// ray-uniform form: n = n_rays * S samples in ray-major order, S % 64 == 0, one image id per ray
+template <int C, bool WIDE, int W>
+__global__ __launch_bounds__(W * 64) void shade_fwd_mfma_rays_kernel(
+  F2N_SHADE_FWD_PARAMS(ray_img), int64_t n, int S)
+{
+  shade_fwd_mfma_body<C, WIDE, W, true>(
+    enc, dirs, ray_img, p_w_h, p_b_h, p_w1, p_b1, p_w2, p_b2, p_emb, logit, rgb, nullptr, n, S);
+}
+#undef F2N_SHADE_FWD_PARAMS
+
 }  // namespace
 
 namespace f2n_detail
@@ -1024,12 +1193,14 @@ bool shade_bwd_mfma_supports(int C, int64_t n)
   return (C == 8 || C == 16 || C == 32 || C == 64) && n < ((int64_t)1 << 28);
 }
 
-int launch_shade_bwd_mfma(
-  const float * enc_cm, int C, const float * dirs, const int32_t * sample_img, const float * w_h,
+// S = 0: the per-sample kernels (img = one id per sample); S > 0: the ray-uniform kernels
+// (img = one id per ray, n = n_rays * S).  The same choice of form (TS, fences, WIDE) for both.
+static int launch_shade_bwd_mfma_any(
+  const float * enc_cm, int C, const float * dirs, const int32_t * img, const float * w_h,
   const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
   const float * app_emb, const float * d_logit, const float * d_rgb, float * d_enc_cm,
   float * g_w_h, float * g_b_h, float * g_w1, float * g_b1, float * g_w2, float * g_b2,
-  float * g_app_emb, int64_t n, hipStream_t stream)
+  float * g_app_emb, int64_t n, int S, hipStream_t stream)
 {
   // the embedding rows are read as float4
   if (app_emb && (reinterpret_cast<uintptr_t>(app_emb) & 15u)) return F2N_E_INVALID_ARG;
@@ -1037,7 +1208,11 @@ int launch_shade_bwd_mfma(
   const bool wide = (int64_t)C * n >= ((int64_t)1 << 30);   // row offsets beyond 32 bits
   // form: 0 by size, 1 one wave per SIMD, 2 / 3 two waves (phase-fenced / phases mixed)
   const int waves = f2n_get_option(F2N_OPT_SHADE_BWD_WAVES);
-  const int ts = (waves == 1 || (waves == 0 && n < kShadeBwdTwoWavesMinSamples)) ? 4 : 2;
+  // (the ray-uniform form at C = 64 with 64-bit row offsets, 2^24 samples and more, spills four
+  // registers at two waves per SIMD: those launches take its one-wave form, which does not)
+  const bool rays_one_wave = S > 0 && wide && C == 64;
+  const int ts =
+    (waves == 1 || (waves == 0 && n < kShadeBwdTwoWavesMinSamples) || rays_one_wave) ? 4 : 2;
   // scheduling (V & 1: phases may mix).  One wave: mixed unless F2N_OPT_SHADE_VARIANT = 1, as in
   // round 3.  Two waves: fenced (1.30 against 1.33 ms per 8.2 M samples) unless SHADE_BWD_WAVES = 3;
   // the WIDE kernels are always fenced there (mixed, they spill).
@@ -1047,10 +1222,17 @@ int launch_shade_bwd_mfma(
     using MS = MShape<CC, TT>;                                                                       \
     const int64_t n_strides = (n + MS::kStride - 1) / MS::kStride;                                   \
     const unsigned grid = (unsigned)std::min<int64_t>(256, (n_strides + MS::kWaves - 1) / MS::kWaves); \
-    hipLaunchKernelGGL(                                                                              \
-      (shade_bwd_mfma_kernel<CC, VV, WW, TT>), dim3(grid), dim3(MS::kWaves * 64), 0, stream, enc_cm, \
-      dirs, sample_img, w_h, b_h, w1, b1, w2, b2, app_emb, d_logit, d_rgb, d_enc_cm, g_w_h, g_b_h,   \
-      g_w1, g_b1, g_w2, g_b2, g_app_emb, n);                                                         \
+    if (S > 0) {                                                                                     \
+      if constexpr (!(CC == 64 && WW && TT == 2)) /* rays_one_wave */                                \
+        hipLaunchKernelGGL(                                                                          \
+          (shade_bwd_mfma_rays_kernel<CC, VV, WW, TT>), dim3(grid), dim3(MS::kWaves * 64), 0,        \
+          stream, enc_cm, dirs, img, w_h, b_h, w1, b1, w2, b2, app_emb, d_logit, d_rgb, d_enc_cm,    \
+          g_w_h, g_b_h, g_w1, g_b1, g_w2, g_b2, g_app_emb, n, S);                                    \
+    } else                                                                                           \
+      hipLaunchKernelGGL(                                                                            \
+        (shade_bwd_mfma_kernel<CC, VV, WW, TT>), dim3(grid), dim3(MS::kWaves * 64), 0, stream,       \
+        enc_cm, dirs, img, w_h, b_h, w1, b1, w2, b2, app_emb, d_logit, d_rgb, d_enc_cm, g_w_h,       \
+        g_b_h, g_w1, g_b1, g_w2, g_b2, g_app_emb, n);                                                \
   }
 #define F2N_LAUNCH_MFMA_T(CC, TT)                            \
   if (wide) F2N_LAUNCH_MFMA_V(CC, (TT == 2 ? 0 : 1), true, TT) \
@@ -1072,11 +1254,38 @@ int launch_shade_bwd_mfma(
   return f2n_launch_status();
 }
 
-
-int launch_shade_fwd_mfma(
+int launch_shade_bwd_mfma(
   const float * enc_cm, int C, const float * dirs, const int32_t * sample_img, const float * w_h,
   const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
-  const float * app_emb, float * logit, float * rgb, float * pre_cm, int64_t n, hipStream_t stream)
+  const float * app_emb, const float * d_logit, const float * d_rgb, float * d_enc_cm,
+  float * g_w_h, float * g_b_h, float * g_w1, float * g_b1, float * g_w2, float * g_b2,
+  float * g_app_emb, int64_t n, hipStream_t stream)
+{
+  return launch_shade_bwd_mfma_any(
+    enc_cm, C, dirs, sample_img, w_h, b_h, w1, b1, w2, b2, app_emb, d_logit, d_rgb, d_enc_cm, g_w_h,
+    g_b_h, g_w1, g_b1, g_w2, g_b2, g_app_emb, n, 0, stream);
+}
+
+int launch_shade_bwd_mfma_rays(
+  const float * enc_cm, int C, const float * dirs, const int32_t * ray_img, const float * w_h,
+  const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
+  const float * app_emb, const float * d_logit, const float * d_rgb, float * d_enc_cm,
+  float * g_w_h, float * g_b_h, float * g_w1, float * g_b1, float * g_w2, float * g_b2,
+  float * g_app_emb, int n_rays, int S, hipStream_t stream)
+{
+  if (S <= 0 || S % 64 != 0 || n_rays <= 0) return F2N_E_INVALID_ARG;
+  return launch_shade_bwd_mfma_any(
+    enc_cm, C, dirs, ray_img, w_h, b_h, w1, b1, w2, b2, app_emb, d_logit, d_rgb, d_enc_cm, g_w_h,
+    g_b_h, g_w1, g_b1, g_w2, g_b2, g_app_emb, (int64_t)n_rays * S, S, stream);
+}
+
+
+// S = 0: the per-sample kernels; S > 0: the ray-uniform kernels (img per ray, no pre_cm)
+static int launch_shade_fwd_mfma_any(
+  const float * enc_cm, int C, const float * dirs, const int32_t * img, const float * w_h,
+  const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
+  const float * app_emb, float * logit, float * rgb, float * pre_cm, int64_t n, int S,
+  hipStream_t stream)
 {
   const int64_t n_strides = (n + 63) / 64;
   if (app_emb && (reinterpret_cast<uintptr_t>(app_emb) & 15u)) return F2N_E_INVALID_ARG;
@@ -1087,9 +1296,14 @@ int launch_shade_fwd_mfma(
   {                                                                                                \
     constexpr int kW = KW;                                                                         \
     const unsigned grid = (unsigned)std::min<int64_t>(256, (n_strides + kW - 1) / kW);             \
-    hipLaunchKernelGGL(                                                                            \
-      (shade_fwd_mfma_kernel<CC, WW, KW>), dim3(grid), dim3(kW * 64), 0, stream, enc_cm, dirs,     \
-      sample_img, w_h, b_h, w1, b1, w2, b2, app_emb, logit, rgb, pre_cm, n);                       \
+    if (S > 0)                                                                                     \
+      hipLaunchKernelGGL(                                                                          \
+        (shade_fwd_mfma_rays_kernel<CC, WW, KW>), dim3(grid), dim3(kW * 64), 0, stream, enc_cm,    \
+        dirs, img, w_h, b_h, w1, b1, w2, b2, app_emb, logit, rgb, n, S);                           \
+    else                                                                                           \
+      hipLaunchKernelGGL(                                                                          \
+        (shade_fwd_mfma_kernel<CC, WW, KW>), dim3(grid), dim3(kW * 64), 0, stream, enc_cm, dirs,   \
+        img, w_h, b_h, w1, b1, w2, b2, app_emb, logit, rgb, pre_cm, n);                            \
   }
 #define F2N_LAUNCH_FWD(CC)                                                   \
   if (wide) F2N_LAUNCH_FWD_W(CC, true, 12)                                   \
@@ -1106,6 +1320,26 @@ int launch_shade_fwd_mfma(
 #undef F2N_LAUNCH_FWD
 #undef F2N_LAUNCH_FWD_W
   return f2n_launch_status();
+}
+
+int launch_shade_fwd_mfma(
+  const float * enc_cm, int C, const float * dirs, const int32_t * sample_img, const float * w_h,
+  const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
+  const float * app_emb, float * logit, float * rgb, float * pre_cm, int64_t n, hipStream_t stream)
+{
+  return launch_shade_fwd_mfma_any(
+    enc_cm, C, dirs, sample_img, w_h, b_h, w1, b1, w2, b2, app_emb, logit, rgb, pre_cm, n, 0, stream);
+}
+
+int launch_shade_fwd_mfma_rays(
+  const float * enc_cm, int C, const float * dirs, const int32_t * ray_img, const float * w_h,
+  const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
+  const float * app_emb, float * logit, float * rgb, int n_rays, int S, hipStream_t stream)
+{
+  if (S <= 0 || S % 64 != 0 || n_rays <= 0) return F2N_E_INVALID_ARG;
+  return launch_shade_fwd_mfma_any(
+    enc_cm, C, dirs, ray_img, w_h, b_h, w1, b1, w2, b2, app_emb, logit, rgb, nullptr,
+    (int64_t)n_rays * S, S, stream);
 }
 
 }  // namespace f2n_detail

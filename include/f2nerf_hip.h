@@ -75,7 +75,11 @@ const char * f2n_status_string(int status);
                                   stride mixed (not fenced; WIDE kernels stay fenced); same d_enc bit
                                   for bit, parameter gradients within the order of float sums       */
 #define F2N_SHADE_BWD_TWO_WAVES_MIN_SAMPLES (3 << 19)
-#define F2N_OPT_COUNT 11
+#define F2N_OPT_SHADE_RAYS 11   /* Renderer, fused per-sample network on a dense [n_rays, S] grid of
+                                  samples with S % 64 == 0: 0 the ray-uniform kernels
+                                  (f2n_shade_fwd_rays / f2n_shade_bwd_rays), 1 always the per-sample
+                                  kernels; same logit bit for bit, everything else within rounding    */
+#define F2N_OPT_COUNT 12
 int f2n_set_option(int key, int value);
 int f2n_get_option(int key);
 
@@ -460,6 +464,38 @@ int f2n_shade_bwd(
   const float * app_emb, const float * d_logit, const float * d_rgb, float * d_enc_cm,
   float * g_w_h, float * g_b_h, float * g_w1, float * g_b1, float * g_w2, float * g_b2,
   float * g_app_emb, const float * pre_cm, int64_t n, void * stream);
+
+/* The same network on a dense grid of samples: n = n_rays * S samples in ray-major order (the
+ * sampler's [n_rays, S] grid before compaction), S a multiple of 64, so that every 64-sample stride
+ * of the kernels lies inside one ray.  The reference lines are those of f2n_shade_fwd --
+ * src/hash_3d_anchored.cpp:86, src/renderer.cpp:93-104, src/sh_shader.cpp:24-28, src/sh_shader.cu:11-103.
+ * What is the same for every sample of a ray is done once per stride: the direction (read from
+ * dirs[3 * s0] of the stride's first sample: `dirs` stays the per-sample [n, 3] array and must hold
+ * the ray's direction in every sample of the ray), SH16(dir), the embedding row of ray_img[ray]
+ * ([n_rays] image id per ray, or NULL: no appearance embedding -- it replaces sample_img and the
+ * ScatterIdx launch, src/CustomOps/Scatter.cu:43-70) and the SH half of the hidden layer,
+ * b1 + w1[:, 16:32] . SH(dir).  Matrix-core kernels only: F2N_E_UNSUPPORTED for a C other than 8, 16,
+ * 32, 64 and for 2^28 samples or more; F2N_E_INVALID_ARG for S % 64 != 0 or a null pointer.
+ * Numerics: logit is bit-identical to f2n_shade_fwd's (the head layer is untouched); rgb agrees to
+ * rounding, not to the bit (the same f32 terms, the SH part of the hidden layer added first instead
+ * of last). */
+int f2n_shade_fwd_rays(
+  const float * enc_cm, int C, const float * dirs, const int32_t * ray_img, const float * w_h,
+  const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
+  const float * app_emb, float * logit, float * rgb, int n_rays, int S, void * stream);
+
+/* Backward of the above, with the contract of f2n_shade_bwd (d_enc_cm overwritten, the seven
+ * parameter gradients accumulated into) -- the autograd chain of the same reference lines and
+ * ScatterAddFuncBackwardBlock, src/CustomOps/Scatter.cu:21-41,72-101.  F2N_OPT_SHADE_BWD_WAVES and
+ * F2N_OPT_SHADE_VARIANT choose its form as they do for f2n_shade_bwd.  d_enc and the parameter
+ * gradients agree with f2n_shade_bwd's to rounding, not to the bit: the same f32 terms in another
+ * order (d w1[:, 16:32] is summed over the samples of a stride before it is multiplied by SH(dir)). */
+int f2n_shade_bwd_rays(
+  const float * enc_cm, int C, const float * dirs, const int32_t * ray_img, const float * w_h,
+  const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
+  const float * app_emb, const float * d_logit, const float * d_rgb, float * d_enc_cm,
+  float * g_w_h, float * g_b_h, float * g_w1, float * g_b1, float * g_w2, float * g_b2,
+  float * g_app_emb, int n_rays, int S, void * stream);
 
 /* ------------------------------------------------------------------ optimiser (section 8f) ----- */
 
