@@ -250,6 +250,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
       },
       py::arg("rays_o"), py::arg("rays_d"), py::arg("emb_idx") = py::none(),
       py::arg("mode") = "validate", py::arg("noise") = py::none(), py::arg("bg_color") = py::none())
+    .def(
+      "render_rays",
+      [](Renderer & r, const Tensor & o, const Tensor & d, const c10::optional<Tensor> & emb_idx,
+         const std::string & mode, const c10::optional<Tensor> & noise,
+         const c10::optional<Tensor> & bg) {
+        py::gil_scoped_release no_gil;
+        return r.render_rays(
+          o, d, opt_tensor(emb_idx), parse_mode(mode), opt_tensor(noise), opt_tensor(bg));
+      },
+      py::arg("rays_o"), py::arg("rays_d"), py::arg("emb_idx") = py::none(),
+      py::arg("mode") = "validate", py::arg("noise") = py::none(), py::arg("bg_color") = py::none(),
+      "the no-grad render as one kernel: (colors, depths, last_trans, kept); see Renderer::render_rays")
     .def("render_all_rays", &Renderer::render_all_rays, py::call_guard<py::gil_scoped_release>())
     .def("render_image", &Renderer::render_image, py::call_guard<py::gil_scoped_release>())
     .def(
@@ -292,6 +304,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def("set_fused_ray_grad", [](Renderer & r, bool f) { r.options_.fused_ray_grad = f; },
          "rays that require grad take the fused path: see RendererOptions::fused_ray_grad")
     .def("set_margin_min_samples", [](Renderer & r, int64_t n) { r.options_.margin_min_samples = n; })
+    .def("set_one_pass", &Renderer::set_one_pass,
+         "render_all_rays / render_image in one kernel per chunk: see RendererOptions::one_pass")
+    .def("one_pass_applies", &Renderer::one_pass_applies)
     .def("set_deferred_check", [](Renderer & r, bool f) { r.options_.deferred_check = f; },
          "no host read in render(): see RendererOptions::deferred_check")
     .def("deferred_check_ok", &Renderer::deferred_check_ok)
@@ -371,7 +386,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def_readwrite("noise_rotation_x", &LocalizerParam::noise_rotation_x)
     .def_readwrite("noise_rotation_y", &LocalizerParam::noise_rotation_y)
     .def_readwrite("noise_rotation_z", &LocalizerParam::noise_rotation_z)
-    .def_readwrite("resize_factor", &LocalizerParam::resize_factor);
+    .def_readwrite("resize_factor", &LocalizerParam::resize_factor)
+    .def_readwrite("one_pass", &LocalizerParam::one_pass);
 
   py::class_<Localizer, std::shared_ptr<Localizer>>(m, "Localizer")
     .def(py::init<const LocalizerParam &>(), py::arg("param"),

@@ -37,6 +37,9 @@ struct LocalizerParam
   float noise_rotation_y = 2.5f;
   float noise_rotation_z = 2.5f;
   int32_t resize_factor = 1;
+  // render particles and images with the one-kernel inference path (RendererOptions::one_pass); not
+  // part of inference_params.yaml
+  bool one_pass = false;
 };
 
 namespace f2n

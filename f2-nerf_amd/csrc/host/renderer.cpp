@@ -261,13 +261,19 @@ RenderResult Renderer::render(
   return res;
 }
 
+bool Renderer::fused_net_applies() const
+{
+  const auto & field = scene_field_->options_;
+  return options_.fused_shade && f2n::shade_supported(field.n_levels * field.n_channels) &&
+         field.mlp_out_dim == 16;
+}
+
 Renderer::Route Renderer::choose_route(
   const Tensor & rays_o, const Tensor & rays_d, const Tensor & bg_color) const
 {
   Route route;
   const auto & field = scene_field_->options_;
-  route.fused_net = options_.fused_shade && f2n::shade_supported(field.n_levels * field.n_channels) &&
-                    field.mlp_out_dim == 16;
+  route.fused_net = fused_net_applies();
   const bool rays_need_grad =
     torch::GradMode::is_enabled() && (rays_o.requires_grad() || rays_d.requires_grad());
   // the fused kernels work on detached copies; shade() hands the encoding's gradient back to these
@@ -713,12 +719,117 @@ RenderResult Renderer::composite(
   return {out.colors, out.depths, out.weights, kept.pts_idx_bounds};
 }
 
+// ---- one-pass inference render ---------------------------------------------------------------------
+
+bool Renderer::one_pass_applies() const
+{
+  if (!options_.one_pass || !fused_net_applies()) return false;
+  if (!torch::GradMode::is_enabled()) return true;
+  for (const auto & p : parameters())
+    if (p.requires_grad()) return false;
+  return true;
+}
+
+void Renderer::render_rays_into(
+  const Tensor & rays_o_raw, const Tensor & rays_d_raw, const Tensor & emb_idx_in, RunningMode mode,
+  const Tensor & noise_raw, const Tensor & bg_raw, Tensor colors, Tensor depths, Tensor last_trans,
+  Tensor kept)
+{
+  const Tensor rays_o = f2n::dev_f32(rays_o_raw.detach(), "rays_o");
+  const Tensor rays_d = f2n::dev_f32(rays_d_raw.detach(), "rays_d");
+  const Tensor noise = noise_raw.defined() ? f2n::dev_f32(noise_raw.detach(), "noise") : Tensor();
+  const Tensor bg = f2n::dev_f32(bg_raw.detach(), "bg_color");
+  const int n_rays = (int)rays_o.size(0);
+  const int S = pts_sampler_->options_.max_samples;
+  TORCH_CHECK(rays_o.numel() == (int64_t)n_rays * 3 && rays_d.numel() == (int64_t)n_rays * 3, "rays shape");
+  TORCH_CHECK(!noise.defined() || noise.numel() == (int64_t)n_rays * S, "noise shape");
+  TORCH_CHECK(bg.numel() == (int64_t)n_rays * 3, "bg_color shape");
+  const bool train = mode == RunningMode::TRAIN;
+  TORCH_CHECK(!train || emb_idx_in.defined(), "TRAIN mode needs emb_idx");
+  const Tensor emb_idx = train ? f2n::dev_i32(emb_idx_in, "emb_idx") : Tensor();
+  TORCH_CHECK(!emb_idx.defined() || emb_idx.numel() == n_rays, "emb_idx shape");
+  TORCH_CHECK(
+    colors.is_contiguous() && depths.is_contiguous() && last_trans.is_contiguous() &&
+      kept.is_contiguous() && colors.numel() == (int64_t)n_rays * 3 && depths.numel() == n_rays &&
+      last_trans.numel() == n_rays && kept.numel() == n_rays,
+    "render_rays outputs");
+  if (n_rays == 0) return;
+  if (occupancy_)
+    TORCH_CHECK(
+      occupancy_->words().device() == rays_o.device(), "the occupancy grid lives on another device");
+  Hash3DAnchored & field = *scene_field_;
+  const Tensor table16 = field.table_f16();
+  const Tensor w_h = f2n::dev_f32(field.mlp_->weight.detach(), "field head weight");
+  const Tensor b_h = f2n::dev_f32(field.mlp_->bias.detach(), "field head bias");
+  auto mlp = shader_->mlp_params();
+  const Tensor w1 = f2n::dev_f32(mlp[0].detach(), "shader w1"), b1 = f2n::dev_f32(mlp[1].detach(), "shader b1");
+  const Tensor w2 = f2n::dev_f32(mlp[2].detach(), "shader w2"), b2 = f2n::dev_f32(mlp[3].detach(), "shader b2");
+  const Tensor emb = train ? f2n::dev_f32(app_emb_.detach(), "app_emb") : Tensor();
+  void * stream = f2n::current_stream(rays_o);
+  f2n::ScopedKernelTimer timer("render_rays", stream, (double)n_rays);
+  f2n::check(
+    f2n_render_rays(
+      rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), f2n::fptr(noise),
+      reinterpret_cast<const uint16_t *>(table16.data_ptr()), field.prim_pool_.data_ptr<int32_t>(),
+      field.bias_pool_.data_ptr<float>(), field.level_mul_.data_ptr<float>(), w_h.data_ptr<float>(),
+      b_h.data_ptr<float>(), w1.data_ptr<float>(), b1.data_ptr<float>(), w2.data_ptr<float>(),
+      b2.data_ptr<float>(), f2n::fptr(emb), f2n::iptr(emb_idx),
+      occupancy_ ? occupancy_->words_ptr() : nullptr, occupancy_ ? (int)occupancy_->resolution() : 0,
+      bg.data_ptr<float>(), colors.data_ptr<float>(), depths.data_ptr<float>(),
+      last_trans.data_ptr<float>(), kept.data_ptr<int32_t>(), nullptr, n_rays, S,
+      pts_sampler_->options_.step, (int)field.options_.n_levels, (int)field.options_.n_channels,
+      (uint32_t)field.local_size_, field.level_stride_, options_.early_stop_trans, 3.f, 1e-2f, stream),
+    "f2n_render_rays");
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> Renderer::render_rays(
+  const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
+  const Tensor & noise_in, const Tensor & bg_in)
+{
+  torch::NoGradGuard no_grad;
+  TORCH_CHECK(
+    fused_net_applies(),
+    "render_rays needs the fused per-sample network: n_levels * n_channels in {8, 16, 32, 64}, a "
+    "16-wide field head and fused_shade");
+  const int64_t n_rays = rays_o.size(0);
+  const auto fopt = f2n::float_on(rays_o.device());
+  Tensor noise = noise_in.defined() ? noise_in
+                                    : pts_sampler_->draw_noise(n_rays, mode, rays_o.device());
+  Tensor bg_color = bg_in.defined() ? bg_in
+                    : (mode == RunningMode::TRAIN) ? torch::rand({n_rays, 3}, fopt)
+                                                   : torch::ones({n_rays, 3}, fopt) * .5f;
+  Tensor colors = torch::empty({n_rays, 3}, fopt), depths = torch::empty({n_rays}, fopt);
+  Tensor last_trans = torch::empty({n_rays}, fopt);
+  Tensor kept = torch::empty({n_rays}, f2n::int_on(rays_o.device()));
+  render_rays_into(rays_o, rays_d, emb_idx, mode, noise, bg_color, colors, depths, last_trans, kept);
+  return {colors, depths, last_trans, kept};
+}
+
 // ---- whole-image helpers -------------------------------------------------------------------------
 
 std::tuple<Tensor, Tensor> Renderer::render_all_rays(
   const Tensor & rays_o, const Tensor & rays_d, const int batch_size)
 {
   const int64_t n_rays = rays_d.size(0);
+  const bool rays_need_grad =
+    torch::GradMode::is_enabled() && (rays_o.requires_grad() || rays_d.requires_grad());
+  if (one_pass_applies() && !rays_need_grad && rays_d.is_cuda() && batch_size > 0) {
+    // one launch per chunk, each into its rows of one output: nothing to concatenate
+    torch::NoGradGuard no_grad;
+    const auto fopt = f2n::float_on(rays_d.device());
+    Tensor colors = torch::empty({n_rays, 3}, fopt), depths = torch::empty({n_rays, 1}, fopt);
+    Tensor last_trans = torch::empty({n_rays}, fopt);
+    Tensor kept = torch::empty({n_rays}, f2n::int_on(rays_d.device()));
+    const Tensor bg = torch::ones({std::min<int64_t>(batch_size, n_rays), 3}, fopt) * .5f;
+    for (int64_t lo = 0; lo < n_rays; lo += batch_size) {
+      const int64_t hi = std::min<int64_t>(lo + batch_size, n_rays);
+      render_rays_into(
+        rays_o.slice(0, lo, hi), rays_d.slice(0, lo, hi), Tensor(), RunningMode::VALIDATE, Tensor(),
+        bg.slice(0, 0, hi - lo), colors.slice(0, lo, hi), depths.slice(0, lo, hi),
+        last_trans.slice(0, lo, hi), kept.slice(0, lo, hi));
+    }
+    return {colors, depths};
+  }
   std::vector<Tensor> colors, depths;
   for (int64_t lo = 0; lo < n_rays; lo += batch_size) {
     const int64_t hi = std::min<int64_t>(lo + batch_size, n_rays);

@@ -112,6 +112,11 @@ struct RendererOptions
   // the table, MLP and embedding gradients take exactly the kernels they take without it.  Off: such
   // rays go op by op.  The bucketed dense route is not used for them.
   bool fused_ray_grad = false;
+  // Inference in one kernel (f2n_render_rays): render_all_rays / render_image take it when the fused
+  // per-sample network applies and nothing can ask for a gradient (Renderer::one_pass_applies);
+  // otherwise they do exactly what they do without it.  render() and train_step never take it: it
+  // produces no per-sample weights and no gradients.
+  bool one_pass = false;
 };
 
 class Renderer : public torch::nn::Module
@@ -129,6 +134,22 @@ public:
   RenderResult render(
     const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
     const Tensor & noise, const Tensor & bg_color);
+
+  // The no-grad render as one kernel launch (f2n_render_rays): colours [n, 3], depths [n], last_trans
+  // [n] (1 - opacity of the ray: an alpha mask) and kept [n] int32 (samples composited per ray).
+  // mode, noise and bg_color as in render(); the attached occupancy grid is used.  Requires the fused
+  // per-sample network (L*F in {8,16,32,64}, a 16-wide field head, fused_shade).  Nothing is read
+  // back to the host and nothing per-sample is allocated, so the call can be captured in a hipGraph;
+  // last_n_samples_ / last_kept_fraction_ (the adaptive route of render()) are left alone.
+  std::tuple<Tensor, Tensor, Tensor, Tensor> render_rays(
+    const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
+    const Tensor & noise = Tensor(), const Tensor & bg_color = Tensor());
+
+  void set_one_pass(bool on) { options_.one_pass = on; }
+  // does render_all_rays / render_image take the one-kernel path right now?  (options_.one_pass, the
+  // fused network applies, and grad mode is off or no parameter requires grad; rays that themselves
+  // require grad under grad mode keep the default routes whatever this says)
+  bool one_pass_applies() const;
 
   std::tuple<Tensor, Tensor> render_all_rays(
     const Tensor & rays_o, const Tensor & rays_d, const int batch_size);
@@ -179,6 +200,12 @@ private:
   };
 
   Route choose_route(const Tensor & rays_o, const Tensor & rays_d, const Tensor & bg_color) const;
+  bool fused_net_applies() const;
+  // one f2n_render_rays launch into preallocated outputs (rows of one chunk)
+  void render_rays_into(
+    const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
+    const Tensor & noise, const Tensor & bg_color, Tensor colors, Tensor depths, Tensor last_trans,
+    Tensor kept);
 
   // The routes.  render_fused: detached rays, then march / dense / dense bucketed.
   RenderResult render_op_by_op(

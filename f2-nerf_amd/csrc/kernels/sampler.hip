@@ -12,79 +12,10 @@
 // stops issuing strides, so a terminated ray costs ceil(kept/64) strides, not S/64.
 #include "hash_grid.hiph"
 #include "occupancy.hiph"
+#include "sampler.hiph"
 
 namespace
 {
-
-struct RayFrame
-{
-  float ox, oy, oz;
-  float dx, dy, dz;  // unit direction
-};
-
-// rays_d / linalg_norm(rays_d, 2, -1, true)  (points_sampler.cpp:24)
-__device__ __forceinline__ RayFrame load_ray(
-  const float * __restrict__ rays_o, const float * __restrict__ rays_d, int r)
-{
-  RayFrame rf;
-  rf.ox = rays_o[3 * r];
-  rf.oy = rays_o[3 * r + 1];
-  rf.oz = rays_o[3 * r + 2];
-  const float x = rays_d[3 * r], y = rays_d[3 * r + 1], z = rays_d[3 * r + 2];
-  const float nrm = sqrtf(fmaf(z, z, fmaf(y, y, x * x)));
-  rf.dx = x / nrm;
-  rf.dy = y / nrm;
-  rf.dz = z / nrm;
-  return rf;
-}
-
-struct StrideCarry
-{
-  float noise;       // cumulative noise up to the previous stride
-  float lx, ly, lz;  // last sample point of the previous stride
-};
-
-struct StrideSample
-{
-  float t, px, py, pz, dt;
-  bool valid;
-};
-
-// Samples k0 .. k0+63 of one ray (points_sampler.cpp:31-48):
-//   t_k = cumsum(noise)_k * step ; p_k = o + d*t_k (mul, then add -- two ATen ops, not fused) ;
-//   dt_0 = 0, dt_k = |p_k - p_{k-1}|   (differences of points, quirk Q7)
-// The same function feeds f2n_sample_rays, f2n_density_march and f2n_sample_compact so that all
-// three see bit-identical samples.
-__device__ __forceinline__ StrideSample make_stride(
-  const RayFrame & rf, const float * __restrict__ noise_row, int k0, int S, float step,
-  StrideCarry & carry, int lane)
-{
-  StrideSample sm;
-  const int k = k0 + lane;
-  sm.valid = k < S;
-  float cum;
-  if (noise_row) {
-    const float nz = sm.valid ? noise_row[k] : 0.f;
-    cum = carry.noise + wave_incl_scan(nz);
-  } else {
-    cum = (float)(min(k, S - 1) + 1);  // cumsum of ones is exact
-  }
-  sm.t = cum * step;
-  const float mx = rf.dx * sm.t, my = rf.dy * sm.t, mz = rf.dz * sm.t;
-  sm.px = rf.ox + mx;
-  sm.py = rf.oy + my;
-  sm.pz = rf.oz + mz;
-  const float qx = wave_shift_up1(sm.px, carry.lx);
-  const float qy = wave_shift_up1(sm.py, carry.ly);
-  const float qz = wave_shift_up1(sm.pz, carry.lz);
-  const float ex = sm.px - qx, ey = sm.py - qy, ez = sm.pz - qz;
-  sm.dt = (k == 0) ? 0.f : sqrtf(fmaf(ez, ez, fmaf(ey, ey, ex * ex)));
-  carry.noise = wave_bcast_last(cum);
-  carry.lx = wave_bcast_last(sm.px);
-  carry.ly = wave_bcast_last(sm.py);
-  carry.lz = wave_bcast_last(sm.pz);
-  return sm;
-}
 
 __device__ __forceinline__ int ray_of_wave()
 {

@@ -47,6 +47,7 @@
 // is faster there.  The data-gradient chain per sample is unchanged:
 // d_enc is bit-identical to the TS = 4 form, the parameter gradients differ in the order of sums.
 #include "shade_mfma.hiph"
+#include "shade_fwd_mfma.hiph"
 
 #include "sh_basis.hiph"
 
@@ -54,18 +55,6 @@
 
 namespace
 {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c)
-{
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-constexpr int kOut1 = 16;   // field head width
-constexpr int kIn2 = 32;    // shader input = 16 shading features + 16 SH
-constexpr int kHid = 64;    // shader hidden width
-constexpr float kEps = 1e-3f;
 
 // TS = 16-sample column tiles per stride: 2 (the default, two waves per SIMD) or 4 (round 3, one).
 template <int C, int TS>
@@ -133,15 +122,6 @@ __device__ __forceinline__ void phase_fence_v()
   if constexpr (!(V & 1)) __builtin_amdgcn_sched_barrier(0);
 }
 
-__device__ __forceinline__ void wave_lds_sync()
-{
-  // one wavefront's LDS operations execute in order; this only stops the compiler from moving the
-  // transposed reads above the writes of other lanes
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // row[byte_off / 4] with a wave-uniform row pointer: global_load_dword v, v_off, s[row:row+1]
 // (Off = uint32_t: the saddr + 32-bit voffset form above; uint64_t, the WIDE kernels for C * n * 4 >=
 // 2^32: a 64-bit add per access and the vaddr form -- ~6 % slower, against the 2-3x of falling back
@@ -167,34 +147,12 @@ struct RowOffset<true>
   typedef uint64_t type;
 };
 
-// Pins global loads where they are written: without it the scheduler sinks them to their first use,
-// ~200 MFMAs later, and the wave then waits a full memory latency there.
-__device__ __forceinline__ void issue_fence() { __builtin_amdgcn_sched_barrier(0); }
-
-// max(x, 0) in one instruction: as integers, positive floats order like floats and every negative
-// float (and -0) is a negative integer.  fmaxf / v_med3 put a canonicalising v_max x, x in front.
-// (Not inline asm: the hazard recogniser does not see an asm's read of a register an MFMA is
-// still writing.)
-__device__ __forceinline__ float relu(float x)
-{
-  const int b = __float_as_int(x);
-  return __int_as_float(b > 0 ? b : 0);
-}
-
 // another lane's v by DPP: 0x140 row_mirror, lane 15 - m within each 16-lane row; 0x141
 // row_half_mirror, lane 7 - m within each 8; 0x4e quad_perm [2,3,0,1], lane m ^ 2
 template <int kCtrl>
 __device__ __forceinline__ float dpp_move(float v)
 {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), kCtrl, 0xf, 0xf, false));
-}
-
-// i == 0 ? a : i == 1 ? b : i == 2 ? c : d, on values: written on array elements, that conditional is
-// an lvalue and becomes ONE load through a selected address, which keeps the array in scratch
-__device__ __forceinline__ float pick4(int i, float a, float b, float c, float d)
-{
-  const float lo = (i & 1) ? b : a, hi = (i & 1) ? d : c;
-  return (i & 2) ? hi : lo;
 }
 
 // sum over the 16 lanes of a quarter (a DPP row), result in every lane of the quarter
@@ -944,20 +902,6 @@ __global__ __launch_bounds__((MShape<C, TS>::kWaves * 64)) void shade_bwd_mfma_r
 // samples inside the bench -- 52 products fewer but 200 vector instructions more and, at 168
 // registers, ten spilled; this kernel waits on latencies, not on the matrix pipe.  LDS: the three forward weight operands (56 slots at
 // C = 32) + a 16-row tile per wave that moves SH16(dir) from lane = sample into the Q-layout.
-template <int C, int W = 12>
-struct FShape
-{
-  static_assert(C % 8 == 0 && C <= 64, "MFMA path: C must be 8, 16, 32 or 64");
-  static constexpr int kS1 = C / 4;
-  static constexpr int oWA1 = 0, oWA2 = oWA1 + kS1, oWA3 = oWA2 + 32, kSlots = oWA3 + 16;
-  static constexpr int oBh = kSlots * 64, oB1 = oBh + 16, oB2 = oB1 + 64, kWFloats = oB2 + 4;
-  static constexpr int kP = 68;             // [16][kP] SH tile per wave (b32 accesses only)
-  static constexpr int kWaveFloats = 16 * kP;
-  static constexpr int kWaves = W;   // 16 = four per SIMD (the default: the allocator fits 128 registers
-                                     // without spilling; 0.552 -> 0.536 ms per 8.2 M samples), 12 = three, 8 = two
-  static constexpr int kLdsFloats = kWFloats + kWaves * kWaveFloats;
-};
-
 //
 // RAYS (see shade_bwd_mfma_body): `sample_img` holds one image id per ray, the direction and the id
 // are loaded once per stride through wave-uniform addresses, sh_basis runs once, and the SH half of
@@ -976,23 +920,7 @@ __device__ __forceinline__ void shade_fwd_mfma_body(
   constexpr int kS1 = S::kS1, kP = S::kP;
   __shared__ __attribute__((aligned(16))) float lds_all[RAYS ? S::kWFloats : S::kLdsFloats];
   float * lds_w = lds_all;
-  for (int i = threadIdx.x; i < S::kSlots * 64; i += S::kWaves * 64) {
-    const int slot = i >> 6, l = i & 63, q = l >> 4, m = l & 15;
-    float v;
-    if (slot < S::oWA2) {
-      v = p_w_h[m * C + q * kS1 + (slot - S::oWA1)];
-    } else if (slot < S::oWA3) {
-      const int M = (slot - S::oWA2) >> 3, t = (slot - S::oWA2) & 7;
-      v = p_w1[(16 * M + m) * kIn2 + ((t < 4) ? 4 * q + t : 16 + 4 * q + (t - 4))];
-    } else {
-      const int M = (slot - S::oWA3) >> 2, r = (slot - S::oWA3) & 3;
-      v = ((m & 3) == 0 && m < 12) ? p_w2[(m >> 2) * kHid + 16 * M + 4 * q + r] : 0.f;
-    }
-    lds_w[i] = v;
-  }
-  if (threadIdx.x < 16) lds_w[S::oBh + threadIdx.x] = p_b_h[threadIdx.x];
-  if (threadIdx.x < 64) lds_w[S::oB1 + threadIdx.x] = p_b1[threadIdx.x];
-  if (threadIdx.x < 4) lds_w[S::oB2 + threadIdx.x] = (threadIdx.x < 3) ? p_b2[threadIdx.x] : 0.f;
+  stage_fwd_weights<C, W>(lds_w, p_w_h, p_b_h, p_w1, p_b1, p_w2, p_b2);
   __syncthreads();
 
   const int lane = lane_id();

@@ -497,6 +497,43 @@ int f2n_shade_bwd_rays(
   float * g_w_h, float * g_b_h, float * g_w1, float * g_b1, float * g_w2, float * g_b2,
   float * g_app_emb, int n_rays, int S, void * stream);
 
+/* ------------------------------------------------------------------ one-pass inference render - */
+
+/* Renderer::render without gradients as ONE kernel, rays in and colours out -- src/renderer.cpp:33-123
+ * as used by render_all_rays (src/renderer.cpp:125-151), render_image (src/renderer.cpp:153-172) and
+ * Localizer::evaluate_poses (src/localizer.cpp:172): the sampler (src/points_sampler.cpp:20-64), the
+ * early-stop first pass (:58-90), the second field query, the shader (:92-105) and the compositing
+ * sums (:107-118).  One wavefront per ray in 64-sample strides; per stride the field is evaluated
+ * ONCE: its f16-rounded encoding feeds
+ *   the chain  logit_c = fma(enc_c, w_h[0][c], .) from b_h[0], in f2n_density_march's order -- it
+ *              decides which samples exist: kept (and len) are f2n_density_march's, or with a grid
+ *              f2n_density_march_occ's, bit for bit;
+ *   the network of f2n_shade_fwd_rays on the matrix cores (head Linear(C->16), embedding row of
+ *              ray_img[ray], SH16(dir), Linear(32->64), ReLU, Linear(64->3), sigmoid tail), whose
+ *              h[0] is the density logit that weights the kept samples, as in f2n_composite_fwd.
+ * Nothing per-sample is written: no compaction, no survivor count, O(n_rays) memory, no workspace, no
+ * atomics (two launches give the same bits); capturable in a hipGraph.
+ *   w_h [16,C], b_h [16], w1 [64,32], b1 [64], w2 [3,64], b2 [3]  row-major, as f2n_shade_fwd
+ *   app_emb [*,16] (16-byte aligned) with ray_img [n_rays], or both NULL: no appearance embedding
+ *   occ_bits [G^3/32] with G a power of two in 32..256, or NULL: no grid (G is then ignored); an
+ *            all-ones grid gives the bits of no grid
+ *   bg [n_rays,3];  outputs colors [n_rays,3], depths [n_rays], last_trans [n_rays] (1 - opacity),
+ *   kept [n_rays] (samples composited), len [n_rays] or NULL (the prefix length kept was thinned from)
+ * C = L*F in {8,16,32,64} with F in {1,2,4,8} and L <= 32, else F2N_E_UNSUPPORTED; any S >= 1 (the
+ * last stride is partial when S % 64 != 0).  No per-sample weights and no gradients: training and
+ * pose optimisation keep the routes above. */
+int f2n_render_rays(
+  const float * rays_o, const float * rays_d, const float * noise /* [n_rays,S] or NULL */,
+  const uint16_t * table, const int32_t * primes, const float * bias, const float * mul,
+  const float * w_h, const float * b_h, const float * w1, const float * b1,
+  const float * w2, const float * b2,
+  const float * app_emb, const int32_t * ray_img /* both NULL: no appearance embedding */,
+  const uint32_t * occ_bits /* NULL: no grid */, int G,
+  const float * bg, float * colors, float * depths, float * last_trans,
+  int32_t * kept, int32_t * len /* may be NULL */,
+  int n_rays, int S, float step, int L, int F, uint32_t T, int64_t level_stride,
+  float t_thresh, float density_shift, float t_shift, void * stream);
+
 /* ------------------------------------------------------------------ optimiser (section 8f) ----- */
 
 /* One fused pass of torch::optim::Adam::step() over one f32 parameter tensor -- the call at
