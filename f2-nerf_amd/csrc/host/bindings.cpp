@@ -98,22 +98,49 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
       auto o = f2n::composite(field_out, rgb, dt, t, idx, bg);
       return py::make_tuple(o.colors, o.depths, o.weights);
     });
-  m.def("get_rays_from_pose", [](const Tensor & pose, const Tensor & intr, const Tensor & ij) {
-    Rays r = get_rays_from_pose(pose, intr, ij);
-    return py::make_tuple(r.origins, r.dirs);
-  });
-  m.def("get_view_rays", [](const Tensor & pose, const Tensor & intr, int h, int w) {
-    Rays r = get_view_rays(pose, intr, h, w);
-    return py::make_tuple(r.origins, r.dirs);
-  });
+  // dist: optional (k1, k2, p1, p2) per camera, see rays.hpp; None = pinhole
+  m.def(
+    "get_rays_from_pose",
+    [](const Tensor & pose, const Tensor & intr, const Tensor & ij,
+       const c10::optional<Tensor> & dist) {
+      Rays r = get_rays_from_pose(pose, intr, ij, opt_tensor(dist));
+      return py::make_tuple(r.origins, r.dirs);
+    },
+    py::arg("pose"), py::arg("intrinsic"), py::arg("ij"), py::arg("dist") = py::none());
+  m.def(
+    "get_rays_from_poses",
+    [](const Tensor & poses, const Tensor & intr, const Tensor & ij,
+       const c10::optional<Tensor> & dist) {
+      Rays r = get_rays_from_poses(poses, intr, ij, opt_tensor(dist));
+      return py::make_tuple(r.origins, r.dirs);
+    },
+    py::arg("poses"), py::arg("intrinsic"), py::arg("ij"), py::arg("dist") = py::none());
+  m.def(
+    "get_view_rays",
+    [](const Tensor & pose, const Tensor & intr, int h, int w, const c10::optional<Tensor> & dist) {
+      Rays r = get_view_rays(pose, intr, h, w, opt_tensor(dist));
+      return py::make_tuple(r.origins, r.dirs);
+    },
+    py::arg("pose"), py::arg("intrinsic"), py::arg("h"), py::arg("w"),
+    py::arg("dist") = py::none());
   m.def(
     "sample_random_rays",
-    [](const Tensor & poses, const Tensor & intr, int h, int w, int64_t n, const Tensor & images) {
-      auto [r, gt, cam] = sample_random_rays(poses, intr, h, w, n, images);
+    [](const Tensor & poses, const Tensor & intr, int h, int w, int64_t n,
+       const c10::optional<Tensor> & images, const c10::optional<Tensor> & dist) {
+      auto [r, gt, cam] =
+        sample_random_rays(poses, intr, h, w, n, opt_tensor(images), opt_tensor(dist));
       return py::make_tuple(r.origins, r.dirs, gt, cam);
     },
     py::arg("poses"), py::arg("intrinsics"), py::arg("h"), py::arg("w"), py::arg("batch_size"),
-    py::arg("images") = Tensor());
+    py::arg("images") = py::none(), py::arg("dist") = py::none());
+  m.def(
+    "project_points",
+    [](const Tensor & points, const Tensor & pose, const Tensor & intr,
+       const c10::optional<Tensor> & dist) {
+      return project_points(points, pose, intr, opt_tensor(dist));
+    },
+    py::arg("points"), py::arg("pose"), py::arg("intrinsic"), py::arg("dist") = py::none(),
+    "f2n_project_points -> (pix [N,2] (row, col), valid [N] i32)");
   m.def("train_loss", &f2n::train_loss, py::arg("colors"), py::arg("gt_colors"), py::arg("var"),
         py::arg("var_loss_weight"));
   m.def("ray_order", &f2n::ray_order, "caller indices of rays_d sorted into pixel-compact bundles");
@@ -263,7 +290,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
       py::arg("mode") = "validate", py::arg("noise") = py::none(), py::arg("bg_color") = py::none(),
       "the no-grad render as one kernel: (colors, depths, last_trans, kept); see Renderer::render_rays")
     .def("render_all_rays", &Renderer::render_all_rays, py::call_guard<py::gil_scoped_release>())
-    .def("render_image", &Renderer::render_image, py::call_guard<py::gil_scoped_release>())
+    .def(
+      "render_image",
+      [](Renderer & r, const Tensor & pose, const Tensor & intr, int h, int w, int batch_size,
+         const c10::optional<Tensor> & dist) {
+        py::gil_scoped_release no_gil;
+        return r.render_image(pose, intr, h, w, batch_size, opt_tensor(dist));
+      },
+      py::arg("pose"), py::arg("intrinsic"), py::arg("h"), py::arg("w"), py::arg("batch_size"),
+      py::arg("dist") = py::none())
     .def(
       "train_step",
       [](Renderer & r, const Tensor & o, const Tensor & d, const Tensor & emb_idx, const Tensor & gt,
@@ -387,7 +422,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def_readwrite("noise_rotation_y", &LocalizerParam::noise_rotation_y)
     .def_readwrite("noise_rotation_z", &LocalizerParam::noise_rotation_z)
     .def_readwrite("resize_factor", &LocalizerParam::resize_factor)
-    .def_readwrite("one_pass", &LocalizerParam::one_pass);
+    .def_readwrite("one_pass", &LocalizerParam::one_pass)
+    .def_readwrite("dist_params", &LocalizerParam::dist_params);
 
   py::class_<Localizer, std::shared_ptr<Localizer>>(m, "Localizer")
     .def(py::init<const LocalizerParam &>(), py::arg("param"),

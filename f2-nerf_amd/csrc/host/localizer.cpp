@@ -110,6 +110,9 @@ void Localizer::init(
   // rows 0 and 1 (fx, skew, cx / fy, cy) scale with the image; row 2 stays [0, 0, 1]
   intrinsic_ = intrinsic.to(torch::kFloat32).reshape({3, 3}).to(dev).clone();
   intrinsic_.slice(0, 0, 2).div_(param_.resize_factor);
+  const std::array<float, 4> & k = param_.dist_params;
+  if (k[0] != 0.f || k[1] != 0.f || k[2] != 0.f || k[3] != 0.f)
+    dist_ = torch::tensor({k[0], k[1], k[2], k[3]}).to(dev);
   center_ = center.to(torch::kFloat32).reshape({3}).to(dev);
   radius_ = radius;
   infer_height_ = height / param_.resize_factor;
@@ -186,7 +189,7 @@ Tensor Localizer::render_image(const Tensor & pose)
 {
   f2n::dev_f32(pose, "pose");
   return std::get<0>(
-    renderer_->render_image(pose, intrinsic_, infer_height_, infer_width_, kRayChunk));
+    renderer_->render_image(pose, intrinsic_, infer_height_, infer_width_, kRayChunk, dist_));
 }
 
 Rays Localizer::pose_rays(const Tensor & poses, const Tensor & ij)
@@ -195,7 +198,7 @@ Rays Localizer::pose_rays(const Tensor & poses, const Tensor & ij)
   TORCH_CHECK(
     p.dim() == 3 && p.size(2) == 4 && (p.size(1) == 3 || p.size(1) == 4) && p.size(0) > 0,
     "poses must be [P,3,4] or [P,4,4], P > 0");
-  return get_rays_from_poses(p, intrinsic_, ij);
+  return get_rays_from_poses(p, intrinsic_, ij, dist_);
 }
 
 Localizer::PoseScores Localizer::evaluate_poses_full(

@@ -40,6 +40,11 @@ struct LocalizerParam
   // render particles and images with the one-kernel inference path (RendererOptions::one_pass); not
   // part of inference_params.yaml
   bool one_pass = false;
+  // lens distortion (k1, k2, p1, p2) of the camera whose images are localised, the columns of
+  // cams_meta.tsv (src/dataset.cpp:59-63): pose_rays and render_image undistort their pixels in the
+  // ray kernel, so the image handed in is the raw one.  They act on normalised coordinates:
+  // resize_factor leaves them alone.  Zeros = pinhole.  Not part of inference_params.yaml either.
+  std::array<float, 4> dist_params = {0.f, 0.f, 0.f, 0.f};
 };
 
 namespace f2n
@@ -128,6 +133,7 @@ private:
 
   int infer_height_ = 0, infer_width_ = 0;
   Tensor intrinsic_;
+  Tensor dist_;  // [4] on the device; undefined when param_.dist_params is all zeros
   Tensor center_;
   float radius_ = 1.f;
 };

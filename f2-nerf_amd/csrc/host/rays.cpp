@@ -19,9 +19,21 @@ std::pair<Tensor, int> pose_blocks(const Tensor & pose)
   return {f2n::dev_f32(pose, "pose"), (int)(pose.size(1) * 4)};
 }
 
+// dist as [n_cams,4] contiguous f32 on the poses' device; undefined stays undefined (pinhole)
+Tensor dist_rows(const Tensor & dist, int64_t n_cams, const Tensor & poses)
+{
+  if (!dist.defined()) return dist;
+  TORCH_CHECK(
+    dist.numel() == n_cams * 4 && dist.size(-1) == 4,
+    "dist must hold (k1, k2, p1, p2) for each of the ", n_cams, " cameras");
+  Tensor d = f2n::dev_f32(dist.detach(), "dist").view({n_cams, 4});
+  TORCH_CHECK(d.device() == poses.device(), "dist must be on the poses' device");
+  return d;
+}
+
 Rays launch_gen_rays(
   const Tensor & pose, const Tensor & intrinsic, const Tensor & cam_idx, const Tensor & ij,
-  int64_t first_pixel, int width, int64_t n)
+  int64_t first_pixel, int width, int64_t n, const Tensor & dist = {})
 {
   auto [poses, pose_ld] = pose_blocks(pose);
   Tensor K = f2n::dev_f32(intrinsic, "intrinsic");
@@ -29,6 +41,16 @@ Rays launch_gen_rays(
     K.dim() == 3 && K.size(1) == 3 && K.size(2) == 3 && K.size(0) == poses.size(0),
     "intrinsic must be [B,3,3] with the poses' B");
   Rays rays{torch::empty({n, 3}, poses.options()), torch::empty({n, 3}, poses.options())};
+  if (dist.defined()) {
+    Tensor D = dist_rows(dist, poses.size(0), poses);
+    f2n::check(
+      f2n_gen_rays_dist(
+        poses.data_ptr<float>(), pose_ld, K.data_ptr<float>(), D.data_ptr<float>(), poses.size(0),
+        f2n::iptr(cam_idx), f2n::iptr(ij), first_pixel, width, rays.origins.data_ptr<float>(),
+        rays.dirs.data_ptr<float>(), n, f2n::current_stream(poses)),
+      "f2n_gen_rays_dist");
+    return rays;
+  }
   f2n::check(
     f2n_gen_rays(
       poses.data_ptr<float>(), pose_ld, K.data_ptr<float>(), poses.size(0), f2n::iptr(cam_idx),
@@ -40,18 +62,20 @@ Rays launch_gen_rays(
 
 // launch_gen_rays with a backward to the pose (the intrinsics are constants, as in the reference's
 // pose optimisation, src/localizer.cpp:142-167).  ij empty = pixel first_pixel + r of a `width`-wide
-// image (undefined tensors cannot pass through apply()).  No cam_idx: every ray uses pose 0, or ray
-// r pose r.
+// image, dist empty = pinhole (undefined tensors cannot pass through apply()).  No cam_idx: every ray
+// uses pose 0, or ray r pose r.
 class GenRaysFn : public torch::autograd::Function<GenRaysFn>
 {
 public:
   static torch::autograd::variable_list forward(
-    torch::autograd::AutogradContext * ctx, Tensor pose, Tensor intrinsic, Tensor ij,
+    torch::autograd::AutogradContext * ctx, Tensor pose, Tensor intrinsic, Tensor ij, Tensor dist,
     int64_t first_pixel, int64_t width, int64_t n)
   {
     if (ij.numel() == 0) ij = Tensor();
-    Rays rays = launch_gen_rays(pose, intrinsic, Tensor(), ij, first_pixel, (int)width, n);
-    ctx->save_for_backward({f2n::dev_f32(intrinsic, "intrinsic"), ij});
+    if (dist.numel() == 0) dist = Tensor();
+    dist = dist_rows(dist, pose.size(0), pose);
+    Rays rays = launch_gen_rays(pose, intrinsic, Tensor(), ij, first_pixel, (int)width, n, dist);
+    ctx->save_for_backward({f2n::dev_f32(intrinsic, "intrinsic"), ij, dist});
     ctx->saved_data["first_pixel"] = first_pixel;
     ctx->saved_data["width"] = width;
     ctx->saved_data["pose_shape"] = pose.sizes().vec();
@@ -64,6 +88,7 @@ public:
     auto saved = ctx->get_saved_variables();
     const Tensor & K = saved[0];
     const Tensor & ij = saved[1];
+    const Tensor & dist = saved[2];
     const auto shape = ctx->saved_data["pose_shape"].toIntVector();
     const int64_t n_cams = shape[0];
     const int pose_ld = (int)(shape[1] * 4);
@@ -72,15 +97,27 @@ public:
     const int64_t n = ref.defined() ? ref.size(0) : 0;
     Tensor d_o = grad[0].defined() ? f2n::dev_f32(grad[0], "grad rays_o") : torch::zeros({n, 3}, opt);
     Tensor d_d = grad[1].defined() ? f2n::dev_f32(grad[1], "grad rays_d") : torch::zeros({n, 3}, opt);
-    Tensor d_pose = torch::empty(shape, opt);
     Tensor ws = torch::empty({f2n_gen_rays_bwd_workspace_floats(n)}, opt);
+    if (dist.defined()) {
+      // (no rays: the entry writes nothing)
+      Tensor d_pose = n > 0 ? torch::empty(shape, opt) : torch::zeros(shape, opt);
+      f2n::check(
+        f2n_gen_rays_dist_bwd(
+          K.data_ptr<float>(), dist.data_ptr<float>(), n_cams, f2n::iptr(ij),
+          ctx->saved_data["first_pixel"].toInt(), (int)ctx->saved_data["width"].toInt(),
+          d_o.data_ptr<float>(), d_d.data_ptr<float>(), d_pose.data_ptr<float>(), pose_ld,
+          ws.data_ptr<float>(), n, f2n::current_stream(K)),
+        "f2n_gen_rays_dist_bwd");
+      return {d_pose, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    }
+    Tensor d_pose = torch::empty(shape, opt);
     f2n::check(
       f2n_gen_rays_bwd(
         K.data_ptr<float>(), n_cams, f2n::iptr(ij), ctx->saved_data["first_pixel"].toInt(),
         (int)ctx->saved_data["width"].toInt(), d_o.data_ptr<float>(), d_d.data_ptr<float>(),
         d_pose.data_ptr<float>(), pose_ld, ws.data_ptr<float>(), n, f2n::current_stream(K)),
       "f2n_gen_rays_bwd");
-    return {d_pose, Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    return {d_pose, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
   }
 };
 
@@ -88,18 +125,21 @@ public:
 // gradient
 Rays gen_rays(
   const Tensor & pose, const Tensor & intrinsic, const Tensor & ij, int64_t first_pixel, int width,
-  int64_t n)
+  int64_t n, const Tensor & dist)
 {
   if (!(torch::GradMode::is_enabled() && pose.requires_grad()))
-    return launch_gen_rays(pose, intrinsic, Tensor(), ij, first_pixel, width, n);
+    return launch_gen_rays(pose, intrinsic, Tensor(), ij, first_pixel, width, n, dist);
   const Tensor pixels = ij.defined() ? ij : torch::empty({0}, f2n::int_on(pose.device()));
-  auto out = GenRaysFn::apply(pose, intrinsic.detach(), pixels, first_pixel, (int64_t)width, n);
+  const Tensor lens = dist.defined() ? dist.detach() : torch::empty({0}, f2n::float_on(pose.device()));
+  auto out =
+    GenRaysFn::apply(pose, intrinsic.detach(), pixels, lens, first_pixel, (int64_t)width, n);
   return {out[0], out[1]};
 }
 
 }  // namespace
 
-Rays get_rays_from_pose(const Tensor & pose, const Tensor & intrinsic, const Tensor & ij)
+Rays get_rays_from_pose(
+  const Tensor & pose, const Tensor & intrinsic, const Tensor & ij, const Tensor & dist)
 {
   TORCH_CHECK(ij.dim() == 2 && ij.size(1) == 2, "ij must be [N,2]");
   const int64_t n = ij.size(0);
@@ -107,31 +147,38 @@ Rays get_rays_from_pose(const Tensor & pose, const Tensor & intrinsic, const Ten
     pose.size(0) == 1 || pose.size(0) == n, "pose batch must be 1 or N (src/rays.cpp broadcast)");
   // the reference converts whatever ij holds with .to(kFloat32); pixel indices are exact either way
   Tensor ij32 = f2n::dev_i32(ij.to(torch::kInt32), "ij");
-  return gen_rays(pose, intrinsic, ij32, 0, 1, n);
+  return gen_rays(pose, intrinsic, ij32, 0, 1, n, dist);
 }
 
-Rays get_rays_from_poses(const Tensor & poses, const Tensor & intrinsic, const Tensor & ij)
+Rays get_rays_from_poses(
+  const Tensor & poses, const Tensor & intrinsic, const Tensor & ij, const Tensor & dist)
 {
   TORCH_CHECK(ij.dim() == 2 && ij.size(1) == 2, "ij must be [K,2]");
   TORCH_CHECK(intrinsic.dim() == 2, "intrinsic must be [3,3]: the poses share one camera");
   Tensor ij32 = f2n::dev_i32(ij, "ij");
   const int64_t P = poses.size(0), K = ij32.size(0);
   Tensor cam = torch::arange(P * K, f2n::int_on(ij32.device())).floor_divide_(K);
+  Tensor lens;
+  if (dist.defined()) {
+    TORCH_CHECK(dist.numel() == 4, "dist must be [4]: the poses share one camera");
+    lens = dist.reshape({1, 4}).expand({P, 4});
+  }
   return launch_gen_rays(
-    poses, intrinsic.unsqueeze(0).expand({P, 3, 3}), cam, ij32.repeat({P, 1}), 0, 1, P * K);
+    poses, intrinsic.unsqueeze(0).expand({P, 3, 3}), cam, ij32.repeat({P, 1}), 0, 1, P * K, lens);
 }
 
-Rays get_view_rays(const Tensor & pose, const Tensor & intrinsic, int h, int w)
+Rays get_view_rays(
+  const Tensor & pose, const Tensor & intrinsic, int h, int w, const Tensor & dist)
 {
   Tensor p = pose.dim() == 2 ? pose.unsqueeze(0) : pose;
   Tensor k = intrinsic.dim() == 2 ? intrinsic.unsqueeze(0) : intrinsic;
   TORCH_CHECK(p.size(0) == 1 && h > 0 && w > 0, "get_view_rays: one pose, a positive image size");
-  return gen_rays(p, k, Tensor(), 0, w, (int64_t)h * w);
+  return gen_rays(p, k, Tensor(), 0, w, (int64_t)h * w, dist);
 }
 
 std::tuple<Rays, Tensor, Tensor> sample_random_rays(
   const Tensor & poses, const Tensor & intrinsics, int h, int w, int64_t batch_size,
-  const Tensor & images)
+  const Tensor & images, const Tensor & dist)
 {
   const auto iopt = torch::TensorOptions().dtype(torch::kInt32).device(poses.device());
   const int64_t n_images = poses.size(0);
@@ -139,11 +186,38 @@ std::tuple<Rays, Tensor, Tensor> sample_random_rays(
   Tensor i = torch::randint(0, h, {batch_size}, iopt);
   Tensor j = torch::randint(0, w, {batch_size}, iopt);
   Tensor ij = torch::stack({i, j}, -1).contiguous();
-  Rays rays = launch_gen_rays(poses, intrinsics, cam, ij, 0, 1, batch_size);
+  Rays rays = launch_gen_rays(poses, intrinsics, cam, ij, 0, 1, batch_size, dist);
   Tensor gt;
   if (images.defined()) {
     Tensor flat = (cam.to(torch::kLong) * h + i.to(torch::kLong)) * w + j.to(torch::kLong);
     gt = images.view({-1, 3}).index({flat}).to(poses.device()).contiguous();
   }
   return {rays, gt, cam};
+}
+
+std::tuple<Tensor, Tensor> project_points(
+  const Tensor & points, const Tensor & pose, const Tensor & intrinsic, const Tensor & dist)
+{
+  Tensor pts = f2n::dev_f32(points, "points");
+  TORCH_CHECK(pts.dim() == 2 && pts.size(1) == 3, "points must be [N,3]");
+  const int64_t n = pts.size(0);
+  auto [poses, pose_ld] = pose_blocks(pose.dim() == 2 ? pose.unsqueeze(0) : pose);
+  const int64_t B = poses.size(0);
+  TORCH_CHECK(B == 1 || B == n, "pose batch must be 1 or N");
+  Tensor K = f2n::dev_f32(intrinsic.dim() == 2 ? intrinsic.unsqueeze(0) : intrinsic, "intrinsic");
+  TORCH_CHECK(
+    K.dim() == 3 && K.size(1) == 3 && K.size(2) == 3 && K.size(0) == B,
+    "intrinsic must be [B,3,3] with the poses' B");
+  TORCH_CHECK(
+    poses.device() == pts.device() && K.device() == pts.device(),
+    "points, pose and intrinsic must be on the same device");
+  Tensor D = dist_rows(dist, B, poses);
+  Tensor pix = torch::empty({n, 2}, pts.options());
+  Tensor valid = torch::empty({n}, f2n::int_on(pts.device()));
+  f2n::check(
+    f2n_project_points(
+      pts.data_ptr<float>(), poses.data_ptr<float>(), pose_ld, K.data_ptr<float>(), f2n::fptr(D), B,
+      nullptr, pix.data_ptr<float>(), valid.data_ptr<int32_t>(), n, f2n::current_stream(pts)),
+    "f2n_project_points");
+  return {pix, valid};
 }

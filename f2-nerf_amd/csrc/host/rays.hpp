@@ -18,28 +18,52 @@ struct alignas(32) Rays
 // src/localizer.cpp:142-167): the backward (f2n_gen_rays_bwd) returns d(pose) in the pose's own shape
 // ([B,3,4] / [B,4,4], or [3,4] / [4,4] through get_view_rays), row 3 of a [4,4] pose zero, the sum
 // over the rays in a fixed order.  The intrinsics are constants: they never receive a gradient.
+//
+// Lens distortion: every function takes an optional `dist` holding (k1, k2, p1, p2) per camera, the
+// columns CamsMeta::dist_params reads from cams_meta.tsv (src/dataset.cpp:59-63; the reference's
+// src/rays.cpp:7-28 ignores them).  Defined: the pixel is undistorted in the kernel
+// (f2n_gen_rays_dist, 8 Newton steps) and the backward is f2n_gen_rays_dist_bwd.  Undefined: the
+// pinhole entry points, as before.  A camera whose four numbers are zero gives the pinhole bits
+// either way.  Like the intrinsics, `dist` never receives a gradient.
 
 // pose [B,3,4] (or [B,4,4]), intrinsic [B,3,3], ij [N,2] = (row, col), float or integer; B == 1 or
 // B == N.  Pixel centres (+0.5), camera looks down -z, y up.  One kernel (f2n_gen_rays).
+// dist: [B,4].
 Rays get_rays_from_pose(
-  const torch::Tensor & pose, const torch::Tensor & intrinsic, const torch::Tensor & ij);
+  const torch::Tensor & pose, const torch::Tensor & intrinsic, const torch::Tensor & ij,
+  const torch::Tensor & dist = {});
 
 // The same K pixels under each of P poses that share one camera, pose-major (ray p*K + k is pixel k
 // under pose p): what the reference's Localizer::evaluate_poses builds with one get_rays_from_pose
 // per pose and two cats (src/localizer.cpp:218-231), as one f2n_gen_rays launch with a per-ray
 // camera index.  poses [P,3,4] (or [P,4,4]), intrinsic [3,3], ij [K,2] int32.  Not differentiated.
+// dist: [4], the one camera's.
 Rays get_rays_from_poses(
-  const torch::Tensor & poses, const torch::Tensor & intrinsic, const torch::Tensor & ij);
+  const torch::Tensor & poses, const torch::Tensor & intrinsic, const torch::Tensor & ij,
+  const torch::Tensor & dist = {});
 
 // All h*w pixels of one view in row-major order, without materialising the pixel grid
 // (Dataset::get_rays_from_pose(idx) / Renderer::render_image of the reference).
-Rays get_view_rays(const torch::Tensor & pose, const torch::Tensor & intrinsic, int h, int w);
+// dist: [4] or [1,4].
+Rays get_view_rays(
+  const torch::Tensor & pose, const torch::Tensor & intrinsic, int h, int w,
+  const torch::Tensor & dist = {});
 
 // Dataset::sample_random_rays (src/dataset.cpp:150-171) with everything on the device: camera and
 // pixel indices are drawn there, each ray reads its own camera from the pose / intrinsic tables
 // (no index_select, no host randint + copy).  images: optional [E, h, w, 3] for the ground truth.
 // Not differentiated: the rays carry no gradient to `poses` (training samples are data).
+// dist: [E,4], one row per image.
 // Returns {rays, gt_colors [n,3] (undefined without images), cam_indices [n] i32}.
 std::tuple<Rays, torch::Tensor, torch::Tensor> sample_random_rays(
   const torch::Tensor & poses, const torch::Tensor & intrinsics, int h, int w, int64_t batch_size,
-  const torch::Tensor & images = {});
+  const torch::Tensor & images = {}, const torch::Tensor & dist = {});
+
+// The forward model, world point -> pixel (f2n_project_points): points [N,3]; pose [B,3,4] (or
+// [B,4,4], or one [3,4] / [4,4]), intrinsic [B,3,3] (or [3,3]), dist [B,4] (or [4]; undefined =
+// pinhole); B == 1 or B == N.  Returns {pix [N,2] f32 continuous (row, col) with pixel (i, j) centred
+// at (i + .5, j + .5), valid [N] i32: 1 iff the point lies strictly in front of its camera}.  No
+// image-bounds test.  Not differentiated.
+std::tuple<torch::Tensor, torch::Tensor> project_points(
+  const torch::Tensor & points, const torch::Tensor & pose, const torch::Tensor & intrinsic,
+  const torch::Tensor & dist = {});

@@ -843,9 +843,10 @@ std::tuple<Tensor, Tensor> Renderer::render_all_rays(
 }
 
 std::tuple<Tensor, Tensor> Renderer::render_image(
-  const Tensor & pose, const Tensor & intrinsic, const int h, const int w, const int batch_size)
+  const Tensor & pose, const Tensor & intrinsic, const int h, const int w, const int batch_size,
+  const Tensor & dist)
 {
-  Rays rays = get_view_rays(pose, intrinsic, h, w);  // pixel grid generated in the kernel
+  Rays rays = get_view_rays(pose, intrinsic, h, w, dist);  // pixel grid generated in the kernel
   // The view is traversed in B x B pixel tiles rather than row by row: the ray-tile encode takes 64
   // consecutive rays per workgroup, and an 8 x 8 block of pixels is a bundle 8 pixels wide both
   // ways instead of a strip 64 pixels long -- a third fewer distinct table lines per gather at the

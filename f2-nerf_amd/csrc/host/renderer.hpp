@@ -154,9 +154,11 @@ public:
   std::tuple<Tensor, Tensor> render_all_rays(
     const Tensor & rays_o, const Tensor & rays_d, const int batch_size);
 
+  // dist: optional (k1, k2, p1, p2) of the view's camera, [4] or [1,4] (get_view_rays); undefined =
+  // pinhole, as in the reference
   std::tuple<Tensor, Tensor> render_image(
     const torch::Tensor & pose, const torch::Tensor & intrinsic, const int h, const int w,
-    const int batch_size);
+    const int batch_size, const torch::Tensor & dist = torch::Tensor());
 
   std::vector<torch::optim::OptimizerParamGroup> optim_param_groups(float lr);
 

@@ -17,6 +17,10 @@
 //     |d/|d||; the normalisation's Jacobian (I - n n^T)/|d| annihilates that direction, so the path
 //     is zero analytically (autograd forms it from roundings of the order of 1e-7 of the terms);
 //   * the SH encoding of the directions has no backward in the reference (src/sh_shader.cu:105-115).
+//
+//   f2n_gen_rays_dist_bwd  the same for cameras with lens distortion: v_r is the undistorted
+//                       direction of camera.hiph, which does not depend on the pose.
+#include "camera.hiph"
 #include "hash_grid.hiph"
 
 namespace
@@ -268,6 +272,68 @@ __global__ __launch_bounds__(F2N_BLOCK) void gen_rays_bwd_final_kernel(
   if (pose_ld == 16 && threadIdx.x >= 12 && threadIdx.x < 16) d_pose[threadIdx.x] = 0.f;
 }
 
+// ---- f2n_gen_rays_dist_bwd ------------------------------------------------------------------------
+//
+// The per-ray and the partial kernel above with v_r from camera_pixel_to_dir (the function the
+// forward calls): same partition, same order of the sums, the same final kernel.  A row of zeros in
+// `dist` gives the bits of the kernels above.
+
+__global__ __launch_bounds__(F2N_BLOCK) void lens_rays_bwd_per_ray_kernel(
+  const float * __restrict__ intrinsics, const float * __restrict__ dist,
+  const int32_t * __restrict__ ij, int64_t first_pixel, int width, const float * __restrict__ d_o,
+  const float * __restrict__ d_d, float * __restrict__ d_poses, int pose_ld, int64_t n)
+{
+  const int64_t r = (int64_t)blockIdx.x * F2N_BLOCK + threadIdx.x;
+  if (r >= n) return;
+  float row, col, u, v;
+  ray_pixel(ij, first_pixel, width, r, row, col);
+  camera_pixel_to_dir(intrinsics + r * 9, load_lens(dist, r), row, col, u, v);
+  const float w = -1.f;
+  float * P = d_poses + r * pose_ld;
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    const float g = d_d[3 * r + a];
+    P[4 * a] = g * u;
+    P[4 * a + 1] = g * v;
+    P[4 * a + 2] = g * w;
+    P[4 * a + 3] = d_o[3 * r + a];
+  }
+  if (pose_ld == 16) {
+#pragma unroll
+    for (int j = 12; j < 16; j++) P[j] = 0.f;
+  }
+}
+
+__global__ __launch_bounds__(F2N_BLOCK) void lens_rays_bwd_partial_kernel(
+  const float * __restrict__ K, const float * __restrict__ dist, const int32_t * __restrict__ ij,
+  int64_t first_pixel, int width, const float * __restrict__ d_o, const float * __restrict__ d_d,
+  float * __restrict__ partial, int64_t n, int64_t per_group)
+{
+  __shared__ float part[F2N_WAVES_PER_BLOCK][12];
+  const int64_t lo = (int64_t)blockIdx.x * per_group;
+  const int64_t hi = (lo + per_group < n) ? lo + per_group : n;
+  const LensDist lens = load_lens(dist, 0);
+  float acc[12];
+#pragma unroll
+  for (int c = 0; c < 12; c++) acc[c] = 0.f;
+  for (int64_t r = lo + threadIdx.x; r < hi; r += F2N_BLOCK) {
+    float row, col, u, v;
+    ray_pixel(ij, first_pixel, width, r, row, col);
+    camera_pixel_to_dir(K, lens, row, col, u, v);
+    const float w = -1.f;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      const float g = d_d[3 * r + a];
+      acc[4 * a] = fmaf(g, u, acc[4 * a]);
+      acc[4 * a + 1] = fmaf(g, v, acc[4 * a + 1]);
+      acc[4 * a + 2] = fmaf(g, w, acc[4 * a + 2]);
+      acc[4 * a + 3] += d_o[3 * r + a];
+    }
+  }
+  const float s = block_sum12(acc, part);
+  if (threadIdx.x < 12) partial[12 * (int64_t)blockIdx.x + threadIdx.x] = s;
+}
+
 inline bool is_pow2(uint32_t v) { return v && !(v & (v - 1u)); }
 
 }  // namespace
@@ -341,5 +407,40 @@ extern "C" int f2n_gen_rays_bwd(
   hipLaunchKernelGGL(
     gen_rays_bwd_per_ray_kernel, dim3(f2n_div_up(n, F2N_BLOCK)), dim3(F2N_BLOCK), 0, s, intrinsics,
     ij, first_pixel, width, d_rays_o, d_rays_d, d_poses, pose_ld, n);
+  return f2n_launch_status();
+}
+
+extern "C" int f2n_gen_rays_dist_bwd(
+  const float * intrinsics, const float * dist, int64_t n_cams, const int32_t * ij,
+  int64_t first_pixel, int width, const float * d_rays_o, const float * d_rays_d, float * d_poses,
+  int pose_ld, float * workspace, int64_t n, void * stream)
+{
+  if (!intrinsics || !d_rays_o || !d_rays_d || !d_poses || !workspace || n < 0 || n_cams < 1)
+    return F2N_E_INVALID_ARG;
+  if (pose_ld != 12 && pose_ld != 16) return F2N_E_INVALID_ARG;
+  if (!ij && width <= 0) return F2N_E_INVALID_ARG;
+  if (first_pixel < 0) return F2N_E_INVALID_ARG;
+  if (n_cams != 1 && n_cams != n) return F2N_E_INVALID_ARG;
+  if (n == 0) return F2N_OK;
+  if (!dist)  // pinhole: the existing kernels
+    return f2n_gen_rays_bwd(
+      intrinsics, n_cams, ij, first_pixel, width, d_rays_o, d_rays_d, d_poses, pose_ld, workspace, n,
+      stream);
+  hipStream_t s = (hipStream_t)stream;
+  if (n_cams == 1) {
+    const int64_t groups = pose_groups(n);
+    const int64_t per = (n + groups - 1) / groups;
+    hipLaunchKernelGGL(
+      lens_rays_bwd_partial_kernel, dim3((unsigned)groups), dim3(F2N_BLOCK), 0, s, intrinsics, dist,
+      ij, first_pixel, width, d_rays_o, d_rays_d, workspace, n, per);
+    if (hipGetLastError() != hipSuccess) return F2N_E_LAUNCH;
+    hipLaunchKernelGGL(
+      gen_rays_bwd_final_kernel, dim3(1), dim3(F2N_BLOCK), 0, s, workspace, (int)groups, d_poses,
+      pose_ld);
+    return f2n_launch_status();
+  }
+  hipLaunchKernelGGL(
+    lens_rays_bwd_per_ray_kernel, dim3(f2n_div_up(n, F2N_BLOCK)), dim3(F2N_BLOCK), 0, s, intrinsics,
+    dist, ij, first_pixel, width, d_rays_o, d_rays_d, d_poses, pose_ld, n);
   return f2n_launch_status();
 }

@@ -262,6 +262,51 @@ int f2n_gen_rays_bwd(
   const float * d_rays_o, const float * d_rays_d, float * d_poses, int pose_ld, float * workspace,
   int64_t n, void * stream);
 
+/* f2n_gen_rays for cameras with lens distortion: the k1, k2, p1, p2 that cams_meta.tsv carries per
+ * image (src/dataset.cpp:59-63 reads them; get_rays_from_pose, src/rays.cpp:7-28, ignores them and
+ * treats every camera as a pinhole).  The OpenCV / COLMAP "OPENCV" model on the normalised image
+ * point, y down: with r2 = x^2 + y^2 and rad = 1 + r2 (k1 + k2 r2),
+ *     xd = x rad + 2 p1 x y + p2 (r2 + 2 x^2),   yd = y rad + p1 (r2 + 2 y^2) + 2 p2 x y.
+ * Pixel (row, col) is the DISTORTED point xd = (col+.5-cx)/fx, yd = (row+.5-cy)/fy; the ray is
+ * dir = R . (x, -y, -1) with (x, y) the solution of the model: exactly 8 Newton steps from (xd, yd),
+ * f32, analytic Jacobian, no data-dependent exit (the same bits on every run); a step whose
+ * determinant is not above 1e-8 in magnitude, or that would leave the finite numbers, is skipped, so
+ * finite arguments give finite rays.
+ *   dist  [n_cams, 4] (k1, k2, p1, p2), addressed like intrinsics: each ray uses its camera's row.
+ *         NULL, or a row of four exact zeros: that camera is a pinhole and its rays are the bits of
+ *         f2n_gen_rays (no iteration).
+ * Everything else as f2n_gen_rays.  Not modelled: fisheye and other camera models, k3 and beyond. */
+int f2n_gen_rays_dist(
+  const float * poses, int pose_ld, const float * intrinsics, const float * dist, int64_t n_cams,
+  const int32_t * cam_idx, const int32_t * ij, int64_t first_pixel, int width, float * rays_o,
+  float * rays_d, int64_t n, void * stream);
+
+/* f2n_gen_rays_bwd for f2n_gen_rays_dist (src/rays.cpp:7-28 under autograd, src/localizer.cpp:142-167;
+ * coefficients of src/dataset.cpp:59-63): v_r is the undistorted direction (x, -y, -1), formed by the
+ * device function the forward calls; it does not depend on the pose, so the formulas of
+ * f2n_gen_rays_bwd stand as they are.  dist [n_cams, 4] or NULL, n_cams is 1 or n.  The workspace is
+ * f2n_gen_rays_bwd_workspace_floats(n) floats; n_cams == 1 sums in the same fixed partition and
+ * order (the same bits on every run; with zero coefficients the bits of f2n_gen_rays_bwd).  Neither
+ * the intrinsics nor the coefficients receive a gradient.  n == 0 returns F2N_OK and writes nothing. */
+int f2n_gen_rays_dist_bwd(
+  const float * intrinsics, const float * dist, int64_t n_cams, const int32_t * ij,
+  int64_t first_pixel, int width, const float * d_rays_o, const float * d_rays_d, float * d_poses,
+  int pose_ld, float * workspace, int64_t n, void * stream);
+
+/* The forward model of the same camera, the inverse of f2n_gen_rays_dist (the projection that
+ * src/rays.cpp:7-28 inverts, with the coefficients of src/dataset.cpp:59-63): world point -> pixel.
+ *   points  [n, 3]; poses, pose_ld, intrinsics, dist (NULL = pinhole), n_cams, cam_idx: addressed as
+ *           in f2n_gen_rays_dist, each point under its camera
+ *   pix     [n, 2] f32 continuous (row, col), pixel (i, j) centred at (i + .5, j + .5):
+ *           c = R^T (p - t), x = c_x / -c_z, y = -c_y / -c_z, distorted as above,
+ *           row = yd fy + cy, col = xd fx + cx
+ *   valid   [n] i32: 1 iff the point lies strictly in front of the camera (c_z < 0); pix of a point
+ *           that does not is (0, 0).  No test against the image bounds: the caller knows its h, w. */
+int f2n_project_points(
+  const float * points, const float * poses, int pose_ld, const float * intrinsics,
+  const float * dist, int64_t n_cams, const int32_t * cam_idx, float * pix, int32_t * valid,
+  int64_t n, void * stream);
+
 /* PtsSampler::get_samples (about 20 ATen launches) -- src/points_sampler.cpp:20-64.
  *   noise   [n_rays, S] f32 step multipliers (TRAIN: U[0.5,1.5)), or NULL for all-ones (VALIDATE)
  *   outputs pts [n_rays*S, 3], dirs [n_rays*S, 3], dt [n_rays*S], t [n_rays*S], bounds [n_rays,2]
