@@ -342,6 +342,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def("set_one_pass", &Renderer::set_one_pass,
          "render_all_rays / render_image in one kernel per chunk: see RendererOptions::one_pass")
     .def("one_pass_applies", &Renderer::one_pass_applies)
+    .def_property_readonly(
+      "one_pass_head", [](const Renderer & r) { return r.options_.one_pass_head; },
+      "RendererOptions::one_pass_head as set_one_pass_head left it")
+    .def("set_one_pass_head", &Renderer::set_one_pass_head,
+         "how the one-pass render walks a ray: 0 one wavefront per ray (default), -1 whole rays eight "
+         "to a wavefront, a positive multiple of 64 = head then tail; see RendererOptions::one_pass_head")
     .def("set_deferred_check", [](Renderer & r, bool f) { r.options_.deferred_check = f; },
          "no host read in render(): see RendererOptions::deferred_check")
     .def("deferred_check_ok", &Renderer::deferred_check_ok)
@@ -423,6 +429,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def_readwrite("noise_rotation_z", &LocalizerParam::noise_rotation_z)
     .def_readwrite("resize_factor", &LocalizerParam::resize_factor)
     .def_readwrite("one_pass", &LocalizerParam::one_pass)
+    .def_readwrite("one_pass_head", &LocalizerParam::one_pass_head)
     .def_readwrite("dist_params", &LocalizerParam::dist_params);
 
   py::class_<Localizer, std::shared_ptr<Localizer>>(m, "Localizer")

@@ -106,7 +106,10 @@ void Localizer::init(
   // the pose optimisation renders 65536-ray chunks of 1024 samples with rays that require grad:
   // they take the fused path (RendererOptions::fused_ray_grad)
   renderer_->options_.fused_ray_grad = true;
-  if (param_.one_pass) renderer_->set_one_pass(true);
+  if (param_.one_pass) {
+    renderer_->set_one_pass(true);
+    renderer_->set_one_pass_head(param_.one_pass_head);
+  }
   // rows 0 and 1 (fx, skew, cx / fy, cy) scale with the image; row 2 stays [0, 0, 1]
   intrinsic_ = intrinsic.to(torch::kFloat32).reshape({3, 3}).to(dev).clone();
   intrinsic_.slice(0, 0, 2).div_(param_.resize_factor);

@@ -40,6 +40,9 @@ struct LocalizerParam
   // render particles and images with the one-kernel inference path (RendererOptions::one_pass); not
   // part of inference_params.yaml
   bool one_pass = false;
+  // with one_pass: RendererOptions::one_pass_head (0 = one ray per wavefront, -1 = whole rays eight
+  // to a wavefront, a positive multiple of 64 = head then tail)
+  int one_pass_head = 0;
   // lens distortion (k1, k2, p1, p2) of the camera whose images are localised, the columns of
   // cams_meta.tsv (src/dataset.cpp:59-63): pose_rays and render_image undistort their pixels in the
   // ray kernel, so the image handed in is the raw one.  They act on normalised coordinates:

@@ -730,6 +730,15 @@ bool Renderer::one_pass_applies() const
   return true;
 }
 
+void Renderer::set_one_pass_head(int n_head)
+{
+  TORCH_CHECK(
+    n_head == 0 || n_head == -1 || (n_head > 0 && n_head % 64 == 0),
+    "one_pass_head is 0 (one ray per wavefront), -1 (whole rays eight to a wavefront) or a positive "
+    "multiple of 64 (head, then tail)");
+  options_.one_pass_head = n_head;
+}
+
 void Renderer::render_rays_into(
   const Tensor & rays_o_raw, const Tensor & rays_d_raw, const Tensor & emb_idx_in, RunningMode mode,
   const Tensor & noise_raw, const Tensor & bg_raw, Tensor colors, Tensor depths, Tensor last_trans,
@@ -766,20 +775,41 @@ void Renderer::render_rays_into(
   const Tensor w2 = f2n::dev_f32(mlp[2].detach(), "shader w2"), b2 = f2n::dev_f32(mlp[3].detach(), "shader b2");
   const Tensor emb = train ? f2n::dev_f32(app_emb_.detach(), "app_emb") : Tensor();
   void * stream = f2n::current_stream(rays_o);
+  // 0: one launch; otherwise the head (n_head >= S: whole rays) and, for a shorter head, the tail
+  const int head_opt = options_.one_pass_head;
+  const int n_head = head_opt < 0 ? S : std::min(head_opt, S);
+  void * state = nullptr;
+  if (head_opt > 0 && n_head < S) {
+    const int64_t words = f2n_render_rays_state_bytes(n_rays) / 4;
+    if (
+      !one_pass_state_.defined() || one_pass_state_.device() != rays_o.device() ||
+      one_pass_state_.numel() < words)
+      one_pass_state_ = torch::empty({words}, f2n::float_on(rays_o.device()));
+    state = one_pass_state_.data_ptr<float>();
+  }
   f2n::ScopedKernelTimer timer("render_rays", stream, (double)n_rays);
+#define F2N_RENDER_RAYS_ARGS                                                                       \
+  rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), f2n::fptr(noise),                            \
+    reinterpret_cast<const uint16_t *>(table16.data_ptr()), field.prim_pool_.data_ptr<int32_t>(),  \
+    field.bias_pool_.data_ptr<float>(), field.level_mul_.data_ptr<float>(), w_h.data_ptr<float>(), \
+    b_h.data_ptr<float>(), w1.data_ptr<float>(), b1.data_ptr<float>(), w2.data_ptr<float>(),       \
+    b2.data_ptr<float>(), f2n::fptr(emb), f2n::iptr(emb_idx),                                      \
+    occupancy_ ? occupancy_->words_ptr() : nullptr,                                                \
+    occupancy_ ? (int)occupancy_->resolution() : 0, bg.data_ptr<float>(),                          \
+    colors.data_ptr<float>(), depths.data_ptr<float>(), last_trans.data_ptr<float>(),              \
+    kept.data_ptr<int32_t>(), nullptr, n_rays, S, pts_sampler_->options_.step,                     \
+    (int)field.options_.n_levels, (int)field.options_.n_channels, (uint32_t)field.local_size_,     \
+    field.level_stride_, options_.early_stop_trans, 3.f, 1e-2f
+  if (head_opt == 0) {
+    f2n::check(f2n_render_rays(F2N_RENDER_RAYS_ARGS, stream), "f2n_render_rays");
+    return;
+  }
   f2n::check(
-    f2n_render_rays(
-      rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), f2n::fptr(noise),
-      reinterpret_cast<const uint16_t *>(table16.data_ptr()), field.prim_pool_.data_ptr<int32_t>(),
-      field.bias_pool_.data_ptr<float>(), field.level_mul_.data_ptr<float>(), w_h.data_ptr<float>(),
-      b_h.data_ptr<float>(), w1.data_ptr<float>(), b1.data_ptr<float>(), w2.data_ptr<float>(),
-      b2.data_ptr<float>(), f2n::fptr(emb), f2n::iptr(emb_idx),
-      occupancy_ ? occupancy_->words_ptr() : nullptr, occupancy_ ? (int)occupancy_->resolution() : 0,
-      bg.data_ptr<float>(), colors.data_ptr<float>(), depths.data_ptr<float>(),
-      last_trans.data_ptr<float>(), kept.data_ptr<int32_t>(), nullptr, n_rays, S,
-      pts_sampler_->options_.step, (int)field.options_.n_levels, (int)field.options_.n_channels,
-      (uint32_t)field.local_size_, field.level_stride_, options_.early_stop_trans, 3.f, 1e-2f, stream),
-    "f2n_render_rays");
+    f2n_render_rays_head(F2N_RENDER_RAYS_ARGS, n_head, state, stream), "f2n_render_rays_head");
+  if (n_head < S)
+    f2n::check(
+      f2n_render_rays_tail(F2N_RENDER_RAYS_ARGS, n_head, state, stream), "f2n_render_rays_tail");
+#undef F2N_RENDER_RAYS_ARGS
 }
 
 std::tuple<Tensor, Tensor, Tensor, Tensor> Renderer::render_rays(

@@ -117,6 +117,14 @@ struct RendererOptions
   // otherwise they do exactly what they do without it.  render() and train_step never take it: it
   // produces no per-sample weights and no gradients.
   bool one_pass = false;
+  // How the one-pass render walks a ray (render_rays and everything that follows one_pass):
+  //   0  one wavefront per ray, one launch (f2n_render_rays) -- the default;
+  //  -1  the whole ray eight rays to a wavefront (f2n_render_rays_head with n_head >= S);
+  //  a positive multiple of 64: the first one_pass_head samples eight rays to a wavefront, then the
+  //      rays still alive one wavefront each (f2n_render_rays_head + f2n_render_rays_tail).
+  // For scenes whose rays stop after a few samples.  Still no host read, O(n_rays)
+  // memory (64 bytes of state per ray of a chunk, cached) and capturable in a hipGraph.
+  int one_pass_head = 0;
 };
 
 class Renderer : public torch::nn::Module
@@ -146,6 +154,8 @@ public:
     const Tensor & noise = Tensor(), const Tensor & bg_color = Tensor());
 
   void set_one_pass(bool on) { options_.one_pass = on; }
+  // RendererOptions::one_pass_head: 0, -1 or a positive multiple of 64
+  void set_one_pass_head(int n_head);
   // does render_all_rays / render_image take the one-kernel path right now?  (options_.one_pass, the
   // fused network applies, and grad mode is off or no parameter requires grad; rays that themselves
   // require grad under grad mode keep the default routes whatever this says)
@@ -177,6 +187,9 @@ public:
   int64_t last_n_samples_ = 0;  // survivors of the most recent render() (bench bookkeeping)
   float last_kept_fraction_ = 0.f;
   f2n::HostCount survivors_;
+  // f2n_render_rays_head's state for the largest chunk seen (one_pass_head > 0); grown outside graph
+  // capture by the warm-up calls, reused afterwards
+  Tensor one_pass_state_;
 
   // options_.deferred_check: renders since the last reset whose guess "nothing terminates" was wrong
   // (device int32, created on first use; stays valid across hipGraph replays).  deferred_check_ok()
@@ -203,7 +216,8 @@ private:
 
   Route choose_route(const Tensor & rays_o, const Tensor & rays_d, const Tensor & bg_color) const;
   bool fused_net_applies() const;
-  // one f2n_render_rays launch into preallocated outputs (rows of one chunk)
+  // f2n_render_rays -- or, by options_.one_pass_head, the head or head + tail -- into preallocated
+  // outputs (rows of one chunk)
   void render_rays_into(
     const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
     const Tensor & noise, const Tensor & bg_color, Tensor colors, Tensor depths, Tensor last_trans,

@@ -1,0 +1,501 @@
+// render_rays_head.hip -- the one-pass render where rays are SHORT: eight rays to a wavefront.
+//
+// render_rays_kernel (render_rays.hip) gives one wavefront to one ray and walks it 64 samples at a
+// time: a ray that keeps three samples still pays a 64-sample stride and a full pass of the network
+// (an 800 x 800 view keeping 3.1 samples per ray: 16x the default route).  Here the HEAD of every ray
+// -- its first n_head samples -- is walked with density_march8_kernel's mapping (sampler.hip): a ray
+// owns half a DPP row, g = lane >> 3 is the ray of the wave, m = lane & 7 the sample of an 8-sample
+// stride.  Replaces the same reference sites as f2n_render_rays: Renderer::render
+// (src/renderer.cpp:33-123) as render_all_rays (:125-151) and Localizer::evaluate_poses
+// (src/localizer.cpp:172) use it.
+//
+//   f2n_render_rays_head  per 8-sample stride of 8 rays: sample, contract, occupancy bit, the level
+//     loop with the march's chain logit and the f16 tile (column = lane), the march's keep decision
+//     by half_scan_step (sampler.hiph: the 64-lane scan's additions, so kept / len are the march's
+//     bit for bit), then -- if any of the 64 columns is a kept, occupied sample -- the network on
+//     the 64 columns and the compositing sums inside each 8-lane group.  Column c belongs to ray
+//     c >> 3 for the whole life of the wave: SH16(dir) and the embedding row of the 8 rays sit in a
+//     small LDS block per wave, written once per ray group.  b1 + W1[:, 16:32] . SH is RECOMPUTED per
+//     stride (4 more matrix instructions per 16 x 16 block, in the one-ray form's order: the same
+//     bits per column): held per column it would be 64 registers and cost the register class.
+//     A ray that ends inside the head gets its outputs here; one that is still alive at
+//     k0 == n_head leaves its state (below) and a pending flag.
+//   f2n_render_rays_tail  render_one_ray (render_rays.hiph), resumed from that state at k0 = n_head
+//     for the pending rays; the others are skipped on a scalar flag load.
+//
+// n_head is a multiple of 64 or >= S: the 64-lane scan's block boundary is where the half-row form's
+// carries ARE the one-ray form's (carry + ((T3 + T2) + (T1 + T0))).
+//
+// State, 16 words (64 bytes) per ray, written by the head only when n_head < S:
+//   [0] int32 pending (1: resume at n_head, 0: the ray's outputs are final)
+//   [1] cumulative noise   [2..4] last sample point   [5] chain optical depth (the march's)
+//   [6] compositing optical depth   [7..10] the partial sums r, g, b, depth (reduced over the group)
+//   [11] int32 n_kept   [12] int32 n_len   [13..15] unused
+// A ray that is not pending has only word 0 written.
+//
+// No atomics, no workspace but the state: two launches give the same bits.
+#include "render_rays.hiph"
+
+#include <algorithm>
+
+namespace
+{
+
+constexpr int kStateWords = 16;
+
+template <int C>
+struct HShape
+{
+  using R = RShape<C>;
+  using FS = typename R::FS;
+  // ~150 registers (the half-row scans' state on top of the network's; capped at 128 the kernel
+  // spills): three waves per SIMD, so ONE workgroup of 12 waves per CU rather than two of 8
+  static constexpr int kWaves = 12;
+  static constexpr int kRayFloats = 2 * 8 * 16;  // SH16(dir) and the embedding row of the wave's 8 rays
+  static constexpr int kWaveFloats = R::kWaveFloats + kRayFloats;
+  static constexpr int kLdsFloats = FS::kWFloats + kWaves * kWaveFloats;
+  static_assert(kLdsFloats * 4 <= 160 * 1024, "LDS budget");
+};
+
+// inclusive scan inside the own 8-lane group, in lane order (every move by all lanes, then selected)
+__device__ __forceinline__ float group_incl_scan(float v, int m)
+{
+  const float s1 = dpp_get<0x111, 0xf, 0xf>(v, 0.f);
+  v += (m >= 1 ? s1 : 0.f);
+  const float s2 = dpp_get<0x112, 0xf, 0xf>(v, 0.f);
+  v += (m >= 2 ? s2 : 0.f);
+  const float s4 = dpp_get<0x114, 0xf, 0xf>(v, 0.f);
+  v += (m >= 4 ? s4 : 0.f);
+  return v;
+}
+
+__device__ __forceinline__ float group_sum(float v, int m, int lane)
+{
+  return group_last(group_incl_scan(v, m), lane);
+}
+
+#define F2N_RENDER_PARAMS                                                                          \
+  const float * __restrict__ rays_o, const float * __restrict__ rays_d,                            \
+    const float * __restrict__ noise, const uint16_t * __restrict__ table,                         \
+    const int32_t * __restrict__ primes, const float * __restrict__ bias,                          \
+    const float * __restrict__ mul, const float * __restrict__ p_w_h,                              \
+    const float * __restrict__ p_b_h, const float * __restrict__ p_w1,                             \
+    const float * __restrict__ p_b1, const float * __restrict__ p_w2,                              \
+    const float * __restrict__ p_b2, const float * __restrict__ p_emb,                             \
+    const int32_t * __restrict__ ray_img, const uint32_t * __restrict__ bits, int G,               \
+    const float * __restrict__ bg, float * __restrict__ colors, float * __restrict__ depths,       \
+    float * __restrict__ last_trans, int32_t * __restrict__ kept, int32_t * __restrict__ len,      \
+    int n_rays, int S, float step, uint32_t T, int64_t level_stride, float t_thresh,               \
+    float density_shift, float t_shift
+
+template <int C, int F, bool POW2>
+__global__ __launch_bounds__(HShape<C>::kWaves * 64) void render_rays_head_kernel(
+  F2N_RENDER_PARAMS, float * __restrict__ state, int n_head)
+{
+  using H = HShape<C>;
+  using R = RShape<C>;
+  using FS = typename R::FS;
+  constexpr int L = C / F, kS1 = FS::kS1, kPitch = R::kPitch;
+  __shared__ __attribute__((aligned(16))) float lds_all[H::kLdsFloats];
+  float * lds_w = lds_all;
+  stage_fwd_weights<C, H::kWaves>(lds_w, p_w_h, p_b_h, p_w1, p_b1, p_w2, p_b2);
+  __syncthreads();
+
+  const int lane = lane_id();
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int q = lane >> 4, mq = lane & 15;  // the matrix layout: quarter, column of a 16-wide block
+  const int g = lane >> 3, m = lane & 7;    // the march's: ray of the wave, sample of the stride
+  float * wave_lds = lds_all + FS::kWFloats + wave * H::kWaveFloats;
+  __half * tile = reinterpret_cast<__half *>(wave_lds);
+  float * OUT = wave_lds + R::kTileFloats;
+  float * SHT = OUT + R::kOutFloats;  // [8 rays][16]
+  float * EMB = SHT + 8 * 16;         // [8 rays][16]
+  const float * wop = lds_w + lane;
+  const bool has_emb = (p_emb != nullptr) && (ray_img != nullptr);
+  const bool has_grid = bits != nullptr;
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  const float bias0 = p_b_h[0];
+  const bool hand_over = n_head < S;  // (then n_head is a multiple of 64)
+  const int k_end = hand_over ? n_head : S;
+  const int n_groups = (n_rays + 7) >> 3;
+
+  for (int w8 = (int)blockIdx.x * H::kWaves + wave; w8 < n_groups; w8 += (int)gridDim.x * H::kWaves) {
+    const int r_raw = (w8 << 3) + g;
+    const bool has_ray = r_raw < n_rays;
+    const int r = has_ray ? r_raw : n_rays - 1;  // (spare groups of the last wave: idle)
+    const RayFrame rf = load_ray(rays_o, rays_d, r);
+    const float * nrow = noise ? noise + (int64_t)r * S : nullptr;
+
+    // ---- once per ray group: SH16(dir) and the embedding row of the 8 rays, for the columns to read
+    wave_lds_sync();  // (the previous group's last reads stay in front)
+    {
+      float sh[16];
+      sh_basis<4>(rf.dx, rf.dy, rf.dz, sh);
+      if (m == 0) {
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+          const f32x4 v = {sh[4 * t], sh[4 * t + 1], sh[4 * t + 2], sh[4 * t + 3]};
+          *reinterpret_cast<f32x4 *>(SHT + g * 16 + 4 * t) = v;
+        }
+      }
+      if (has_emb && m < 4)
+        *reinterpret_cast<f32x4 *>(EMB + g * 16 + 4 * m) =
+          *reinterpret_cast<const f32x4 *>(p_emb + (int64_t)ray_img[r] * kOut1 + 4 * m);
+    }
+    wave_lds_sync();
+
+    HalfScan ns = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, ds = ns;
+    float lx = 0.f, ly = 0.f, lz = 0.f;  // last sample point of the previous stride
+    float comp_carry = 0.f;              // the compositing optical depth (head logit), per ray
+    float cr = 0.f, cg = 0.f, cb = 0.f, cd = 0.f;
+    int n_kept = 0, n_len = 0;
+    bool done = !has_ray;
+    for (int k0 = 0; k0 < k_end; k0 += 8) {
+      // ---- 1. sample and test: density_march8_kernel's stride
+      const int j = (k0 >> 4) & 3, h = (k0 >> 3) & 1;
+      const int k = k0 + m;
+      const bool valid = k < S;
+      float cum, dummy;
+      if (nrow) {
+        const float nz = valid ? nrow[k] : 0.f;
+        cum = half_scan_step(nz, j, h, m, lane, ns, dummy);
+        if (j == 3 && h == 1) ns.carry = ns.carry + group_last(dummy, lane);  // (T3 + T2) + (T1 + T0)
+      } else {
+        cum = (float)(min(k, S - 1) + 1);
+      }
+      const float t = cum * step;
+      const float mx = rf.dx * t, my = rf.dy * t, mz = rf.dz * t;
+      const float px = rf.ox + mx, py = rf.oy + my, pz = rf.oz + mz;
+      const float sx = dpp_get<0x111, 0xf, 0xf>(px, 0.f), sy = dpp_get<0x111, 0xf, 0xf>(py, 0.f),
+                  sz = dpp_get<0x111, 0xf, 0xf>(pz, 0.f);  // (moved by all lanes, then selected)
+      const float qx = m >= 1 ? sx : lx, qy = m >= 1 ? sy : ly, qz = m >= 1 ? sz : lz;
+      const float ex = px - qx, ey = py - qy, ez = pz - qz;
+      const float dt = (k == 0) ? 0.f : sqrtf(fmaf(ez, ez, fmaf(ey, ey, ex * ex)));
+      lx = group_last(px, lane);
+      ly = group_last(py, lane);
+      lz = group_last(pz, lane);
+      float x = px, y = py, z = pz;
+      contract_point(x, y, z);
+      // finished, absent and unoccupied samples do not gather
+      const bool occ = valid && !done && (!has_grid || occ_test_contracted(x, y, z, bits, G));
+      const unsigned long long om = __ballot(occ);
+      // ---- 2. encode: the march's chain, and the values parked for the network
+      float sec = 0.f;
+      if (om != 0ull) {  // (wave-uniform)
+        if (occ) {       // (no cross-lane move inside)
+          float logit = bias0;
+#pragma unroll 1
+          for (int l = 0; l < L; l++) {
+            const LevelParams lp = load_level(primes, bias, mul, l);
+            uint32_t row[8];
+            float w[8], acc[F];
+            corner_rows_and_weights<POW2>(x, y, z, lp, T, row, w);
+            gather_blend<F>(table + level_stride * l, row, w, acc);
+#pragma unroll
+            for (int kk = 0; kk < F; kk++) {
+              __half hv;
+              logit = fmaf(round_f16_keep(acc[kk], hv), p_w_h[l * F + kk], logit);
+              tile[(l * F + kk) * kPitch + lane] = hv;
+            }
+          }
+          const float sigma = expf(logit - density_shift);
+          sec = sigma * dt;
+        }
+      }
+      // ---- 3. the keep decision, exactly the march's (unoccupied lanes feed 0.f, outside any branch)
+      float incl;
+      half_scan_step(sec, j, h, m, lane, ds, incl);
+      const float before = (j == 0 && h == 0) ? 0.f : ds.last;
+      const float shifted = dpp_get<0x111, 0xf, 0xf>(incl, 0.f);
+      const float prev = m >= 1 ? shifted : before;
+      const float depth = ds.carry + prev;
+      ds.last = group_last(incl, lane);
+      if (j == 3 && h == 1) ds.carry = ds.carry + ds.last;
+      const float trans_c = expf(-depth);
+      const bool keep = valid && !done && (trans_c > t_thresh);
+      const unsigned long long km = __ballot(keep);
+      const bool use = keep && occ;  // this lane's sample is one of its ray's list
+      if (!done) {
+        const int cnt = __popc((uint32_t)(km >> (8 * g)) & 0xffu);
+        n_len += cnt;
+        n_kept += __popc((uint32_t)((km & om) >> (8 * g)) & 0xffu);
+        if (cnt < min(8, S - k0)) done = true;  // the mask is a prefix: nothing later survives
+      }
+
+      if ((km & om) != 0ull) {  // (wave-uniform)
+        // ---- 4. the network on the 64 columns, Q-layout.  A column that did not gather holds
+        // whatever the tile held: it never leaves its own lane, and `use` drops it below.
+        wave_lds_sync();
+        f32x4 hh[4];
+#pragma unroll
+        for (int TT = 0; TT < 4; TT++) hh[TT] = *reinterpret_cast<const f32x4 *>(lds_w + FS::oBh + 4 * q);
+#pragma unroll
+        for (int t = 0; t < kS1; t++) {
+          const float a = wop[(FS::oWA1 + t) * 64];
+#pragma unroll
+          for (int TT = 0; TT < 4; TT++)
+            hh[TT] = mfma16(a, __half2float(tile[(q * kS1 + t) * kPitch + 16 * TT + mq]), hh[TT]);
+        }
+        if (q == 0) {
+#pragma unroll
+          for (int TT = 0; TT < 4; TT++) OUT[16 * TT + mq] = hh[TT][0];
+        }
+        // column 16 TT + mq is ray 2 TT + (mq >> 3) of the wave
+        f32x4 Xh[4], shv[4];
+#pragma unroll
+        for (int TT = 0; TT < 4; TT++) {
+          const int cray = 2 * TT + (mq >> 3);
+          shv[TT] = *reinterpret_cast<const f32x4 *>(SHT + cray * 16 + 4 * q);
+          Xh[TT] = hh[TT];
+          if (q == 0) Xh[TT][0] = 1.f;
+          if (has_emb) Xh[TT] += *reinterpret_cast<const f32x4 *>(EMB + cray * 16 + 4 * q);
+        }
+        f32x4 o[4];
+#pragma unroll
+        for (int TT = 0; TT < 4; TT++) {
+          o[TT] = zero4;
+          o[TT][0] = lds_w[FS::oB2 + q];
+        }
+#pragma unroll
+        for (int M = 0; M < 4; M++) {
+          f32x4 pre[4];
+          const f32x4 b1v = *reinterpret_cast<const f32x4 *>(lds_w + FS::oB1 + 16 * M + 4 * q);
+#pragma unroll
+          for (int TT = 0; TT < 4; TT++) pre[TT] = b1v;
+          // b1 + w1[:, 16:32] . SH(dir of the column's ray) first, as the one-ray form sums it
+#pragma unroll
+          for (int t = 4; t < 8; t++) {
+            const float a = wop[(FS::oWA2 + M * 8 + t) * 64];
+#pragma unroll
+            for (int TT = 0; TT < 4; TT++) pre[TT] = mfma16(a, shv[TT][t - 4], pre[TT]);
+          }
+#pragma unroll
+          for (int t = 0; t < 4; t++) {
+            const float a = wop[(FS::oWA2 + M * 8 + t) * 64];
+#pragma unroll
+            for (int TT = 0; TT < 4; TT++) pre[TT] = mfma16(a, Xh[TT][t], pre[TT]);
+          }
+#pragma unroll
+          for (int rr = 0; rr < 4; rr++) {
+            const float a = wop[(FS::oWA3 + M * 4 + rr) * 64];
+#pragma unroll
+            for (int TT = 0; TT < 4; TT++) o[TT] = mfma16(a, relu(pre[TT][rr]), o[TT]);
+          }
+        }
+        if (q < 3) {  // output rows 0, 4, 8 = the colours, in lanes of quarters 0, 1, 2
+#pragma unroll
+          for (int TT = 0; TT < 4; TT++) OUT[(1 + q) * 64 + 16 * TT + mq] = o[TT][0];
+        }
+        wave_lds_sync();
+        // ---- 5. compositing, per ray inside its 8-lane group
+        const float hl = OUT[lane];
+        const float o0 = OUT[64 + lane], o1 = OUT[128 + lane], o2 = OUT[192 + lane];
+        wave_lds_sync();  // (the next stride's tile and OUT writes stay behind these reads)
+        float sec2 = 0.f;
+        if (use) sec2 = expf(hl - density_shift) * dt;
+        const float incl2 = group_incl_scan(sec2, m);
+        const float sh2 = dpp_get<0x111, 0xf, 0xf>(incl2, 0.f);
+        const float trans = expf(-(comp_carry + (m >= 1 ? sh2 : 0.f)));
+        if (use) {
+          const float alpha = 1.f - expf(-sec2);
+          const float w = trans * alpha;
+          cr = fmaf(w, (1.f + 2.f * kEps) / (1.f + expf(-o0)) - kEps, cr);
+          cg = fmaf(w, (1.f + 2.f * kEps) / (1.f + expf(-o1)) - kEps, cg);
+          cb = fmaf(w, (1.f + 2.f * kEps) / (1.f + expf(-o2)) - kEps, cb);
+          cd = fmaf(w, t + t_shift, cd);
+        }
+        comp_carry += group_last(incl2, lane);
+      }
+      if (__ballot(!done) == 0ull) break;
+    }
+    // ---- 6. per ray: its outputs, or the state the tail resumes from
+    cr = group_sum(cr, m, lane);
+    cg = group_sum(cg, m, lane);
+    cb = group_sum(cb, m, lane);
+    cd = group_sum(cd, m, lane);
+    if (has_ray && m == 0) {
+      const bool pending = hand_over && !done;
+      if (!pending) {
+        const float tl = expf(-comp_carry);
+        last_trans[r] = tl;
+        colors[3 * r] = fmaf(tl, bg[3 * r], cr);
+        colors[3 * r + 1] = fmaf(tl, bg[3 * r + 1], cg);
+        colors[3 * r + 2] = fmaf(tl, bg[3 * r + 2], cb);
+        depths[r] = cd / (1.f - tl + 1e-4f);
+        kept[r] = n_kept;
+        if (len) len[r] = n_len;
+        if (hand_over) state[(int64_t)r * kStateWords] = __int_as_float(0);
+      } else {
+        f32x4 * st = reinterpret_cast<f32x4 *>(state + (int64_t)r * kStateWords);
+        const f32x4 s0 = {__int_as_float(1), ns.carry, lx, ly};
+        const f32x4 s1 = {lz, ds.carry, comp_carry, cr};
+        const f32x4 s2 = {cg, cb, cd, __int_as_float(n_kept)};
+        const f32x4 s3 = {__int_as_float(n_len), 0.f, 0.f, 0.f};
+        st[0] = s0;
+        st[1] = s1;
+        st[2] = s2;
+        st[3] = s3;
+      }
+    }
+  }
+}
+
+template <int C, int F, bool POW2>
+__global__ __launch_bounds__(RShape<C>::kWaves * 64) void render_rays_tail_kernel(
+  F2N_RENDER_PARAMS, const float * __restrict__ state, int n_head)
+{
+  using R = RShape<C>;
+  using FS = typename R::FS;
+  __shared__ __attribute__((aligned(16))) float lds_all[R::kLdsFloats];
+  float * lds_w = lds_all;
+  stage_fwd_weights<C, R::kWaves>(lds_w, p_w_h, p_b_h, p_w1, p_b1, p_w2, p_b2);
+  __syncthreads();
+
+  const int lane = lane_id();
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const bool has_emb = (p_emb != nullptr) && (ray_img != nullptr);
+  const bool has_grid = bits != nullptr;
+  const float bias0 = p_b_h[0];
+  const RenderArgs a = {rays_o, rays_d, noise,      table, primes,     bias,  mul, p_w_h,
+                        p_emb,  ray_img, bits,      G,     bg,         colors, depths, last_trans,
+                        kept,   len,     S,         step,  T,          level_stride, t_thresh,
+                        density_shift,   t_shift};
+  __half * tile = reinterpret_cast<__half *>(lds_all + FS::kWFloats + wave * R::kWaveFloats);
+  float * OUT = lds_all + FS::kWFloats + wave * R::kWaveFloats + R::kTileFloats;
+
+  for (int r = (int)blockIdx.x * R::kWaves + wave; r < n_rays; r += (int)gridDim.x * R::kWaves) {
+    // (r lives in scalar registers: the state is fetched with scalar loads, the skip is wave-uniform)
+    const float * st = state + (int64_t)r * kStateWords;
+    if (__float_as_int(st[0]) == 0) continue;
+    const RayResume rs = {n_head, {st[1], st[2], st[3], st[4]}, st[5], st[6], st[7], st[8], st[9],
+                          st[10], __float_as_int(st[11]), __float_as_int(st[12])};
+    render_one_ray<C, F, POW2>(a, r, rs, lds_w, tile, OUT, lane, has_emb, has_grid, bias0);
+  }
+}
+
+inline bool is_pow2(uint32_t v) { return v && !(v & (v - 1u)); }
+
+// the checks of f2n_render_rays, then the head's own: F2N_OK + *launch = false means nothing to do
+int check_args(
+  const float * rays_o, const float * rays_d, const uint16_t * table, const int32_t * primes,
+  const float * bias, const float * mul, const float * w_h, const float * b_h, const float * w1,
+  const float * b1, const float * w2, const float * b2, const float * app_emb,
+  const int32_t * ray_img, const uint32_t * occ_bits, int G, const float * bg, const float * colors,
+  const float * depths, const float * last_trans, const int32_t * kept, int n_rays, int S, int L,
+  int F, uint32_t T, int64_t level_stride, int n_head, const void * state, bool * launch)
+{
+  *launch = false;
+  if (n_rays < 0 || S < 1 || L < 1 || T < 1 || level_stride < 0) return F2N_E_INVALID_ARG;
+  if (F != 1 && F != 2 && F != 4 && F != 8) return F2N_E_UNSUPPORTED;
+  const int64_t C = (int64_t)L * F;
+  if (C != 8 && C != 16 && C != 32 && C != 64) return F2N_E_UNSUPPORTED;
+  if (L > F2N_MAX_LEVELS) return F2N_E_UNSUPPORTED;  // (C = 64 at F = 1)
+  if (level_stride % F) return F2N_E_INVALID_ARG;
+  if (occ_bits && !f2n_occ_res_ok(G)) return F2N_E_INVALID_ARG;
+  if ((app_emb == nullptr) != (ray_img == nullptr)) return F2N_E_INVALID_ARG;
+  // the head ends on a block boundary of the 64-lane scan, or takes the whole ray
+  if (n_head < 1 || (n_head < S && n_head % 64 != 0)) return F2N_E_INVALID_ARG;
+  if (n_head < S && !state) return F2N_E_INVALID_ARG;
+  if (state && (reinterpret_cast<uintptr_t>(state) & 15u)) return F2N_E_INVALID_ARG;
+  if (n_rays == 0) return F2N_OK;
+  if (!rays_o || !rays_d || !table || !primes || !bias || !mul || !w_h || !b_h || !w1 || !b1 ||
+      !w2 || !b2 || !bg || !colors || !depths || !last_trans || !kept)
+    return F2N_E_INVALID_ARG;
+  if (reinterpret_cast<uintptr_t>(table) % (2u * F)) return F2N_E_INVALID_ARG;
+  if (app_emb && (reinterpret_cast<uintptr_t>(app_emb) & 15u)) return F2N_E_INVALID_ARG;
+  *launch = true;
+  return F2N_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t f2n_render_rays_state_bytes(int n_rays)
+{
+  return n_rays < 0 ? -1 : (int64_t)n_rays * kStateWords * 4;
+}
+
+#define F2N_HT_DISPATCH(LAUNCH)                        \
+  switch ((int)(L * F)) {                              \
+    case 8: F2N_HT_C(LAUNCH, 8, F2N_HT_F1(LAUNCH, 8)) break;    \
+    case 16: F2N_HT_C(LAUNCH, 16, F2N_HT_F1(LAUNCH, 16)) break; \
+    case 32: F2N_HT_C(LAUNCH, 32, F2N_HT_F1(LAUNCH, 32)) break; \
+    default: F2N_HT_C(LAUNCH, 64, ) break;             \
+  }
+#define F2N_HT_F(LAUNCH, CC, FF) \
+  if (p2) LAUNCH(CC, FF, true)   \
+  else LAUNCH(CC, FF, false)
+#define F2N_HT_C(LAUNCH, CC, CASE_F1)                  \
+  switch (F) {                                         \
+    CASE_F1                                            \
+    case 2: F2N_HT_F(LAUNCH, CC, 2) break;             \
+    case 4: F2N_HT_F(LAUNCH, CC, 4) break;             \
+    default: F2N_HT_F(LAUNCH, CC, 8) break;            \
+  }
+#define F2N_HT_F1(LAUNCH, CC) case 1: F2N_HT_F(LAUNCH, CC, 1) break;
+
+#define F2N_KARGS                                                                                  \
+  rays_o, rays_d, noise, table, primes, bias, mul, w_h, b_h, w1, b1, w2, b2, app_emb, ray_img,     \
+    occ_bits, G, bg, colors, depths, last_trans, kept, len, n_rays, S, step, T, level_stride,      \
+    t_thresh, density_shift, t_shift
+
+extern "C" int f2n_render_rays_head(
+  const float * rays_o, const float * rays_d, const float * noise, const uint16_t * table,
+  const int32_t * primes, const float * bias, const float * mul, const float * w_h,
+  const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
+  const float * app_emb, const int32_t * ray_img, const uint32_t * occ_bits, int G, const float * bg,
+  float * colors, float * depths, float * last_trans, int32_t * kept, int32_t * len, int n_rays,
+  int S, float step, int L, int F, uint32_t T, int64_t level_stride, float t_thresh,
+  float density_shift, float t_shift, int n_head, void * state, void * stream)
+{
+  bool launch;
+  const int st = check_args(
+    rays_o, rays_d, table, primes, bias, mul, w_h, b_h, w1, b1, w2, b2, app_emb, ray_img, occ_bits,
+    G, bg, colors, depths, last_trans, kept, n_rays, S, L, F, T, level_stride, n_head, state,
+    &launch);
+  if (st != F2N_OK || !launch) return st;
+  hipStream_t s = (hipStream_t)stream;
+  const bool p2 = is_pow2(T);
+  // persistent workgroups, 12 waves of 8 rays each, one per CU
+#define F2N_HEAD(CC, FF, P2)                                                                       \
+  {                                                                                                \
+    using H = HShape<CC>;                                                                          \
+    const unsigned grid = std::min<unsigned>(f2n_div_up(f2n_div_up(n_rays, 8), H::kWaves), 256u);  \
+    hipLaunchKernelGGL(                                                                            \
+      (render_rays_head_kernel<CC, FF, P2>), dim3(grid), dim3(H::kWaves * 64), 0, s, F2N_KARGS,    \
+      static_cast<float *>(state), n_head);                                                        \
+  }
+  F2N_HT_DISPATCH(F2N_HEAD)
+#undef F2N_HEAD
+  return f2n_launch_status();
+}
+
+extern "C" int f2n_render_rays_tail(
+  const float * rays_o, const float * rays_d, const float * noise, const uint16_t * table,
+  const int32_t * primes, const float * bias, const float * mul, const float * w_h,
+  const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
+  const float * app_emb, const int32_t * ray_img, const uint32_t * occ_bits, int G, const float * bg,
+  float * colors, float * depths, float * last_trans, int32_t * kept, int32_t * len, int n_rays,
+  int S, float step, int L, int F, uint32_t T, int64_t level_stride, float t_thresh,
+  float density_shift, float t_shift, int n_head, const void * state, void * stream)
+{
+  bool launch;
+  const int st = check_args(
+    rays_o, rays_d, table, primes, bias, mul, w_h, b_h, w1, b1, w2, b2, app_emb, ray_img, occ_bits,
+    G, bg, colors, depths, last_trans, kept, n_rays, S, L, F, T, level_stride, n_head, state,
+    &launch);
+  if (st != F2N_OK || !launch) return st;
+  if (n_head >= S) return F2N_OK;  // the head rendered every ray whole: nothing is pending
+  hipStream_t s = (hipStream_t)stream;
+  const bool p2 = is_pow2(T);
+#define F2N_TAIL(CC, FF, P2)                                                                       \
+  {                                                                                                \
+    using R = RShape<CC>;                                                                          \
+    const unsigned grid = std::min<unsigned>(f2n_div_up(n_rays, R::kWaves), 512u);                 \
+    hipLaunchKernelGGL(                                                                            \
+      (render_rays_tail_kernel<CC, FF, P2>), dim3(grid), dim3(R::kWaves * 64), 0, s, F2N_KARGS,    \
+      static_cast<const float *>(state), n_head);                                                  \
+  }
+  F2N_HT_DISPATCH(F2N_TAIL)
+#undef F2N_TAIL
+  return f2n_launch_status();
+}

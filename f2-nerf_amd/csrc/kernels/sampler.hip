@@ -387,68 +387,8 @@ __global__ __launch_bounds__(F2N_BLOCK) void density_march16_kernel(
 // the second half needs, for its first lanes, what the first half's lanes 7 / 6,7 / 4..7 held after
 // steps 0 / 1 / 2 (kept in registers, fetched with row_shl) and adds the first half's own result at
 // step 8.  Same counts, bit for bit (tests/test_gpu_fused.py).
-struct HalfScan
-{
-  float carry, t0, t1p, t2, last;  // as RowScan
-  float pv, pa, pb, pc;            // the first half's values after steps 0, 1, 2, 4 (per lane)
-};
-
-// lane 7 of the own 8-lane group in every lane of the group
-__device__ __forceinline__ float group_last(float v, int lane)
-{
-  const float lo = dpp_get<0x157, 0xf, 0xf>(v, 0.f), hi = dpp_get<0x15F, 0xf, 0xf>(v, 0.f);
-  return (lane & 8) ? hi : lo;
-}
-
-// value after the row scan (16 lanes of the 64-lane scan) of the element this lane holds: m = lane
-// within the group = lane within the half row, h = which half of the row this stride is
-__device__ __forceinline__ float half_row_scan(float v, int m, int h, HalfScan & st)
-{
-  // (every DPP move is executed by ALL lanes and selected afterwards: inside a conditional
-  // expression it would run with the other lanes switched off, and a lane that reads a switched-off
-  // lane gets the fill value)
-  float a, b, c;
-  if (h == 0) {  // (wave-uniform)
-    const float s1 = dpp_get<0x111, 0xf, 0xf>(v, 0.f);
-    a = v + (m >= 1 ? s1 : 0.f);
-    const float s2 = dpp_get<0x112, 0xf, 0xf>(a, 0.f);
-    b = a + (m >= 2 ? s2 : 0.f);
-    const float s4 = dpp_get<0x114, 0xf, 0xf>(b, 0.f);
-    c = b + (m >= 4 ? s4 : 0.f);
-    st.pv = v;
-    st.pa = a;
-    st.pb = b;
-    st.pc = c;
-    return c;
-  }
-  const float s1 = dpp_get<0x111, 0xf, 0xf>(v, 0.f), f1 = dpp_get<0x107, 0xf, 0xf>(st.pv, 0.f);
-  a = v + (m >= 1 ? s1 : f1);
-  const float s2 = dpp_get<0x112, 0xf, 0xf>(a, 0.f), f2 = dpp_get<0x106, 0xf, 0xf>(st.pa, 0.f);
-  b = a + (m >= 2 ? s2 : f2);
-  const float s4 = dpp_get<0x114, 0xf, 0xf>(b, 0.f), f4 = dpp_get<0x104, 0xf, 0xf>(st.pb, 0.f);
-  c = b + (m >= 4 ? s4 : f4);
-  return c + st.pc;
-}
-
-// as row_scan_step, for half j * 2 + h of the 64-sample block
-__device__ __forceinline__ float half_scan_step(
-  float v, int j, int h, int m, int lane, HalfScan & st, float & incl_in_block)
-{
-  const float rs = half_row_scan(v, m, h, st);
-  float inner;
-  if (j == 0) inner = rs;
-  else if (j == 1) inner = rs + st.t0;
-  else if (j == 2) inner = rs + st.t1p;
-  else inner = (rs + st.t2) + st.t1p;
-  if (h == 1) {  // the row is complete: its total
-    const float tj = group_last(rs, lane);
-    if (j == 0) st.t0 = tj;
-    else if (j == 1) st.t1p = tj + st.t0;
-    else if (j == 2) st.t2 = tj;
-  }
-  incl_in_block = inner;
-  return st.carry + inner;
-}
+// (HalfScan, group_last, half_row_scan and half_scan_step live in sampler.hiph: render_rays_head.hip
+// walks its rays with the same helpers)
 
 template <int F, bool POW2>
 __global__ __launch_bounds__(F2N_BLOCK) void density_march8_kernel(

@@ -579,6 +579,56 @@ int f2n_render_rays(
   int n_rays, int S, float step, int L, int F, uint32_t T, int64_t level_stride,
   float t_thresh, float density_shift, float t_shift, void * stream);
 
+/* f2n_render_rays where rays are short, in two launches that still read nothing back.  Replaces the
+ * same sites: src/renderer.cpp:33-123 as used by src/renderer.cpp:125-151 and src/localizer.cpp:172.
+ *
+ * f2n_render_rays_head renders the first n_head samples of every ray EIGHT rays to a wavefront (a ray
+ * owns 8 lanes, strides of 8 samples, f2n_density_march's default mapping): a ray that stops after
+ * three samples costs an eighth of a wavefront's stride, not a whole one.  kept and len are still
+ * f2n_density_march's / f2n_density_march_occ's bit for bit; colours, depths and last_trans agree
+ * with f2n_render_rays to rounding (the same terms; the sums inside a stride in another order).  A
+ * ray that ends inside the head gets its outputs; a ray still alive at sample n_head gets none yet:
+ * its state goes to `state` and it is marked pending.
+ * f2n_render_rays_tail resumes the pending rays at sample n_head in f2n_render_rays's one-ray form
+ * and writes their outputs; the others are skipped.  Same arguments as the head, after it on the
+ * same stream.
+ *   n_head  a multiple of 64 (the block boundary of the 64-lane scan, where both forms' carries are
+ *           the same bits), or any value >= S: the whole ray in the short form, no state written,
+ *           state may be NULL and the tail is a no-op.  Anything else: F2N_E_INVALID_ARG.
+ *   state   f2n_render_rays_state_bytes(n_rays) bytes, 16-byte aligned: 64 bytes per ray,
+ *           16 words: [0] int32 pending, [1] cumulative noise, [2..4] last sample point, [5] the
+ *           march's optical depth, [6] the compositing optical depth, [7..10] partial r, g, b, depth,
+ *           [11] int32 kept, [12] int32 len, [13..15] unused.  NULL with n_head < S:
+ *           F2N_E_INVALID_ARG.  Written by the head in full before the tail reads it: no need to
+ *           clear it.
+ * Everything else as f2n_render_rays.  No atomics, no other workspace: two runs give the same bits. */
+int64_t f2n_render_rays_state_bytes(int n_rays);
+int f2n_render_rays_head(
+  const float * rays_o, const float * rays_d, const float * noise /* [n_rays,S] or NULL */,
+  const uint16_t * table, const int32_t * primes, const float * bias, const float * mul,
+  const float * w_h, const float * b_h, const float * w1, const float * b1,
+  const float * w2, const float * b2,
+  const float * app_emb, const int32_t * ray_img /* both NULL: no appearance embedding */,
+  const uint32_t * occ_bits /* NULL: no grid */, int G,
+  const float * bg, float * colors, float * depths, float * last_trans,
+  int32_t * kept, int32_t * len /* may be NULL */,
+  int n_rays, int S, float step, int L, int F, uint32_t T, int64_t level_stride,
+  float t_thresh, float density_shift, float t_shift, int n_head, void * state, void * stream);
+/* The second launch (see above): the rest of src/renderer.cpp:33-123 for the rays that are still alive
+ * after n_head samples, as src/renderer.cpp:125-151 and src/localizer.cpp:172 use it. */
+int f2n_render_rays_tail(
+  const float * rays_o, const float * rays_d, const float * noise /* [n_rays,S] or NULL */,
+  const uint16_t * table, const int32_t * primes, const float * bias, const float * mul,
+  const float * w_h, const float * b_h, const float * w1, const float * b1,
+  const float * w2, const float * b2,
+  const float * app_emb, const int32_t * ray_img /* both NULL: no appearance embedding */,
+  const uint32_t * occ_bits /* NULL: no grid */, int G,
+  const float * bg, float * colors, float * depths, float * last_trans,
+  int32_t * kept, int32_t * len /* may be NULL */,
+  int n_rays, int S, float step, int L, int F, uint32_t T, int64_t level_stride,
+  float t_thresh, float density_shift, float t_shift, int n_head, const void * state,
+  void * stream);
+
 /* ------------------------------------------------------------------ optimiser (section 8f) ----- */
 
 /* One fused pass of torch::optim::Adam::step() over one f32 parameter tensor -- the call at

@@ -15,8 +15,13 @@ process under its own time limit, and a child that fails ends the run.  --profil
 `rocprofv3 --kernel-trace --stats` run of shape a in a fresh child.  One JSON line per shape and arm;
 --out appends them to a file.
 
+--head 0,64,-1 adds arms for RendererOptions::one_pass_head (0: the one-launch kernel again, 64: the
+first 64 samples eight rays to a wavefront and the survivors one wavefront each, -1: whole rays eight to
+a wavefront); all arms -- off, on, and these -- alternate call by call, and the lines are appended to
+profiles/render_rays_head_ab.jsonl unless --out names another file.
+
   python tools/microbench_render_rays.py [--shapes a,b,c] [--reps 5] [--warmup 2] [--out FILE]
-                                         [--profile DIR]
+                                         [--head 0,64,-1] [--profile DIR]
 """
 import argparse
 import importlib
@@ -36,12 +41,20 @@ def _median(v):
     return sorted(v)[len(v) // 2]
 
 
+HEADS = []   # --head: further arms "head=<n>" after "off" and "on"
+
+
+def _arms():
+    return ["off", "on"] + ["head=%d" % h for h in HEADS]
+
+
 def _ab(torch, hr, fn, reps, warmup):
-    """{arm: [ms, ...]} with the two arms alternating call by call"""
-    ms = {"off": [], "on": []}
+    """{arm: [ms, ...]} with the arms alternating call by call"""
+    ms = {arm: [] for arm in _arms()}
     for it in range(warmup + reps):
-        for arm in ("off", "on"):
-            hr.set_one_pass(arm == "on")
+        for arm in _arms():
+            hr.set_one_pass(arm != "off")
+            hr.set_one_pass_head(int(arm[5:]) if arm.startswith("head=") else 0)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             fn()
@@ -49,12 +62,13 @@ def _ab(torch, hr, fn, reps, warmup):
             if it >= warmup:
                 ms[arm].append((time.perf_counter() - t0) * 1e3)
     hr.set_one_pass(False)
+    hr.set_one_pass_head(0)
     return ms
 
 
 def _lines(shape, what, n_rays, S, ms, extra):
     out = []
-    for arm in ("off", "on"):
+    for arm in _arms():
         med = _median(ms[arm])
         out.append(json.dumps(dict(
             shape=shape, what=what, one_pass=arm, rays=n_rays, samples_per_ray=S,
@@ -125,13 +139,21 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default="")
+    ap.add_argument("--head", default="", metavar="N,N,..",
+                    help="further arms: one_pass with one_pass_head = N (0, -1 or a multiple of 64)")
     ap.add_argument("--profile", default="", metavar="DIR",
                     help="also one rocprofv3 --kernel-trace --stats run of shape a into DIR")
     args = ap.parse_args()
+    HEADS[:] = [int(v) for v in args.head.split(",") if v]
     if args.shape:
         run_shape(args.shape, args.reps, args.warmup)
         return 0
     me = [sys.executable, os.path.abspath(__file__), "--reps", str(args.reps), "--warmup", str(args.warmup)]
+    if HEADS:
+        me += ["--head=" + args.head]
+        if not args.out:
+            args.out = os.path.join(ROOT, "profiles", "render_rays_head_ab.jsonl")
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     for shape in args.shapes.split(","):
         res = subprocess.run(["timeout", "-k", "10", str(CHILD_TIMEOUT_S), *me, "--shape", shape],
                              cwd=ROOT, stdout=subprocess.PIPE, text=True)
