@@ -161,6 +161,18 @@ Tensor Hash3DAnchored::table_for(const Tensor & feat_pool)
   return t16;
 }
 
+f2n::FieldArgs Hash3DAnchored::kernel_args(const Tensor & table16) const
+{
+  return {reinterpret_cast<const uint16_t *>(table16.data_ptr()),
+          prim_pool_.data_ptr<int32_t>(),
+          bias_pool_.data_ptr<float>(),
+          level_mul_.data_ptr<float>(),
+          (int)options_.n_levels,
+          (int)options_.n_channels,
+          (uint32_t)local_size_,
+          level_stride_};
+}
+
 std::pair<Tensor, Tensor> Hash3DAnchored::density_head() const
 {
   return {mlp_->weight.detach().select(0, 0).contiguous(),
@@ -231,6 +243,7 @@ variable_list Hash3DAnchoredFunction::forward(
   const int L = (int)field->options_.n_levels, F = (int)field->options_.n_channels;
   if (info->precomputed_cm_.defined()) return {info->precomputed_cm_.t()};
   Tensor table16 = field->table_for(feat_pool);
+  const f2n::FieldArgs g = field->kernel_args(table16);
   // f32 tensor holding f16-rounded values (the reference's out_feat.to(kFloat32), fused).  Storage
   // is channel-major [L*F, n] -- every wavefront store is one coalesced 256-byte row segment instead
   // of 64 scattered 8-byte pieces (2.5x faster encode on MI355X) -- and the caller receives the
@@ -242,18 +255,14 @@ variable_list Hash3DAnchoredFunction::forward(
     if (spr > 0 && spr % 16 == 0 && n % spr == 0 && n / spr <= INT32_MAX) {
       f2n::check(
         f2n_hash_fwd_raytile(
-          points.data_ptr<float>(), reinterpret_cast<const uint16_t *>(table16.data_ptr()),
-          field->prim_pool_.data_ptr<int32_t>(), field->bias_pool_.data_ptr<float>(),
-          field->level_mul_.data_ptr<float>(), out_cm.data_ptr<float>(), (int)(n / spr), (int)spr, L,
-          F, (uint32_t)field->local_size_, field->level_stride_, f2n::current_stream(points)),
+          points.data_ptr<float>(), g.table, g.primes, g.bias, g.mul, out_cm.data_ptr<float>(),
+          (int)(n / spr), (int)spr, g.L, g.F, g.T, g.level_stride, f2n::current_stream(points)),
         "f2n_hash_fwd_raytile");
     } else {
       f2n::check(
         f2n_hash_fwd(
-          points.data_ptr<float>(), reinterpret_cast<const uint16_t *>(table16.data_ptr()),
-          field->prim_pool_.data_ptr<int32_t>(), field->bias_pool_.data_ptr<float>(),
-          field->level_mul_.data_ptr<float>(), out_cm.data_ptr<float>(), 1, n, nullptr, n, L, F,
-          (uint32_t)field->local_size_, field->level_stride_, f2n::current_stream(points)),
+          points.data_ptr<float>(), g.table, g.primes, g.bias, g.mul, out_cm.data_ptr<float>(), 1, n,
+          nullptr, n, g.L, g.F, g.T, g.level_stride, f2n::current_stream(points)),
         "f2n_hash_fwd");
     }
   }
@@ -278,6 +287,7 @@ variable_list Hash3DAnchoredFunction::backward(AutogradContext * ctx, variable_l
   const auto [grad_in, ld_point, ld_chan] =
     f2n::encoding_grad_strides(grad_output[0], n, (int64_t)L * F);
   Tensor table16 = field->table_for(feat_pool);
+  const f2n::FieldArgs g = field->kernel_args(table16);
   // points need a gradient only for pose optimisation; training rays are data
   const bool want_points = ctx->needs_input_grad(0);
   Tensor points_grad = want_points ? torch::empty({n, 3}, points.options()) : Tensor();
@@ -300,7 +310,7 @@ variable_list Hash3DAnchoredFunction::backward(AutogradContext * ctx, variable_l
   // capped at 64 GiB: bigger batches run in rounds); it is further capped at half of the device's
   // free memory, and when even that cannot be allocated the atomic kernel takes over.
   int64_t ws_bytes =
-    want_points ? 0 : f2n_hash_bwd_workspace_bytes(n, L, F, (uint32_t)field->local_size_);
+    want_points ? 0 : f2n_hash_bwd_workspace_bytes(n, L, F, g.T);
   Tensor ws;
   if (ws_bytes > 0 && field->options_.binned_backward) {
     size_t free_b = 0, total_b = 0;
@@ -324,11 +334,9 @@ variable_list Hash3DAnchoredFunction::backward(AutogradContext * ctx, variable_l
   if (ws.defined()) {
     f2n::ScopedKernelTimer timer("hash_bwd", stream, (double)n);
     const int st = f2n_hash_bwd_binned(
-      points.data_ptr<float>(), field->prim_pool_.data_ptr<int32_t>(),
-      field->bias_pool_.data_ptr<float>(), field->level_mul_.data_ptr<float>(),
-      grad_in.data_ptr<float>(), ld_point, ld_chan, embeds_grad.data_ptr<float>(), n, L, F,
-      (uint32_t)field->local_size_, field->level_stride_, grad_scale, ws.data_ptr(), ws_bytes,
-      stream);
+      points.data_ptr<float>(), g.primes, g.bias, g.mul, grad_in.data_ptr<float>(), ld_point,
+      ld_chan, embeds_grad.data_ptr<float>(), n, g.L, g.F, g.T, g.level_stride, grad_scale,
+      ws.data_ptr(), ws_bytes, stream);
     if (st != F2N_E_UNSUPPORTED) f2n::check(st, "f2n_hash_bwd_binned");
     done = (st == F2N_OK);  // unsupported = the (shrunk) workspace holds not even one tile
   }
@@ -336,11 +344,10 @@ variable_list Hash3DAnchoredFunction::backward(AutogradContext * ctx, variable_l
     f2n::ScopedKernelTimer timer("hash_bwd", stream, (double)n);
     f2n::check(
       f2n_hash_bwd(
-        points.data_ptr<float>(), reinterpret_cast<const uint16_t *>(table16.data_ptr()),
-        field->prim_pool_.data_ptr<int32_t>(), field->bias_pool_.data_ptr<float>(),
-        field->level_mul_.data_ptr<float>(), grad_in.data_ptr<float>(), ld_point, ld_chan,
-        embeds_grad.data_ptr<float>(), want_points ? points_grad.data_ptr<float>() : nullptr, n, L,
-        F, (uint32_t)field->local_size_, field->level_stride_, grad_scale, stream),
+        points.data_ptr<float>(), g.table, g.primes, g.bias, g.mul, grad_in.data_ptr<float>(),
+        ld_point, ld_chan, embeds_grad.data_ptr<float>(),
+        want_points ? points_grad.data_ptr<float>() : nullptr, n, g.L, g.F, g.T, g.level_stride,
+        grad_scale, stream),
       "f2n_hash_bwd");
   }
   return {points_grad, in_place ? Tensor() : embeds_grad, Tensor()};

@@ -35,6 +35,23 @@ struct Hash3DAnchoredOptions
   torch::Device device = f2n::default_device();
 };
 
+namespace f2n
+{
+
+// The grid as every kernel entry of f2nerf_hip.h that walks it takes it (table, primes, bias, mul,
+// ..., L, F, T, level_stride), already cast.  Pointers into tensors the caller keeps alive.
+struct FieldArgs
+{
+  const uint16_t * table;
+  const int32_t * primes;
+  const float *bias, *mul;
+  int L, F;
+  uint32_t T;
+  int64_t level_stride;
+};
+
+}  // namespace f2n
+
 class Hash3DAnchored : public torch::nn::Module
 {
   using Tensor = torch::Tensor;
@@ -67,6 +84,8 @@ public:
   Tensor table_f16();
   // f16 copy of an arbitrary table tensor (the shadow when it is feat_pool_ itself).
   Tensor table_for(const Tensor & feat_pool);
+  // The grid for a kernel call, over `table16` (what table_f16() / table_for() returned).
+  f2n::FieldArgs kernel_args(const Tensor & table16) const;
 
   // For an optimiser that rewrites the shadow itself while updating feat_pool_ (FusedAdam): the
   // shadow buffer (allocated on demand), and the call that declares it current.

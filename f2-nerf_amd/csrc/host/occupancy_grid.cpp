@@ -24,15 +24,14 @@ void OccupancyGrid::update(Hash3DAnchored & field, float threshold, float decay,
     u = f2n::dev_f32(probe.detach(), "probe");
   }
   Tensor table16 = field.table_f16();
+  const f2n::FieldArgs g = field.kernel_args(table16);
   auto head = field.density_head();
   f2n::check(
     f2n_occ_update(
-      reinterpret_cast<const uint16_t *>(table16.data_ptr()), field.prim_pool_.data_ptr<int32_t>(),
-      field.bias_pool_.data_ptr<float>(), field.level_mul_.data_ptr<float>(),
-      head.first.data_ptr<float>(), head.second.data_ptr<float>(), f2n::fptr(u),
-      density_.data_ptr<float>(), reinterpret_cast<uint32_t *>(words_.data_ptr<int32_t>()), (int)G_,
-      (int)field.options_.n_levels, (int)field.options_.n_channels, (uint32_t)field.local_size_,
-      field.level_stride_, 3.f, threshold, decay, f2n::current_stream(words_)),
+      g.table, g.primes, g.bias, g.mul, head.first.data_ptr<float>(), head.second.data_ptr<float>(),
+      f2n::fptr(u), density_.data_ptr<float>(),
+      reinterpret_cast<uint32_t *>(words_.data_ptr<int32_t>()), (int)G_, g.L, g.F, g.T,
+      g.level_stride, 3.f, threshold, decay, f2n::current_stream(words_)),
     "f2n_occ_update");
 }
 

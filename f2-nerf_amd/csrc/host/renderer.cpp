@@ -181,19 +181,16 @@ public:
         Hash3DAnchored * field =
           ctx->saved_data["hash3d_info"].toCustomClass<Hash3DAnchoredInfo>()->hash3d_;
         const int64_t n = pts.size(0);
-        const int L = (int)field->options_.n_levels, F = (int)field->options_.n_channels;
-        const auto [g, ld_point, ld_chan] = f2n::encoding_grad_strides(g_enc, n, (int64_t)L * F);
+        const f2n::FieldArgs fa = field->kernel_args(table16);
+        const auto [g, ld_point, ld_chan] = f2n::encoding_grad_strides(g_enc, n, (int64_t)fa.L * fa.F);
         void * stream = f2n::current_stream(pts);
         f2n::ScopedKernelTimer timer("hash_rays_grad", stream, (double)n);
         f2n::check(
           f2n_hash_rays_grad(
             pts.data_ptr<float>(), t.data_ptr<float>(), bounds.data_ptr<int32_t>(),
-            rays_d.data_ptr<float>(), reinterpret_cast<const uint16_t *>(table16.data_ptr()),
-            field->prim_pool_.data_ptr<int32_t>(), field->bias_pool_.data_ptr<float>(),
-            field->level_mul_.data_ptr<float>(), g.data_ptr<float>(), ld_point, ld_chan,
-            d_o.data_ptr<float>(), d_d.data_ptr<float>(), (int)n_rays, L, F,
-            (uint32_t)field->local_size_, field->level_stride_, 128.f /* hash_3d_anchored.cu:190 */,
-            stream),
+            rays_d.data_ptr<float>(), fa.table, fa.primes, fa.bias, fa.mul, g.data_ptr<float>(),
+            ld_point, ld_chan, d_o.data_ptr<float>(), d_d.data_ptr<float>(), (int)n_rays, fa.L, fa.F,
+            fa.T, fa.level_stride, 128.f /* hash_3d_anchored.cu:190 */, stream),
           "f2n_hash_rays_grad");
       }
     }
@@ -382,6 +379,7 @@ RenderResult Renderer::render_fused(
     // First pass (renderer.cpp:58-90): density only, never differentiated by the loss.
     torch::NoGradGuard no_grad;
     Tensor table16 = field.table_f16();
+    const f2n::FieldArgs g = field.kernel_args(table16);
     auto head = field.density_head();
     Tensor counts = torch::empty({n_rays}, f2n::int_on(rays_o.device()));
     Tensor len;  // with a grid: the prefix lengths the counts were thinned from
@@ -392,26 +390,20 @@ RenderResult Renderer::render_fused(
       f2n::ScopedKernelTimer timer("density_march_occ", stream, (double)n_rays);
       f2n::check(
         f2n_density_march_occ(
-          rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), f2n::fptr(noise),
-          reinterpret_cast<const uint16_t *>(table16.data_ptr()),
-          field.prim_pool_.data_ptr<int32_t>(), field.bias_pool_.data_ptr<float>(),
-          field.level_mul_.data_ptr<float>(), head.first.data_ptr<float>(),
-          head.second.data_ptr<float>(), occupancy_->words_ptr(), (int)occupancy_->resolution(),
-          counts.data_ptr<int32_t>(), len.data_ptr<int32_t>(), n_rays, S,
-          pts_sampler_->options_.step, (int)field.options_.n_levels, (int)field.options_.n_channels,
-          (uint32_t)field.local_size_, field.level_stride_, options_.early_stop_trans, 3.f, stream),
+          rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), f2n::fptr(noise), g.table, g.primes,
+          g.bias, g.mul, head.first.data_ptr<float>(), head.second.data_ptr<float>(),
+          occupancy_->words_ptr(), (int)occupancy_->resolution(), counts.data_ptr<int32_t>(),
+          len.data_ptr<int32_t>(), n_rays, S, pts_sampler_->options_.step, g.L, g.F, g.T,
+          g.level_stride, options_.early_stop_trans, 3.f, stream),
         "f2n_density_march_occ");
     } else {
       f2n::ScopedKernelTimer timer("density_march", stream, (double)n_rays);
       f2n::check(
       f2n_density_march(
-        rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), f2n::fptr(noise),
-        reinterpret_cast<const uint16_t *>(table16.data_ptr()), field.prim_pool_.data_ptr<int32_t>(),
-        field.bias_pool_.data_ptr<float>(), field.level_mul_.data_ptr<float>(),
-        head.first.data_ptr<float>(), head.second.data_ptr<float>(), counts.data_ptr<int32_t>(),
-        n_rays, S, pts_sampler_->options_.step, (int)field.options_.n_levels,
-        (int)field.options_.n_channels, (uint32_t)field.local_size_, field.level_stride_,
-        options_.early_stop_trans, 3.f, stream),
+        rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), f2n::fptr(noise), g.table, g.primes,
+        g.bias, g.mul, head.first.data_ptr<float>(), head.second.data_ptr<float>(),
+        counts.data_ptr<int32_t>(), n_rays, S, pts_sampler_->options_.step, g.L, g.F, g.T,
+        g.level_stride, options_.early_stop_trans, 3.f, stream),
       "f2n_density_march");
     }
     auto [bounds, total] = bounds_from_counts(counts, stream);
@@ -768,6 +760,7 @@ void Renderer::render_rays_into(
       occupancy_->words().device() == rays_o.device(), "the occupancy grid lives on another device");
   Hash3DAnchored & field = *scene_field_;
   const Tensor table16 = field.table_f16();
+  const f2n::FieldArgs g = field.kernel_args(table16);
   const Tensor w_h = f2n::dev_f32(field.mlp_->weight.detach(), "field head weight");
   const Tensor b_h = f2n::dev_f32(field.mlp_->bias.detach(), "field head bias");
   auto mlp = shader_->mlp_params();
@@ -789,17 +782,15 @@ void Renderer::render_rays_into(
   }
   f2n::ScopedKernelTimer timer("render_rays", stream, (double)n_rays);
 #define F2N_RENDER_RAYS_ARGS                                                                       \
-  rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), f2n::fptr(noise),                            \
-    reinterpret_cast<const uint16_t *>(table16.data_ptr()), field.prim_pool_.data_ptr<int32_t>(),  \
-    field.bias_pool_.data_ptr<float>(), field.level_mul_.data_ptr<float>(), w_h.data_ptr<float>(), \
-    b_h.data_ptr<float>(), w1.data_ptr<float>(), b1.data_ptr<float>(), w2.data_ptr<float>(),       \
+  rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), f2n::fptr(noise), g.table, g.primes, g.bias, \
+    g.mul, w_h.data_ptr<float>(), b_h.data_ptr<float>(), w1.data_ptr<float>(),                     \
+    b1.data_ptr<float>(), w2.data_ptr<float>(),                                                    \
     b2.data_ptr<float>(), f2n::fptr(emb), f2n::iptr(emb_idx),                                      \
     occupancy_ ? occupancy_->words_ptr() : nullptr,                                                \
     occupancy_ ? (int)occupancy_->resolution() : 0, bg.data_ptr<float>(),                          \
     colors.data_ptr<float>(), depths.data_ptr<float>(), last_trans.data_ptr<float>(),              \
-    kept.data_ptr<int32_t>(), nullptr, n_rays, S, pts_sampler_->options_.step,                     \
-    (int)field.options_.n_levels, (int)field.options_.n_channels, (uint32_t)field.local_size_,     \
-    field.level_stride_, options_.early_stop_trans, 3.f, 1e-2f
+    kept.data_ptr<int32_t>(), nullptr, n_rays, S, pts_sampler_->options_.step, g.L, g.F, g.T,      \
+    g.level_stride, options_.early_stop_trans, 3.f, 1e-2f
   if (head_opt == 0) {
     f2n::check(f2n_render_rays(F2N_RENDER_RAYS_ARGS, stream), "f2n_render_rays");
     return;

@@ -1378,8 +1378,6 @@ constexpr int64_t kRecommendedWorkspaceCap = (int64_t)64 << 30;
 std::atomic<uint32_t *> g_bin_stats{nullptr};
 std::atomic<unsigned long long *> g_overflow_counter{nullptr};
 
-inline bool is_pow2(uint32_t v) { return v && !(v & (v - 1u)); }
-
 }  // namespace
 
 // Measurement hook of tools/ab_hash_bwd.py (not part of the ABI header): a device buffer of
@@ -1406,15 +1404,6 @@ extern "C" int64_t f2n_hash_bwd_workspace_bytes(int64_t n, int L, int F, uint32_
   pl = bin_plan(n, L, F, T, kRecommendedWorkspaceCap);  // bigger batches run in several rounds
   return pl.ok ? pl.bytes : 0;
 }
-
-#define F2N_DISPATCH_F(F_, ...)      \
-  switch (F_) {                      \
-    case 1: { constexpr int FF = 1; __VA_ARGS__; } break; \
-    case 2: { constexpr int FF = 2; __VA_ARGS__; } break; \
-    case 4: { constexpr int FF = 4; __VA_ARGS__; } break; \
-    case 8: { constexpr int FF = 8; __VA_ARGS__; } break; \
-    default: return F2N_E_UNSUPPORTED; \
-  }
 
 extern "C" int f2n_hash_bwd_binned(
   const float * pts, const int32_t * primes, const float * bias, const float * mul,
@@ -1443,7 +1432,6 @@ extern "C" int f2n_hash_bwd_binned(
     pl.chunk_tiles = std::min(pl.chunk_tiles, max_tiles);
   }
   hipStream_t s = (hipStream_t)stream;
-  const bool p2 = is_pow2(T);
   const float inv = 1.f / grad_scale;
   const int combine = f2n_get_option(F2N_OPT_BWD_COMBINE) == 0 ? 1 : 0;
   // Level windows [stride*l, stride*l + T*F): where they do not overlap a slice owns its elements
@@ -1508,19 +1496,16 @@ extern "C" int f2n_hash_bwd_binned(
     ba.stats = g_bin_stats.load(std::memory_order_relaxed);
     ba.overflow = g_overflow_counter.load(std::memory_order_relaxed);
     const int64_t tiles_g = tiles * pl.groups;
-#define F2N_BIN_LAUNCH(P2, SAT)                                                                     \
+#define F2N_BIN_LAUNCH(SAT)                                                                        \
   hipLaunchKernelGGL(                                                                              \
     (hash_bwd_bin_kernel<FF, P2, SAT>), grid_a, block_a, 0, s, pts + 3 * p0, primes, bias, mul,    \
     grad_out + p0 * g_ld_point, table_grad, a_records, a_counts, ba)
     const dim3 grid_a((unsigned)tiles), block_a(kBinBlock);
-    F2N_DISPATCH_F(F, {
-      if (pl.log2_sub > 0) {
-        if (p2) F2N_BIN_LAUNCH(true, true);
-        else F2N_BIN_LAUNCH(false, true);
-      } else {
-        if (p2) F2N_BIN_LAUNCH(true, false);
-        else F2N_BIN_LAUNCH(false, false);
-      }
+    f2n_dispatch_field(F, T, [&](auto ff, auto p2) {
+      constexpr int FF = decltype(ff)::value;
+      constexpr bool P2 = decltype(p2)::value;
+      if (pl.log2_sub > 0) F2N_BIN_LAUNCH(true);
+      else F2N_BIN_LAUNCH(false);
       if (pl.log2_sub == 0) {
         if (phases > 0) {
           for (int ph = 0; ph < phases && ph < L; ph++) {
@@ -1574,7 +1559,7 @@ extern "C" int f2n_hash_bwd_binned(
             pl.log2_sub, arena, 0, 1);
         }
       }
-    })
+    });
 #undef F2N_BIN_LAUNCH
     if (hipGetLastError() != hipSuccess) return F2N_E_LAUNCH;
   }

@@ -429,8 +429,6 @@ __global__ __launch_bounds__(F2N_BLOCK) void contract_bwd_kernel(
   dp[3 * p + 2] = oz;
 }
 
-inline bool is_pow2(uint32_t v) { return v && !(v & (v - 1u)); }
-
 }  // namespace
 
 extern "C" int f2n_table_to_f16(
@@ -448,15 +446,6 @@ extern "C" int f2n_table_to_f16(
   return f2n_launch_status();
 }
 
-#define F2N_DISPATCH_F(F_, ...)      \
-  switch (F_) {                      \
-    case 1: { constexpr int FF = 1; __VA_ARGS__; } break; \
-    case 2: { constexpr int FF = 2; __VA_ARGS__; } break; \
-    case 4: { constexpr int FF = 4; __VA_ARGS__; } break; \
-    case 8: { constexpr int FF = 8; __VA_ARGS__; } break; \
-    default: return F2N_E_UNSUPPORTED; \
-  }
-
 extern "C" int f2n_hash_fwd(
   const float * pts, const uint16_t * table_f16, const int32_t * primes, const float * bias,
   const float * mul, float * out, int64_t out_ld_point, int64_t out_ld_chan, uint32_t * idx_out,
@@ -469,17 +458,11 @@ extern "C" int f2n_hash_fwd(
   if (n == 0) return F2N_OK;
   const dim3 grid(f2n_div_up(n, F2N_BLOCK), (unsigned)L), block(F2N_BLOCK);
   hipStream_t s = (hipStream_t)stream;
-  const bool p2 = is_pow2(T);
-  F2N_DISPATCH_F(F, {
-    if (p2)
-      hipLaunchKernelGGL(
-        (hash_fwd_kernel<FF, true>), grid, block, 0, s, pts, table_f16, primes, bias, mul, out,
-        out_ld_point, out_ld_chan, idx_out, n, L, T, level_stride);
-    else
-      hipLaunchKernelGGL(
-        (hash_fwd_kernel<FF, false>), grid, block, 0, s, pts, table_f16, primes, bias, mul, out,
-        out_ld_point, out_ld_chan, idx_out, n, L, T, level_stride);
-  })
+  f2n_dispatch_field(F, T, [&](auto ff, auto p2) {
+    hipLaunchKernelGGL(
+      (hash_fwd_kernel<decltype(ff)::value, decltype(p2)::value>), grid, block, 0, s, pts,
+      table_f16, primes, bias, mul, out, out_ld_point, out_ld_chan, idx_out, n, L, T, level_stride);
+  });
   return f2n_launch_status();
 }
 
@@ -504,21 +487,18 @@ extern "C" int f2n_hash_fwd_raytile(
   if (tiles > 0x7fffffff) return F2N_E_INVALID_ARG;
   const dim3 grid((unsigned)tiles, (unsigned)L), block(F2N_BLOCK);
   hipStream_t s = (hipStream_t)stream;
-  const bool p2 = is_pow2(T);
-#define F2N_RT_LAUNCH(P2, SS)                                                                      \
-  hipLaunchKernelGGL(                                                                              \
-    (hash_fwd_raytile_kernel<FF, P2, SS>), grid, block, 0, s, pts, table_f16, primes, bias, mul,   \
-    out_cm, n_rays, S, T, level_stride, walk)
-  F2N_DISPATCH_F(F, {
-    if (p2) {
-      if (ts == 16) F2N_RT_LAUNCH(true, 16);
-      else F2N_RT_LAUNCH(true, 32);
-    } else {
-      if (ts == 16) F2N_RT_LAUNCH(false, 16);
-      else F2N_RT_LAUNCH(false, 32);
-    }
-  })
-#undef F2N_RT_LAUNCH
+  f2n_dispatch_field(F, T, [&](auto ff, auto p2) {
+    constexpr int FF = decltype(ff)::value;
+    constexpr bool P2 = decltype(p2)::value;
+    if (ts == 16)
+      hipLaunchKernelGGL(
+        (hash_fwd_raytile_kernel<FF, P2, 16>), grid, block, 0, s, pts, table_f16, primes, bias, mul,
+        out_cm, n_rays, S, T, level_stride, walk);
+    else
+      hipLaunchKernelGGL(
+        (hash_fwd_raytile_kernel<FF, P2, 32>), grid, block, 0, s, pts, table_f16, primes, bias, mul,
+        out_cm, n_rays, S, T, level_stride, walk);
+  });
   return f2n_launch_status();
 }
 
@@ -538,7 +518,6 @@ extern "C" int f2n_hash_bwd(
   if (!(grad_scale > 0.f) || m != 0.5f) return F2N_E_INVALID_ARG;  // power of two only
   if (n == 0) return F2N_OK;
   hipStream_t s = (hipStream_t)stream;
-  const bool p2 = is_pow2(T);
   const float inv = 1.f / grad_scale;
 
   // Training case (no point gradient) on a big batch: LDS-sliced accumulation.  The hash work is
@@ -553,15 +532,12 @@ extern "C" int f2n_hash_bwd(
     int n_parts = 1;
     while ((int64_t)L * n_slices * n_parts < 512 && (n / (n_parts * 2)) >= 65536) n_parts *= 2;
     const dim3 grid((unsigned)n_slices, (unsigned)L, (unsigned)n_parts), block(kSliceBlock);
-#define F2N_BWD_SLICED(P2)                                                                        \
-  hipLaunchKernelGGL(                                                                             \
-    (hash_bwd_sliced_kernel<FF, P2>), grid, block, 0, s, pts, primes, bias, mul, grad_out,        \
-    g_ld_point, g_ld_chan, table_grad, n, T, level_stride, grad_scale, inv, n_parts)
-    F2N_DISPATCH_F(F, {
-      if (p2) F2N_BWD_SLICED(true);
-      else F2N_BWD_SLICED(false);
-    })
-#undef F2N_BWD_SLICED
+    f2n_dispatch_field(F, T, [&](auto ff, auto p2) {
+      hipLaunchKernelGGL(
+        (hash_bwd_sliced_kernel<decltype(ff)::value, decltype(p2)::value>), grid, block, 0, s, pts,
+        primes, bias, mul, grad_out, g_ld_point, g_ld_chan, table_grad, n, T, level_stride,
+        grad_scale, inv, n_parts);
+    });
     return f2n_launch_status();
   }
 
@@ -569,20 +545,18 @@ extern "C" int f2n_hash_bwd(
     if (hipMemsetAsync(pts_grad, 0, sizeof(float) * 3 * n, s) != hipSuccess) return F2N_E_LAUNCH;
   }
   const dim3 grid(f2n_div_up(n, F2N_BLOCK), (unsigned)L), block(F2N_BLOCK);
-#define F2N_BWD_LAUNCH(P2, PG)                                                                    \
-  hipLaunchKernelGGL(                                                                             \
-    (hash_bwd_kernel<FF, P2, PG>), grid, block, 0, s, pts, table_f16, primes, bias, mul, grad_out, \
-    g_ld_point, g_ld_chan, table_grad, pts_grad, n, T, level_stride, grad_scale, inv)
-  F2N_DISPATCH_F(F, {
-    if (p2) {
-      if (pts_grad) F2N_BWD_LAUNCH(true, true);
-      else F2N_BWD_LAUNCH(true, false);
-    } else {
-      if (pts_grad) F2N_BWD_LAUNCH(false, true);
-      else F2N_BWD_LAUNCH(false, false);
-    }
-  })
-#undef F2N_BWD_LAUNCH
+  f2n_dispatch_field(F, T, [&](auto ff, auto p2) {
+    constexpr int FF = decltype(ff)::value;
+    constexpr bool P2 = decltype(p2)::value;
+    if (pts_grad)
+      hipLaunchKernelGGL(
+        (hash_bwd_kernel<FF, P2, true>), grid, block, 0, s, pts, table_f16, primes, bias, mul,
+        grad_out, g_ld_point, g_ld_chan, table_grad, pts_grad, n, T, level_stride, grad_scale, inv);
+    else
+      hipLaunchKernelGGL(
+        (hash_bwd_kernel<FF, P2, false>), grid, block, 0, s, pts, table_f16, primes, bias, mul,
+        grad_out, g_ld_point, g_ld_chan, table_grad, pts_grad, n, T, level_stride, grad_scale, inv);
+  });
   return f2n_launch_status();
 }
 

@@ -64,8 +64,6 @@ __global__ __launch_bounds__(F2N_BLOCK) void occ_lookup_kernel(
   out[i] = occ_test_point(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], bits, G) ? 1 : 0;
 }
 
-inline bool is_pow2(uint32_t v) { return v && !(v & (v - 1u)); }
-
 }  // namespace
 
 extern "C" int f2n_occ_update(
@@ -74,10 +72,8 @@ extern "C" int f2n_occ_update(
   int L, int F, uint32_t T, int64_t level_stride, float density_shift, float threshold, float decay,
   void * stream)
 {
-  if (!f2n_occ_res_ok(G) || L < 1 || L > F2N_MAX_LEVELS || T < 1 || level_stride < 0)
-    return F2N_E_INVALID_ARG;
-  if (F != 1 && F != 2 && F != 4 && F != 8) return F2N_E_UNSUPPORTED;
-  if (level_stride % F) return F2N_E_INVALID_ARG;
+  if (!f2n_occ_res_ok(G) || L > F2N_MAX_LEVELS) return F2N_E_INVALID_ARG;
+  if (const int st = f2n_field_args_status(L, F, T, level_stride)) return st;
   if (!table_f16 || !primes || !bias || !mul || !w0 || !b0 || !density || !bits)
     return F2N_E_INVALID_ARG;
   if (reinterpret_cast<uintptr_t>(table_f16) % (2u * F)) return F2N_E_INVALID_ARG;
@@ -87,18 +83,12 @@ extern "C" int f2n_occ_update(
   const int64_t cells = (int64_t)G * G * G;
   const dim3 grid((unsigned)(cells / F2N_BLOCK)), block(F2N_BLOCK);
   hipStream_t s = (hipStream_t)stream;
-  const bool p2 = is_pow2(T);
-#define F2N_OCC_UPDATE(FF, P2)                                                                    \
-  hipLaunchKernelGGL(                                                                             \
-    (occ_update_kernel<FF, P2>), grid, block, 0, s, table_f16, primes, bias, mul, w0, b0, probe_u,\
-    density, bits, G, log2_g, L, T, level_stride, density_shift, threshold, decay)
-  switch (F) {
-    case 1: if (p2) F2N_OCC_UPDATE(1, true); else F2N_OCC_UPDATE(1, false); break;
-    case 2: if (p2) F2N_OCC_UPDATE(2, true); else F2N_OCC_UPDATE(2, false); break;
-    case 4: if (p2) F2N_OCC_UPDATE(4, true); else F2N_OCC_UPDATE(4, false); break;
-    default: if (p2) F2N_OCC_UPDATE(8, true); else F2N_OCC_UPDATE(8, false); break;
-  }
-#undef F2N_OCC_UPDATE
+  f2n_dispatch_field(F, T, [&](auto ff, auto p2) {
+    hipLaunchKernelGGL(
+      (occ_update_kernel<decltype(ff)::value, decltype(p2)::value>), grid, block, 0, s, table_f16,
+      primes, bias, mul, w0, b0, probe_u, density, bits, G, log2_g, L, T, level_stride,
+      density_shift, threshold, decay);
+  });
   return f2n_launch_status();
 }
 

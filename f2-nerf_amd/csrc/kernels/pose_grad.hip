@@ -334,8 +334,6 @@ __global__ __launch_bounds__(F2N_BLOCK) void lens_rays_bwd_partial_kernel(
   if (threadIdx.x < 12) partial[12 * (int64_t)blockIdx.x + threadIdx.x] = s;
 }
 
-inline bool is_pow2(uint32_t v) { return v && !(v & (v - 1u)); }
-
 }  // namespace
 
 extern "C" int f2n_hash_rays_grad(
@@ -359,19 +357,12 @@ extern "C" int f2n_hash_rays_grad(
   const dim3 grid(f2n_div_up(n_rays, F2N_WAVES_PER_BLOCK)), block(F2N_BLOCK);
   hipStream_t s = (hipStream_t)stream;
   const float inv = 1.f / grad_scale;
-#define F2N_RG_LAUNCH(FF, P2)                                                                      \
-  hipLaunchKernelGGL(                                                                              \
-    (hash_rays_grad_kernel<FF, P2>), grid, block, 0, s, pts, t, bounds, rays_d, table_f16, primes, \
-    bias, mul, grad_out, g_ld_point, g_ld_chan, d_rays_o, d_rays_d, n_rays, L, T, level_stride,   \
-    grad_scale, inv)
-  const bool p2 = is_pow2(T);
-  switch (F) {
-    case 1: if (p2) F2N_RG_LAUNCH(1, true); else F2N_RG_LAUNCH(1, false); break;
-    case 2: if (p2) F2N_RG_LAUNCH(2, true); else F2N_RG_LAUNCH(2, false); break;
-    case 4: if (p2) F2N_RG_LAUNCH(4, true); else F2N_RG_LAUNCH(4, false); break;
-    default: if (p2) F2N_RG_LAUNCH(8, true); else F2N_RG_LAUNCH(8, false); break;
-  }
-#undef F2N_RG_LAUNCH
+  f2n_dispatch_field(F, T, [&](auto ff, auto p2) {
+    hipLaunchKernelGGL(
+      (hash_rays_grad_kernel<decltype(ff)::value, decltype(p2)::value>), grid, block, 0, s, pts, t,
+      bounds, rays_d, table_f16, primes, bias, mul, grad_out, g_ld_point, g_ld_chan, d_rays_o,
+      d_rays_d, n_rays, L, T, level_stride, grad_scale, inv);
+  });
   return f2n_launch_status();
 }
 

@@ -34,18 +34,7 @@ namespace
 
 template <int C, int F, bool POW2>
 __global__ __launch_bounds__(RShape<C>::kWaves * 64) void render_rays_kernel(
-  const float * __restrict__ rays_o, const float * __restrict__ rays_d,
-  const float * __restrict__ noise, const uint16_t * __restrict__ table,
-  const int32_t * __restrict__ primes, const float * __restrict__ bias,
-  const float * __restrict__ mul, const float * __restrict__ p_w_h,
-  const float * __restrict__ p_b_h, const float * __restrict__ p_w1,
-  const float * __restrict__ p_b1, const float * __restrict__ p_w2,
-  const float * __restrict__ p_b2, const float * __restrict__ p_emb,
-  const int32_t * __restrict__ ray_img, const uint32_t * __restrict__ bits, int G,
-  const float * __restrict__ bg, float * __restrict__ colors, float * __restrict__ depths,
-  float * __restrict__ last_trans, int32_t * __restrict__ kept, int32_t * __restrict__ len,
-  int n_rays, int S, float step, uint32_t T, int64_t level_stride, float t_thresh,
-  float density_shift, float t_shift)
+  F2N_RENDER_PARAMS)
 {
   using R = RShape<C>;
   using FS = typename R::FS;
@@ -73,8 +62,6 @@ __global__ __launch_bounds__(RShape<C>::kWaves * 64) void render_rays_kernel(
     render_one_ray<C, F, POW2>(a, r, whole, lds_w, tile, OUT, lane, has_emb, has_grid, bias0);
 }
 
-inline bool is_pow2(uint32_t v) { return v && !(v & (v - 1u)); }
-
 }  // namespace
 
 extern "C" int f2n_render_rays(
@@ -86,54 +73,17 @@ extern "C" int f2n_render_rays(
   int S, float step, int L, int F, uint32_t T, int64_t level_stride, float t_thresh,
   float density_shift, float t_shift, void * stream)
 {
-  if (n_rays < 0 || S < 1 || L < 1 || T < 1 || level_stride < 0) return F2N_E_INVALID_ARG;
-  if (F != 1 && F != 2 && F != 4 && F != 8) return F2N_E_UNSUPPORTED;
-  const int64_t C = (int64_t)L * F;
-  if (C != 8 && C != 16 && C != 32 && C != 64) return F2N_E_UNSUPPORTED;
-  if (L > F2N_MAX_LEVELS) return F2N_E_UNSUPPORTED;  // (C = 64 at F = 1)
-  if (level_stride % F) return F2N_E_INVALID_ARG;
-  if (occ_bits && !f2n_occ_res_ok(G)) return F2N_E_INVALID_ARG;
-  if ((app_emb == nullptr) != (ray_img == nullptr)) return F2N_E_INVALID_ARG;
-  if (n_rays == 0) return F2N_OK;
-  if (!rays_o || !rays_d || !table || !primes || !bias || !mul || !w_h || !b_h || !w1 || !b1 ||
-      !w2 || !b2 || !bg || !colors || !depths || !last_trans || !kept)
-    return F2N_E_INVALID_ARG;
-  if (reinterpret_cast<uintptr_t>(table) % (2u * F)) return F2N_E_INVALID_ARG;
-  // the embedding rows are read as float4
-  if (app_emb && (reinterpret_cast<uintptr_t>(app_emb) & 15u)) return F2N_E_INVALID_ARG;
+  bool launch;
+  const int st = render_args_status(F2N_RENDER_KARGS, L, F, S, nullptr, &launch);
+  if (st != F2N_OK || !launch) return st;
   hipStream_t s = (hipStream_t)stream;
-  const bool p2 = is_pow2(T);
   // persistent workgroups: the weight operands are staged once per workgroup, not once per 8 rays
-#define F2N_RENDER(CC, FF, P2)                                                                     \
-  {                                                                                                \
-    using R = RShape<CC>;                                                                          \
-    const unsigned grid = std::min<unsigned>(f2n_div_up(n_rays, R::kWaves), 512u);                 \
-    hipLaunchKernelGGL(                                                                            \
-      (render_rays_kernel<CC, FF, P2>), dim3(grid), dim3(R::kWaves * 64), 0, s, rays_o, rays_d,    \
-      noise, table, primes, bias, mul, w_h, b_h, w1, b1, w2, b2, app_emb, ray_img, occ_bits, G,    \
-      bg, colors, depths, last_trans, kept, len, n_rays, S, step, T, level_stride, t_thresh,       \
-      density_shift, t_shift);                                                                     \
-  }
-#define F2N_RENDER_F(CC, FF)       \
-  if (p2) F2N_RENDER(CC, FF, true) \
-  else F2N_RENDER(CC, FF, false)
-#define F2N_RENDER_C(CC, CASE_F1)                      \
-  switch (F) {                                         \
-    CASE_F1                                            \
-    case 2: F2N_RENDER_F(CC, 2) break;                 \
-    case 4: F2N_RENDER_F(CC, 4) break;                 \
-    default: F2N_RENDER_F(CC, 8) break;                \
-  }
-#define F2N_RENDER_F1(CC) case 1: F2N_RENDER_F(CC, 1) break;
-  switch ((int)C) {
-    case 8: F2N_RENDER_C(8, F2N_RENDER_F1(8)) break;
-    case 16: F2N_RENDER_C(16, F2N_RENDER_F1(16)) break;
-    case 32: F2N_RENDER_C(32, F2N_RENDER_F1(32)) break;
-    default: F2N_RENDER_C(64, ) break;  // (F = 1 would be 64 levels: refused above)
-  }
-#undef F2N_RENDER_F1
-#undef F2N_RENDER_C
-#undef F2N_RENDER_F
-#undef F2N_RENDER
+  f2n_dispatch_width_field(L, F, T, [&](auto cc, auto ff, auto p2) {
+    using R = RShape<decltype(cc)::value>;
+    const unsigned grid = std::min<unsigned>(f2n_div_up(n_rays, R::kWaves), 512u);
+    hipLaunchKernelGGL(
+      (render_rays_kernel<decltype(cc)::value, decltype(ff)::value, decltype(p2)::value>),
+      dim3(grid), dim3(R::kWaves * 64), 0, s, F2N_RENDER_KARGS);
+  });
   return f2n_launch_status();
 }

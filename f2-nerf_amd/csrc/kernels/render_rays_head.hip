@@ -74,20 +74,6 @@ __device__ __forceinline__ float group_sum(float v, int m, int lane)
   return group_last(group_incl_scan(v, m), lane);
 }
 
-#define F2N_RENDER_PARAMS                                                                          \
-  const float * __restrict__ rays_o, const float * __restrict__ rays_d,                            \
-    const float * __restrict__ noise, const uint16_t * __restrict__ table,                         \
-    const int32_t * __restrict__ primes, const float * __restrict__ bias,                          \
-    const float * __restrict__ mul, const float * __restrict__ p_w_h,                              \
-    const float * __restrict__ p_b_h, const float * __restrict__ p_w1,                             \
-    const float * __restrict__ p_b1, const float * __restrict__ p_w2,                              \
-    const float * __restrict__ p_b2, const float * __restrict__ p_emb,                             \
-    const int32_t * __restrict__ ray_img, const uint32_t * __restrict__ bits, int G,               \
-    const float * __restrict__ bg, float * __restrict__ colors, float * __restrict__ depths,       \
-    float * __restrict__ last_trans, int32_t * __restrict__ kept, int32_t * __restrict__ len,      \
-    int n_rays, int S, float step, uint32_t T, int64_t level_stride, float t_thresh,               \
-    float density_shift, float t_shift
-
 template <int C, int F, bool POW2>
 __global__ __launch_bounds__(HShape<C>::kWaves * 64) void render_rays_head_kernel(
   F2N_RENDER_PARAMS, float * __restrict__ state, int n_head)
@@ -373,70 +359,12 @@ __global__ __launch_bounds__(RShape<C>::kWaves * 64) void render_rays_tail_kerne
   }
 }
 
-inline bool is_pow2(uint32_t v) { return v && !(v & (v - 1u)); }
-
-// the checks of f2n_render_rays, then the head's own: F2N_OK + *launch = false means nothing to do
-int check_args(
-  const float * rays_o, const float * rays_d, const uint16_t * table, const int32_t * primes,
-  const float * bias, const float * mul, const float * w_h, const float * b_h, const float * w1,
-  const float * b1, const float * w2, const float * b2, const float * app_emb,
-  const int32_t * ray_img, const uint32_t * occ_bits, int G, const float * bg, const float * colors,
-  const float * depths, const float * last_trans, const int32_t * kept, int n_rays, int S, int L,
-  int F, uint32_t T, int64_t level_stride, int n_head, const void * state, bool * launch)
-{
-  *launch = false;
-  if (n_rays < 0 || S < 1 || L < 1 || T < 1 || level_stride < 0) return F2N_E_INVALID_ARG;
-  if (F != 1 && F != 2 && F != 4 && F != 8) return F2N_E_UNSUPPORTED;
-  const int64_t C = (int64_t)L * F;
-  if (C != 8 && C != 16 && C != 32 && C != 64) return F2N_E_UNSUPPORTED;
-  if (L > F2N_MAX_LEVELS) return F2N_E_UNSUPPORTED;  // (C = 64 at F = 1)
-  if (level_stride % F) return F2N_E_INVALID_ARG;
-  if (occ_bits && !f2n_occ_res_ok(G)) return F2N_E_INVALID_ARG;
-  if ((app_emb == nullptr) != (ray_img == nullptr)) return F2N_E_INVALID_ARG;
-  // the head ends on a block boundary of the 64-lane scan, or takes the whole ray
-  if (n_head < 1 || (n_head < S && n_head % 64 != 0)) return F2N_E_INVALID_ARG;
-  if (n_head < S && !state) return F2N_E_INVALID_ARG;
-  if (state && (reinterpret_cast<uintptr_t>(state) & 15u)) return F2N_E_INVALID_ARG;
-  if (n_rays == 0) return F2N_OK;
-  if (!rays_o || !rays_d || !table || !primes || !bias || !mul || !w_h || !b_h || !w1 || !b1 ||
-      !w2 || !b2 || !bg || !colors || !depths || !last_trans || !kept)
-    return F2N_E_INVALID_ARG;
-  if (reinterpret_cast<uintptr_t>(table) % (2u * F)) return F2N_E_INVALID_ARG;
-  if (app_emb && (reinterpret_cast<uintptr_t>(app_emb) & 15u)) return F2N_E_INVALID_ARG;
-  *launch = true;
-  return F2N_OK;
-}
-
 }  // namespace
 
 extern "C" int64_t f2n_render_rays_state_bytes(int n_rays)
 {
   return n_rays < 0 ? -1 : (int64_t)n_rays * kStateWords * 4;
 }
-
-#define F2N_HT_DISPATCH(LAUNCH)                        \
-  switch ((int)(L * F)) {                              \
-    case 8: F2N_HT_C(LAUNCH, 8, F2N_HT_F1(LAUNCH, 8)) break;    \
-    case 16: F2N_HT_C(LAUNCH, 16, F2N_HT_F1(LAUNCH, 16)) break; \
-    case 32: F2N_HT_C(LAUNCH, 32, F2N_HT_F1(LAUNCH, 32)) break; \
-    default: F2N_HT_C(LAUNCH, 64, ) break;             \
-  }
-#define F2N_HT_F(LAUNCH, CC, FF) \
-  if (p2) LAUNCH(CC, FF, true)   \
-  else LAUNCH(CC, FF, false)
-#define F2N_HT_C(LAUNCH, CC, CASE_F1)                  \
-  switch (F) {                                         \
-    CASE_F1                                            \
-    case 2: F2N_HT_F(LAUNCH, CC, 2) break;             \
-    case 4: F2N_HT_F(LAUNCH, CC, 4) break;             \
-    default: F2N_HT_F(LAUNCH, CC, 8) break;            \
-  }
-#define F2N_HT_F1(LAUNCH, CC) case 1: F2N_HT_F(LAUNCH, CC, 1) break;
-
-#define F2N_KARGS                                                                                  \
-  rays_o, rays_d, noise, table, primes, bias, mul, w_h, b_h, w1, b1, w2, b2, app_emb, ray_img,     \
-    occ_bits, G, bg, colors, depths, last_trans, kept, len, n_rays, S, step, T, level_stride,      \
-    t_thresh, density_shift, t_shift
 
 extern "C" int f2n_render_rays_head(
   const float * rays_o, const float * rays_d, const float * noise, const uint16_t * table,
@@ -448,24 +376,18 @@ extern "C" int f2n_render_rays_head(
   float density_shift, float t_shift, int n_head, void * state, void * stream)
 {
   bool launch;
-  const int st = check_args(
-    rays_o, rays_d, table, primes, bias, mul, w_h, b_h, w1, b1, w2, b2, app_emb, ray_img, occ_bits,
-    G, bg, colors, depths, last_trans, kept, n_rays, S, L, F, T, level_stride, n_head, state,
-    &launch);
+  const int st = render_args_status(F2N_RENDER_KARGS, L, F, n_head, state, &launch);
   if (st != F2N_OK || !launch) return st;
   hipStream_t s = (hipStream_t)stream;
-  const bool p2 = is_pow2(T);
   // persistent workgroups, 12 waves of 8 rays each, one per CU
-#define F2N_HEAD(CC, FF, P2)                                                                       \
-  {                                                                                                \
-    using H = HShape<CC>;                                                                          \
-    const unsigned grid = std::min<unsigned>(f2n_div_up(f2n_div_up(n_rays, 8), H::kWaves), 256u);  \
-    hipLaunchKernelGGL(                                                                            \
-      (render_rays_head_kernel<CC, FF, P2>), dim3(grid), dim3(H::kWaves * 64), 0, s, F2N_KARGS,    \
-      static_cast<float *>(state), n_head);                                                        \
-  }
-  F2N_HT_DISPATCH(F2N_HEAD)
-#undef F2N_HEAD
+  f2n_dispatch_width_field(L, F, T, [&](auto cc, auto ff, auto p2) {
+    using H = HShape<decltype(cc)::value>;
+    const unsigned grid = std::min<unsigned>(f2n_div_up(f2n_div_up(n_rays, 8), H::kWaves), 256u);
+    hipLaunchKernelGGL(
+      (render_rays_head_kernel<decltype(cc)::value, decltype(ff)::value, decltype(p2)::value>),
+      dim3(grid), dim3(H::kWaves * 64), 0, s, F2N_RENDER_KARGS, static_cast<float *>(state),
+      n_head);
+  });
   return f2n_launch_status();
 }
 
@@ -479,23 +401,17 @@ extern "C" int f2n_render_rays_tail(
   float density_shift, float t_shift, int n_head, const void * state, void * stream)
 {
   bool launch;
-  const int st = check_args(
-    rays_o, rays_d, table, primes, bias, mul, w_h, b_h, w1, b1, w2, b2, app_emb, ray_img, occ_bits,
-    G, bg, colors, depths, last_trans, kept, n_rays, S, L, F, T, level_stride, n_head, state,
-    &launch);
+  const int st = render_args_status(F2N_RENDER_KARGS, L, F, n_head, state, &launch);
   if (st != F2N_OK || !launch) return st;
   if (n_head >= S) return F2N_OK;  // the head rendered every ray whole: nothing is pending
   hipStream_t s = (hipStream_t)stream;
-  const bool p2 = is_pow2(T);
-#define F2N_TAIL(CC, FF, P2)                                                                       \
-  {                                                                                                \
-    using R = RShape<CC>;                                                                          \
-    const unsigned grid = std::min<unsigned>(f2n_div_up(n_rays, R::kWaves), 512u);                 \
-    hipLaunchKernelGGL(                                                                            \
-      (render_rays_tail_kernel<CC, FF, P2>), dim3(grid), dim3(R::kWaves * 64), 0, s, F2N_KARGS,    \
-      static_cast<const float *>(state), n_head);                                                  \
-  }
-  F2N_HT_DISPATCH(F2N_TAIL)
-#undef F2N_TAIL
+  f2n_dispatch_width_field(L, F, T, [&](auto cc, auto ff, auto p2) {
+    using R = RShape<decltype(cc)::value>;
+    const unsigned grid = std::min<unsigned>(f2n_div_up(n_rays, R::kWaves), 512u);
+    hipLaunchKernelGGL(
+      (render_rays_tail_kernel<decltype(cc)::value, decltype(ff)::value, decltype(p2)::value>),
+      dim3(grid), dim3(R::kWaves * 64), 0, s, F2N_RENDER_KARGS, static_cast<const float *>(state),
+      n_head);
+  });
   return f2n_launch_status();
 }

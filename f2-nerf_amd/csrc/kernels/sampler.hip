@@ -675,8 +675,6 @@ __global__ __launch_bounds__(kMultiScanBlock) void bounds_from_counts_multi_kern
   if (total && blockIdx.x == gridDim.x - 1 && tid == 0) total[0] = offset + all;
 }
 
-inline bool is_pow2(uint32_t v) { return v && !(v & (v - 1u)); }
-
 }  // namespace
 
 extern "C" int f2n_sample_rays(
@@ -712,10 +710,8 @@ extern "C" int f2n_density_march(
   int32_t * kept, int n_rays, int S, float step, int L, int F, uint32_t T, int64_t level_stride,
   float t_thresh, float density_shift, void * stream)
 {
-  if (n_rays < 0 || S < 1 || L < 1 || L > F2N_MAX_LEVELS || T < 1 || level_stride < 0)
-    return F2N_E_INVALID_ARG;
-  if (F != 1 && F != 2 && F != 4 && F != 8) return F2N_E_UNSUPPORTED;
-  if (level_stride % F) return F2N_E_INVALID_ARG;
+  if (n_rays < 0 || S < 1 || L > F2N_MAX_LEVELS) return F2N_E_INVALID_ARG;
+  if (const int st = f2n_field_args_status(L, F, T, level_stride)) return st;
   if (n_rays == 0) return F2N_OK;
   if (!rays_o || !rays_d || !table_f16 || !primes || !bias || !mul || !w0 || !b0 || !kept)
     return F2N_E_INVALID_ARG;
@@ -727,29 +723,25 @@ extern "C" int f2n_density_march(
   const int rays_per_wave = route == 1 ? 1 : route == 2 ? 4 : 8;
   const dim3 grid(f2n_div_up(n_rays, F2N_WAVES_PER_BLOCK * rays_per_wave)), block(F2N_BLOCK);
   hipStream_t s = (hipStream_t)stream;
-  const bool p2 = is_pow2(T);
-#define F2N_MARCH(FF, P2)                                                                         \
-  if (route == 0)                                                                                 \
-    hipLaunchKernelGGL(                                                                           \
-      (density_march8_kernel<FF, P2>), grid, block, 0, s, rays_o, rays_d, noise, table_f16,       \
-      primes, bias, mul, w0, b0, kept, n_rays, S, step, L, T, level_stride, t_thresh,             \
-      density_shift);                                                                             \
-  else if (rows)                                                                                  \
-    hipLaunchKernelGGL(                                                                           \
-      (density_march16_kernel<FF, P2>), grid, block, 0, s, rays_o, rays_d, noise, table_f16,      \
-      primes, bias, mul, w0, b0, kept, n_rays, S, step, L, T, level_stride, t_thresh,             \
-      density_shift);                                                                             \
-  else                                                                                            \
-    hipLaunchKernelGGL(                                                                           \
-      (density_march_kernel<FF, P2>), grid, block, 0, s, rays_o, rays_d, noise, table_f16, primes,\
-      bias, mul, w0, b0, kept, n_rays, S, step, L, T, level_stride, t_thresh, density_shift)
-  switch (F) {
-    case 1: if (p2) F2N_MARCH(1, true); else F2N_MARCH(1, false); break;
-    case 2: if (p2) F2N_MARCH(2, true); else F2N_MARCH(2, false); break;
-    case 4: if (p2) F2N_MARCH(4, true); else F2N_MARCH(4, false); break;
-    default: if (p2) F2N_MARCH(8, true); else F2N_MARCH(8, false); break;
-  }
-#undef F2N_MARCH
+  f2n_dispatch_field(F, T, [&](auto ff, auto p2) {
+    constexpr int FF = decltype(ff)::value;
+    constexpr bool P2 = decltype(p2)::value;
+    if (route == 0)
+      hipLaunchKernelGGL(
+        (density_march8_kernel<FF, P2>), grid, block, 0, s, rays_o, rays_d, noise, table_f16,
+        primes, bias, mul, w0, b0, kept, n_rays, S, step, L, T, level_stride, t_thresh,
+        density_shift);
+    else if (rows)
+      hipLaunchKernelGGL(
+        (density_march16_kernel<FF, P2>), grid, block, 0, s, rays_o, rays_d, noise, table_f16,
+        primes, bias, mul, w0, b0, kept, n_rays, S, step, L, T, level_stride, t_thresh,
+        density_shift);
+    else
+      hipLaunchKernelGGL(
+        (density_march_kernel<FF, P2>), grid, block, 0, s, rays_o, rays_d, noise, table_f16,
+        primes, bias, mul, w0, b0, kept, n_rays, S, step, L, T, level_stride, t_thresh,
+        density_shift);
+  });
   return f2n_launch_status();
 }
 
@@ -759,11 +751,8 @@ extern "C" int f2n_density_march_occ(
   const uint32_t * bits, int G, int32_t * kept, int32_t * len, int n_rays, int S, float step, int L,
   int F, uint32_t T, int64_t level_stride, float t_thresh, float density_shift, void * stream)
 {
-  if (n_rays < 0 || S < 1 || L < 1 || L > F2N_MAX_LEVELS || T < 1 || level_stride < 0 ||
-      !f2n_occ_res_ok(G))
-    return F2N_E_INVALID_ARG;
-  if (F != 1 && F != 2 && F != 4 && F != 8) return F2N_E_UNSUPPORTED;
-  if (level_stride % F) return F2N_E_INVALID_ARG;
+  if (n_rays < 0 || S < 1 || L > F2N_MAX_LEVELS || !f2n_occ_res_ok(G)) return F2N_E_INVALID_ARG;
+  if (const int st = f2n_field_args_status(L, F, T, level_stride)) return st;
   if (n_rays == 0) return F2N_OK;
   if (!rays_o || !rays_d || !table_f16 || !primes || !bias || !mul || !w0 || !b0 || !bits ||
       !kept || !len)
@@ -771,19 +760,12 @@ extern "C" int f2n_density_march_occ(
   if (reinterpret_cast<uintptr_t>(table_f16) % (2u * F)) return F2N_E_INVALID_ARG;
   const dim3 grid(f2n_div_up(n_rays, F2N_WAVES_PER_BLOCK)), block(F2N_BLOCK);
   hipStream_t s = (hipStream_t)stream;
-  const bool p2 = is_pow2(T);
-#define F2N_MARCH_OCC(FF, P2)                                                                     \
-  hipLaunchKernelGGL(                                                                             \
-    (density_march_occ_kernel<FF, P2>), grid, block, 0, s, rays_o, rays_d, noise, table_f16,      \
-    primes, bias, mul, w0, b0, bits, G, kept, len, n_rays, S, step, L, T, level_stride, t_thresh, \
-    density_shift)
-  switch (F) {
-    case 1: if (p2) F2N_MARCH_OCC(1, true); else F2N_MARCH_OCC(1, false); break;
-    case 2: if (p2) F2N_MARCH_OCC(2, true); else F2N_MARCH_OCC(2, false); break;
-    case 4: if (p2) F2N_MARCH_OCC(4, true); else F2N_MARCH_OCC(4, false); break;
-    default: if (p2) F2N_MARCH_OCC(8, true); else F2N_MARCH_OCC(8, false); break;
-  }
-#undef F2N_MARCH_OCC
+  f2n_dispatch_field(F, T, [&](auto ff, auto p2) {
+    hipLaunchKernelGGL(
+      (density_march_occ_kernel<decltype(ff)::value, decltype(p2)::value>), grid, block, 0, s,
+      rays_o, rays_d, noise, table_f16, primes, bias, mul, w0, b0, bits, G, kept, len, n_rays, S,
+      step, L, T, level_stride, t_thresh, density_shift);
+  });
   return f2n_launch_status();
 }
 

@@ -90,6 +90,29 @@ def test_argument_validation_without_gpu(capi):
         capi.call("contract_fwd", None, None, 5, stream=0)
 
 
+def test_density_march_two_faults_answer_with_the_first_check(capi):
+    """f2n_density_march checks the counts and the level count, then the field arguments (F before the
+    stride's divisibility), then n_rays == 0, then the pointers: with two bad arguments the first
+    check's status is the answer.  Every call here has a fault or no rays: nothing is launched."""
+    INVALID, UNSUPPORTED, OK = -1, -3, 0
+    fn = capi.lib().cdll.f2n_density_march
+    fake = 0x1000
+    # (rays_o, rays_d, noise, table, primes, bias, mul, w0, b0, kept, n_rays, S, step, L, F, T,
+    #  level_stride, t_thresh, density_shift, stream)
+    good = [fake, fake, None] + [fake] * 7 + [4, 128, 1.0 / 32, 16, 2, 1 << 19, 1 << 19, 1e-4, 3.0, None]
+    odd = (1 << 19) + 1
+    for faults, want in (({10: -1, 14: 3}, INVALID), ({13: 0, 14: 3}, INVALID), ({13: 33, 14: 3}, INVALID),
+                         ({15: 0, 14: 3}, INVALID), ({11: 0, 14: 3}, INVALID), ({14: 3, 16: odd}, UNSUPPORTED),
+                         ({3: None, 14: 3}, UNSUPPORTED), ({13: 33, 16: odd}, INVALID),
+                         ({3: None, 13: 33}, INVALID), ({10: -1, 13: 33}, INVALID),
+                         ({13: 64, 14: 1}, INVALID), ({16: -2, 14: 3}, INVALID),
+                         ({10: 0, 14: 3}, UNSUPPORTED), ({10: 0, 16: odd}, INVALID), ({10: 0, 3: None}, OK)):
+        args = list(good)
+        for i, bad in faults.items():
+            args[i] = bad
+        assert fn(*args) == want, faults
+
+
 def test_host_module_mirrors_reference_layout(pkg):
     H = pkg.load_host()
     H.manual_seed(2022)

@@ -121,6 +121,39 @@ def test_march_and_compact_arguments_rejected(capi):
         assert cdll.f2n_sample_compact_occ(*args) == -1, G
 
 
+def test_two_faults_answer_with_the_first_check(capi):
+    """Two bad arguments at once: the status is that of the check an entry makes first.  The order and
+    the codes are each entry's own (the shared field-argument check covers only L < 1, T < 1, a negative
+    stride, F outside {1, 2, 4, 8} and a stride that is no multiple of F, in that order)."""
+    INVALID, UNSUPPORTED = -1, -3
+    cdll = capi.lib().cdll
+    odd = (1 << 19) + 1
+    # f2n_occ_update: G and the level count first, then the field arguments, then the pointers
+    good = [FAKE] * 6 + [None, FAKE, FAKE, 128, 16, 2, 1 << 19, 1 << 19, 3.0, 1.0, 0.95, None]
+    for faults, want in (({10: 0, 11: 3}, INVALID), ({10: 33, 11: 3}, INVALID), ({12: 0, 11: 3}, INVALID),
+                         ({9: 100, 11: 3}, INVALID), ({11: 3, 13: odd}, UNSUPPORTED),
+                         ({0: None, 11: 3}, UNSUPPORTED), ({10: 33, 13: odd}, INVALID),
+                         ({0: None, 10: 33}, INVALID), ({10: 64, 11: 1}, INVALID)):
+        args = list(good)
+        for i, bad in faults.items():
+            args[i] = bad
+        assert cdll.f2n_occ_update(*args) == want, faults
+    # f2n_density_march_occ: counts, level count and G first, then the field arguments, then n_rays == 0
+    # and the pointers
+    good = [FAKE, FAKE, None] + [FAKE] * 7 + [128, FAKE, FAKE, 4, 1024, 1.0 / 256, 16, 2, 1 << 19,
+                                              1 << 19, 1e-4, 3.0, None]
+    for faults, want in (({13: -1, 17: 3}, INVALID), ({16: 0, 17: 3}, INVALID), ({16: 33, 17: 3}, INVALID),
+                         ({18: 0, 17: 3}, INVALID), ({14: 0, 17: 3}, INVALID), ({10: 100, 17: 3}, INVALID),
+                         ({17: 3, 19: odd}, UNSUPPORTED), ({3: None, 17: 3}, UNSUPPORTED),
+                         ({16: 33, 19: odd}, INVALID), ({3: None, 16: 33}, INVALID),
+                         ({13: -1, 16: 33}, INVALID), ({16: 64, 17: 1}, INVALID),
+                         ({13: 0, 17: 3}, UNSUPPORTED), ({13: 0, 19: odd}, INVALID)):
+        args = list(good)
+        for i, bad in faults.items():
+            args[i] = bad
+        assert cdll.f2n_density_march_occ(*args) == want, faults
+
+
 def _resource_usage(tmp_path, name):
     src = os.path.join(build.KERNEL_DIR, name)
     cmd = [build.HIPCC, *build.HIP_FLAGS, "-I", build.INCLUDE_DIR, "-I", build.KERNEL_DIR,

@@ -68,6 +68,24 @@ def test_null_and_negative_arguments_rejected(capi):
         assert cdll.f2n_gen_rays_bwd(*args) == -1, (i, bad)
 
 
+def test_hash_rays_grad_two_faults_answer_with_the_first_check(capi):
+    """f2n_hash_rays_grad checks the pointers, then the counts, then F, then the rest of the field
+    arguments: with two bad arguments the first check's status is the answer."""
+    INVALID, UNSUPPORTED = -1, -3
+    fn = capi.lib().cdll.f2n_hash_rays_grad
+    fake = ctypes.c_void_p(0x1000)
+    good = [fake] * 9 + [1, 1 << 10, fake, fake, 4, 16, 2, 1 << 19, 1 << 19, 128.0, None]
+    odd = (1 << 19) + 1
+    for faults, want in (({13: -1, 15: 3}, INVALID), ({14: 0, 15: 3}, UNSUPPORTED),
+                         ({14: 33, 15: 3}, UNSUPPORTED), ({16: 0, 15: 3}, UNSUPPORTED),
+                         ({15: 3, 17: odd}, UNSUPPORTED), ({4: None, 15: 3}, INVALID),
+                         ({14: 33, 17: odd}, INVALID), ({4: None, 14: 33}, INVALID)):
+        args = list(good)
+        for i, bad in faults.items():
+            args[i] = bad
+        assert fn(*args) == want, faults
+
+
 def _resource_usage(tmp_path):
     cmd = [build.HIPCC, *build.HIP_FLAGS, "-I", build.INCLUDE_DIR, "-I", build.KERNEL_DIR,
            "--offload-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", SRC,

@@ -153,3 +153,14 @@ def test_argument_validation_without_gpu(capi, entry):
         assert call(n_rays=0, occ=None, G=G) == OK, G
     for G in (32, 64, 128, 256):
         assert call(n_rays=0, occ=1 << 20, G=G) == OK, G
+    # ---- two faults at once: the first check's status (F and the width before the stride's
+    # divisibility, the level cap as "unsupported", all of them before the pointers)
+    odd = (1 << 19) * 2 + 1
+    for kw, want in ((dict(n_rays=-1, F=3), INVALID), (dict(L=0, F=3), INVALID), (dict(T=0, F=3), INVALID),
+                     (dict(S=0, F=3), INVALID), (dict(F=3, stride=odd), UNSUPPORTED),
+                     (dict(L=33, F=3), UNSUPPORTED), (dict(L=33, stride=odd), UNSUPPORTED),
+                     (dict(L=3, stride=odd), UNSUPPORTED), (dict(L=64, F=1), UNSUPPORTED),
+                     (dict(L=64, F=1, stride=-2), INVALID), (dict(null=("table",), F=3), UNSUPPORTED),
+                     (dict(null=("table",), L=33), UNSUPPORTED), (dict(n_rays=-1, L=33), INVALID),
+                     (dict(occ=1 << 20, G=100, F=3), UNSUPPORTED)):
+        assert call(**kw) == want, kw
