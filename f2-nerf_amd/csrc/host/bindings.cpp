@@ -339,6 +339,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def("set_fused_ray_grad", [](Renderer & r, bool f) { r.options_.fused_ray_grad = f; },
          "rays that require grad take the fused path: see RendererOptions::fused_ray_grad")
     .def("set_margin_min_samples", [](Renderer & r, int64_t n) { r.options_.margin_min_samples = n; })
+    .def("set_ray_order_min_rays", [](Renderer & r, int64_t n) { r.options_.ray_order_min_rays = n; },
+         "dense first pass: bucket the rays from this many on (RendererOptions::ray_order_min_rays)")
     .def("set_one_pass", &Renderer::set_one_pass,
          "render_all_rays / render_image in one kernel per chunk: see RendererOptions::one_pass")
     .def("one_pass_applies", &Renderer::one_pass_applies)

@@ -191,18 +191,33 @@ Tensor Hash3DAnchored::encode(const Tensor & points, int64_t samples_per_ray, Te
   return torch::autograd::Hash3DAnchoredFunction::apply(x, feat_pool_, torch::IValue(info))[0];
 }
 
+Tensor Hash3DAnchored::encode_contracted(const Tensor & x, int64_t samples_per_ray)
+{
+  TORCH_CHECK(
+    !(torch::GradMode::is_enabled() && x.requires_grad()),
+    "encode_contracted: positions that carry a gradient need encode()");
+  auto info = torch::make_intrusive<Hash3DAnchoredInfo>();
+  info->hash3d_ = this;
+  info->samples_per_ray_ = samples_per_ray;
+  return torch::autograd::Hash3DAnchoredFunction::apply(x, feat_pool_, torch::IValue(info))[0];
+}
+
 Tensor Hash3DAnchored::encode_cached(
   const Tensor & points, const Tensor & enc_cm, const Tensor & contracted)
 {
+  TORCH_CHECK(points.defined() || contracted.defined(), "encode_cached: no positions");
+  const int64_t n = points.defined() ? points.size(0) : contracted.size(0);
   TORCH_CHECK(
-    enc_cm.dim() == 2 && enc_cm.is_contiguous() && enc_cm.size(1) == points.size(0) &&
+    enc_cm.dim() == 2 && enc_cm.is_contiguous() && enc_cm.size(1) == n &&
       enc_cm.size(0) == options_.n_levels * options_.n_channels,
     "encode_cached: enc_cm must be contiguous [L*F, n]");
   auto info = torch::make_intrusive<Hash3DAnchoredInfo>();
   info->hash3d_ = this;
   info->precomputed_cm_ = enc_cm;
-  const bool reuse = contracted.defined() && contracted.sizes() == points.sizes() &&
-                     !(torch::GradMode::is_enabled() && points.requires_grad());
+  const bool reuse =
+    contracted.defined() &&
+    (!points.defined() || (contracted.sizes() == points.sizes() &&
+                           !(torch::GradMode::is_enabled() && points.requires_grad())));
   Tensor x = reuse ? contracted : ContractFn::apply(points)[0];
   return torch::autograd::Hash3DAnchoredFunction::apply(x, feat_pool_, torch::IValue(info))[0];
 }

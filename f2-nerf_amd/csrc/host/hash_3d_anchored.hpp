@@ -68,11 +68,16 @@ public:
   // contracted_out, if given, receives the contracted points (to hand back to encode_cached).
   Tensor encode(const Tensor & points, int64_t samples_per_ray = 0, Tensor * contracted_out = nullptr);
 
+  // encode() of positions that are contracted already (f2n_sample_dense writes them): `x` [n, 3] goes
+  // to the hash encode as it is, no contraction node.  For positions that carry no gradient.
+  Tensor encode_contracted(const Tensor & x, int64_t samples_per_ray = 0);
+
   // Same autograd node as encode(), but the forward result is supplied: `enc_cm` [L*F, n]
   // channel-major, the encoding of exactly these points computed earlier (the Renderer's first pass).
   // Only the backward (table gradient) runs a kernel.
   // `contracted`, if defined, is the contraction of exactly these points (from encode()); it is
-  // used as is when the points carry no gradient.
+  // used as is when the points carry no gradient.  `points` may be undefined when `contracted` is
+  // given (a sampler that wrote contracted positions only).
   Tensor encode_cached(
     const Tensor & points, const Tensor & enc_cm, const Tensor & contracted = Tensor());
 

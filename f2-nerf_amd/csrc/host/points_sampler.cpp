@@ -10,9 +10,20 @@ PtsSampler::PtsSampler(const PtsSamplerOptions & opt) : options_(opt)
 
 Tensor PtsSampler::draw_noise(int64_t n_rays, RunningMode mode, const torch::Device & device) const
 {
+  return cook_noise(draw_noise_raw(n_rays, mode, device));
+}
+
+Tensor PtsSampler::draw_noise_raw(
+  int64_t n_rays, RunningMode mode, const torch::Device & device) const
+{
   if (mode == RunningMode::VALIDATE) return Tensor();
-  return ((torch::rand({n_rays, (int64_t)options_.max_samples}, f2n::float_on(device)) - .5f) + 1.f)
-    .contiguous();
+  return torch::rand({n_rays, (int64_t)options_.max_samples}, f2n::float_on(device));
+}
+
+Tensor PtsSampler::cook_noise(const Tensor & raw)
+{
+  if (!raw.defined()) return raw;
+  return ((raw - .5f) + 1.f).contiguous();
 }
 
 SampleResultFlex PtsSampler::get_samples(
@@ -48,6 +59,41 @@ SampleResultFlex PtsSampler::get_samples(
       res.t.data_ptr<float>(), res.pts_idx_bounds.data_ptr<int32_t>(), n_rays, S, options_.step,
       f2n::current_stream(rays_o)),
     "f2n_sample_rays");
+  return res;
+}
+
+SampleResultFlex PtsSampler::get_samples_dense(
+  const Tensor & rays_o_raw, const Tensor & rays_d_raw, const Tensor & noise_in,
+  const Tensor & noise_rows_in, bool noise_raw)
+{
+  Tensor rays_o = f2n::dev_f32(rays_o_raw, "rays_o");
+  Tensor rays_d = f2n::dev_f32(rays_d_raw, "rays_d");
+  const int n_rays = (int)rays_o.size(0);
+  const int S = options_.max_samples;
+  const int64_t n_all = (int64_t)n_rays * S;
+  Tensor noise, noise_rows;
+  if (noise_in.defined()) {
+    noise = f2n::dev_f32(noise_in, "noise");
+    TORCH_CHECK(noise.numel() == n_all, "noise must hold n_rays * max_samples values");
+    if (noise_rows_in.defined()) {
+      noise_rows = f2n::dev_i32(noise_rows_in, "noise_rows");
+      TORCH_CHECK(noise_rows.numel() == n_rays, "noise_rows must hold n_rays indices");
+    }
+  }
+  const auto fopt = rays_o.options();
+  SampleResultFlex res;
+  res.x = torch::empty({n_all, 3}, fopt);
+  res.dt = torch::empty({n_all}, fopt);
+  res.t = torch::empty({n_all}, fopt);
+  res.pts_idx_bounds = torch::empty({n_rays, 2}, f2n::int_on(rays_o.device()));
+  res.ray_dirs = torch::empty({n_rays, 3}, fopt);
+  f2n::check(
+    f2n_sample_dense(
+      rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), f2n::fptr(noise), f2n::iptr(noise_rows),
+      (noise.defined() && noise_raw) ? 1 : 0, res.x.data_ptr<float>(), res.dt.data_ptr<float>(),
+      res.t.data_ptr<float>(), res.pts_idx_bounds.data_ptr<int32_t>(),
+      res.ray_dirs.data_ptr<float>(), n_rays, S, options_.step, f2n::current_stream(rays_o)),
+    "f2n_sample_dense");
   return res;
 }
 

@@ -16,6 +16,9 @@ struct SampleResultFlex
   Tensor dt;              // [ n_all_pts ]
   Tensor t;               // [ n_all_pts ]
   Tensor pts_idx_bounds;  // [ n_rays, 2 ] start, end
+  // PtsSampler::get_samples_dense only (pts and dirs stay undefined there):
+  Tensor x;               // [ n_all_pts, 3 ] contracted positions
+  Tensor ray_dirs;        // [ n_rays, 3 ] unit direction of each ray
 };
 
 enum RunningMode { TRAIN, VALIDATE };
@@ -39,12 +42,26 @@ public:
   // Same, with the step-noise tensor [n_rays, max_samples] supplied (undefined = all ones).
   SampleResultFlex get_samples(const Tensor & rays_o, const Tensor & rays_d, const Tensor & noise);
 
+  // The dense [n_rays, max_samples] grid for the hash encode and the ray-uniform network kernels, one
+  // kernel (f2n_sample_dense): x (the contracted positions), dt, t, pts_idx_bounds and ray_dirs; no
+  // world positions, no per-sample directions.  Same bits as get_samples + f2n_contract_fwd.
+  //   noise      [n_rays, max_samples] or undefined (all ones)
+  //   noise_rows [n_rays] int32 or undefined: ray r takes row noise_rows[r] of `noise`
+  //   noise_raw  `noise` is draw_noise_raw()'s uniform draw, cooked in the kernel
+  SampleResultFlex get_samples_dense(
+    const Tensor & rays_o, const Tensor & rays_d, const Tensor & noise, const Tensor & noise_rows,
+    bool noise_raw);
+
   // The reference's own ATen formulation (differentiable in rays_o / rays_d through autograd).
   SampleResultFlex get_samples_aten(
     const Tensor & rays_o, const Tensor & rays_d, const Tensor & noise);
 
   // TRAIN: U[0,1) - 0.5 + 1 per sample (points_sampler.cpp:35); VALIDATE: undefined tensor (= ones).
   Tensor draw_noise(int64_t n_rays, RunningMode mode, const torch::Device & device) const;
+  // The two halves of draw_noise: the uniform draw U[0,1) (the same torch::rand call, so the same
+  // generator stream; undefined in VALIDATE), and draw_noise's two element-wise passes over it.
+  Tensor draw_noise_raw(int64_t n_rays, RunningMode mode, const torch::Device & device) const;
+  static Tensor cook_noise(const Tensor & raw);
 
   PtsSamplerOptions options_;
 };

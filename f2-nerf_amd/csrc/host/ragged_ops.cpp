@@ -115,11 +115,13 @@ public:
         f2n::current_stream(weights)),
       "f2n_weight_var_fwd");
     ctx->save_for_backward({weights, idx});
+    ctx->set_materialize_grads(!f2n::lean_grads());
     return {out};
   }
 
   static variable_list backward(AutogradContext * ctx, variable_list grad_output)
   {
+    if (!grad_output[0].defined()) return {Tensor(), Tensor()};  // (lean_grads: nobody asked)
     Tensor dvar = f2n::dev_f32(grad_output[0], "CustomOps::WeightVar grad");
     auto saved = ctx->get_saved_variables();
     Tensor & weights = saved[0];
@@ -193,6 +195,8 @@ public:
     Tensor weights = tiled ? torch::empty({n}, opt) : torch::zeros({n}, opt);
     Tensor last_trans = torch::empty({n_rays}, opt);
     ctx->saved_data["tiled"] = tiled;
+    // (the backward tests .defined(): an absent d_weights goes to the kernel as NULL)
+    ctx->set_materialize_grads(!f2n::lean_grads());
     f2n::check(
       f2n_composite_fwd(
         f2n::fptr(field_out), field_out.size(1), f2n::fptr(rgb), f2n::fptr(dt), f2n::fptr(t),
@@ -344,7 +348,7 @@ class ShadeRaysFn : public torch::autograd::Function<ShadeRaysFn>
 public:
   static variable_list forward(
     AutogradContext * ctx, Tensor enc, Tensor dirs, Tensor ray_img, int64_t S, Tensor w_h,
-    Tensor b_h, Tensor w1, Tensor b1, Tensor w2, Tensor b2, Tensor app_emb)
+    Tensor b_h, Tensor w1, Tensor b1, Tensor w2, Tensor b2, Tensor app_emb, bool dirs_per_ray)
   {
     TORCH_CHECK(enc.is_cuda() && enc.scalar_type() == torch::kFloat32 && enc.dim() == 2, "enc");
     const int64_t n = enc.size(0);
@@ -353,7 +357,8 @@ public:
     const int n_rays = (int)(n / S);
     Tensor enc_cm = as_channel_major(enc);  // [C, n] contiguous
     dirs = f2n::dev_f32(dirs.detach(), "shade dirs");
-    TORCH_CHECK(dirs.numel() == n * 3, "shade_rays: dirs [n, 3]");
+    TORCH_CHECK(
+      dirs.numel() == (dirs_per_ray ? (int64_t)n_rays : n) * 3, "shade_rays: dirs [n, 3] or [n_rays, 3]");
     const bool use_emb =
       ray_img.defined() && app_emb.defined() && ray_img.numel() > 0 && app_emb.numel() > 0;
     if (use_emb) {
@@ -375,7 +380,7 @@ public:
     {
     f2n::ScopedKernelTimer timer("shade_fwd", f2n::current_stream(enc_cm), (double)n);
     f2n::check(
-      f2n_shade_fwd_rays(
+      (dirs_per_ray ? f2n_shade_fwd_raydirs : f2n_shade_fwd_rays)(
         enc_cm.data_ptr<float>(), C, dirs.data_ptr<float>(), use_emb ? f2n::iptr(ray_img) : nullptr,
         f2n::fptr(w_h), f2n::fptr(b_h), f2n::fptr(w1), f2n::fptr(b1), f2n::fptr(w2), f2n::fptr(b2),
         f2n::fptr(emb), logit.data_ptr<float>(), rgb.data_ptr<float>(), n_rays, (int)S,
@@ -385,6 +390,7 @@ public:
     ctx->save_for_backward(
       {enc_cm, dirs, use_emb ? ray_img : Tensor(), w_h, b_h, w1, b1, w2, b2, emb});
     ctx->saved_data["S"] = S;
+    ctx->saved_data["dirs_per_ray"] = dirs_per_ray;
     return {logit, rgb};
   }
 
@@ -395,6 +401,7 @@ public:
            &w1 = sv[5], &b1 = sv[6], &w2 = sv[7], &b2 = sv[8], &emb = sv[9];
     const int C = (int)enc_cm.size(0);
     const int64_t n = enc_cm.size(1), S = ctx->saved_data["S"].toInt();
+    const bool dirs_per_ray = ctx->saved_data["dirs_per_ray"].toBool();
     auto opt = enc_cm.options();
     Tensor d_logit = grad_output[0].defined() ? f2n::dev_f32(grad_output[0], "d_logit")
                                               : torch::zeros({n}, opt);
@@ -421,7 +428,7 @@ public:
     {
     f2n::ScopedKernelTimer timer("shade_bwd", f2n::current_stream(enc_cm), (double)n);
     f2n::check(
-      f2n_shade_bwd_rays(
+      (dirs_per_ray ? f2n_shade_bwd_raydirs : f2n_shade_bwd_rays)(
         enc_cm.data_ptr<float>(), C, dirs.data_ptr<float>(), use_emb ? f2n::iptr(ray_img) : nullptr,
         f2n::fptr(w_h), f2n::fptr(b_h), f2n::fptr(w1), f2n::fptr(b1), f2n::fptr(w2), f2n::fptr(b2),
         f2n::fptr(emb), f2n::fptr(d_logit), f2n::fptr(d_rgb), d_enc_cm.data_ptr<float>(),
@@ -431,7 +438,8 @@ public:
         f2n::current_stream(enc_cm)),
       "f2n_shade_bwd_rays");
     }
-    return {d_enc_cm.t(), Tensor(), Tensor(), Tensor(), g_w_h, g_b_h, g_w1, g_b1, g_w2, g_b2, g_emb};
+    return {d_enc_cm.t(), Tensor(), Tensor(), Tensor(), g_w_h, g_b_h, g_w1, g_b1, g_w2, g_b2, g_emb,
+            Tensor()};
   }
 };
 
@@ -543,15 +551,18 @@ f2n::ShadeOut f2n::shade(
 f2n::ShadeOut f2n::shade_rays(
   const Tensor & enc, const Tensor & dirs, const Tensor & ray_img, int64_t S, const Tensor & w_h,
   const Tensor & b_h, const Tensor & w1, const Tensor & b1, const Tensor & w2, const Tensor & b2,
-  const Tensor & app_emb)
+  const Tensor & app_emb, bool dirs_per_ray)
 {
   const Tensor no_img = torch::empty({0}, f2n::int_on(enc.device()));
   const Tensor no_emb = torch::empty({0, 16}, enc.options());
   const bool use_emb = ray_img.defined() && app_emb.defined();
   auto out = ShadeRaysFn::apply(
-    enc, dirs, use_emb ? ray_img : no_img, S, w_h, b_h, w1, b1, w2, b2, use_emb ? app_emb : no_emb);
+    enc, dirs, use_emb ? ray_img : no_img, S, w_h, b_h, w1, b1, w2, b2, use_emb ? app_emb : no_emb,
+    dirs_per_ray);
   return {out[0], out[1]};
 }
+
+bool f2n::lean_grads() { return f2n_get_option(F2N_OPT_DENSE_LEAN) == 0; }
 
 bool f2n::shade_rays_applies(int64_t n, int64_t n_rays, int64_t S)
 {

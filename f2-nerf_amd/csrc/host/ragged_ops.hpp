@@ -76,10 +76,17 @@ ShadeOut shade(
 // `ray_img` [n_rays] int32 or undefined.  What is the same along a ray (SH(dirs), the embedding
 // row, the SH half of the hidden layer) is done once per 64 samples (f2n_shade_fwd_rays /
 // f2n_shade_bwd_rays).  logit equals shade()'s bit for bit, rgb and the gradients to rounding.
+// dirs_per_ray: `dirs` is [n_rays, 3], one direction per ray (f2n_shade_fwd_raydirs /
+// f2n_shade_bwd_raydirs): the same kernels and, for the same directions, the same bits.
 ShadeOut shade_rays(
   const Tensor & enc, const Tensor & dirs, const Tensor & ray_img, int64_t S, const Tensor & w_h,
   const Tensor & b_h, const Tensor & w1, const Tensor & b1, const Tensor & w2, const Tensor & b2,
-  const Tensor & app_emb);
+  const Tensor & app_emb, bool dirs_per_ray = false);
+
+// F2N_OPT_DENSE_LEAN = 0: the autograd nodes between the per-ray results and the network
+// (CompositeFn, WeightVarFn, the Renderer's RayUnpermuteFn) take an undefined gradient as undefined
+// -- no zero tensor of n samples is made, gathered and read for it.
+bool lean_grads();
 
 // n samples form a dense [n_rays, S] grid that shade_rays serves, and no option asks for the
 // per-sample kernels (F2N_OPT_SHADE_RAYS = 1, or the vector kernels of F2N_OPT_SHADE_FWD / _BWD)

@@ -94,6 +94,8 @@ public:
     ctx->save_for_backward({perm, bounds_sorted, bounds_caller});
     ctx->saved_data["S"] = S;
     ctx->saved_data["rows"] = rows;
+    // (the backward gathers the gradients that exist: no zeros made and moved for the others)
+    ctx->set_materialize_grads(!f2n::lean_grads());
     return {c, d, w};
   }
 
@@ -239,10 +241,26 @@ RenderResult Renderer::render(
   const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
   const Tensor & noise_in, const Tensor & bg_in)
 {
+  return render_routed(rays_o, rays_d, emb_idx, mode, noise_in, bg_in, false);
+}
+
+RenderResult Renderer::render_for_loss(
+  const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
+  const Tensor & noise_in, const Tensor & bg_in)
+{
+  return render_routed(rays_o, rays_d, emb_idx, mode, noise_in, bg_in, true);
+}
+
+RenderResult Renderer::render_routed(
+  const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
+  const Tensor & noise_in, const Tensor & bg_in, bool for_loss)
+{
   const int64_t n_rays = rays_o.size(0);
   const auto fopt = f2n::float_on(rays_o.device());
-  Tensor noise = noise_in.defined() ? noise_in
-                                    : pts_sampler_->draw_noise(n_rays, mode, rays_o.device());
+  // the uniform draw first, as ever (the generator stream does not depend on the route); the lean
+  // dense route hands it to its sampler raw, every other route gets draw_noise's two passes over it
+  Tensor raw = noise_in.defined() ? Tensor()
+                                  : pts_sampler_->draw_noise_raw(n_rays, mode, rays_o.device());
   Tensor bg_color = bg_in.defined() ? bg_in
                     : (mode == RunningMode::TRAIN) ? torch::rand({n_rays, 3}, fopt)
                                                    : torch::ones({n_rays, 3}, fopt) * .5f;
@@ -250,7 +268,12 @@ RenderResult Renderer::render(
     record_kept(0);
     return {bg_color, torch::zeros({n_rays}, fopt), torch::full({n_rays}, 512.f, fopt), Tensor()};
   }
-  const Route route = choose_route(rays_o, rays_d, bg_color);
+  Route route = choose_route(rays_o, rays_d, bg_color);
+  route.noise_raw = route.lean && raw.defined();
+  route.want_var = route.lean && route.bucketed && for_loss;
+  const Tensor noise = noise_in.defined() ? noise_in
+                       : route.noise_raw  ? raw
+                                          : PtsSampler::cook_noise(raw);
   RenderResult res = route.first_pass == Route::OpByOp
                        ? render_op_by_op(rays_o, rays_d, emb_idx, mode, noise, bg_color, route)
                        : render_fused(rays_o, rays_d, emb_idx, mode, noise, bg_color, route);
@@ -290,6 +313,10 @@ Renderer::Route Renderer::choose_route(
                    rays_o.size(0) >= options_.ray_order_min_rays &&
                    f2n_get_option(F2N_OPT_RAY_ORDER) == 0 && !rays_need_grad &&
                    !(torch::GradMode::is_enabled() && bg_color.requires_grad());
+  const int64_t n_rays = rays_o.size(0), S = pts_sampler_->options_.max_samples;
+  route.lean = route.first_pass == Route::Dense && f2n_get_option(F2N_OPT_DENSE_LEAN) == 0 &&
+               !rays_need_grad && !(torch::GradMode::is_enabled() && bg_color.requires_grad()) &&
+               f2n::shade_rays_applies(n_rays * S, n_rays, S);
   return route;
 }
 
@@ -437,16 +464,21 @@ RenderResult Renderer::render_dense_bucketed(
   Tensor perm = torch::empty({n_rays}, iopt), inv = torch::empty({n_rays}, iopt);
   Tensor o_p = torch::empty_like(rays_o), d_p = torch::empty_like(rays_d), bg_p = torch::empty_like(bg);
   Tensor emb_p = emb_idx.defined() ? torch::empty_like(emb_idx) : Tensor();
-  Tensor noise_p = noise.defined() ? torch::empty_like(noise) : Tensor();
+  // (lean: the noise stays where it is, the sampler reads row perm[j] for bucketed ray j)
+  const bool move_noise = noise.defined() && !route.lean;
+  Tensor noise_p = move_noise ? torch::empty_like(noise) : Tensor();
   f2n::check(
     f2n_ray_permute(
       order.data_ptr<int64_t>(), n_rays, (int)S, rays_o.data_ptr<float>(), rays_d.data_ptr<float>(),
-      f2n::iptr(emb_idx), bg.data_ptr<float>(), f2n::fptr(noise), perm.data_ptr<int32_t>(),
+      f2n::iptr(emb_idx), bg.data_ptr<float>(), move_noise ? f2n::fptr(noise) : nullptr,
+      perm.data_ptr<int32_t>(),
       o_p.data_ptr<float>(), d_p.data_ptr<float>(),
       emb_idx.defined() ? emb_p.data_ptr<int32_t>() : nullptr, bg_p.data_ptr<float>(),
       f2n::fptr_mut(noise_p), inv.data_ptr<int32_t>(), stream),
     "f2n_ray_permute");
-  RenderResult r = render_dense(o_p, d_p, emb_p, mode, noise_p, bg_p, route);
+  RenderResult r = route.lean
+                     ? render_dense(o_p, d_p, emb_p, mode, noise, bg_p, route, perm)
+                     : render_dense(o_p, d_p, emb_p, mode, noise_p, bg_p, route);
 
   // every ray kept all S samples (n_kept = n*S, counts <= S): the bounds {i*S, (i+1)*S} are the same
   // in both orders; otherwise the caller-order counts are scanned as the unbucketed route scans them
@@ -461,6 +493,14 @@ RenderResult Renderer::render_dense_bucketed(
       "f2n_counts_through");
     bounds = bounds_from_counts(counts, stream).first;
   }
+  if (route.want_var) {
+    // the variance is a per-ray quantity: taken where the weights lie, its [n_rays] result goes back
+    // with colours and depths as rows of one float -- no [n, S] gather forward or backward
+    Tensor var = CustomOps::WeightVar(r.weights, r.idx_start_end);
+    auto out = RayUnpermuteFn::apply(
+      r.colors, r.depths, var, perm, inv, r.idx_start_end, bounds, /*S=*/1, /*rows=*/true);
+    return {out[0], out[1], Tensor(), bounds, out[2]};
+  }
   auto out = RayUnpermuteFn::apply(
     r.colors, r.depths, r.weights, perm, inv, r.idx_start_end, bounds, S, rows);
   return {out[0], out[1], out[2], bounds};
@@ -470,19 +510,27 @@ RenderResult Renderer::render_dense_bucketed(
 // that encoding, and the shading pass reuses it -- same counts as the march, bit for bit.
 RenderResult Renderer::render_dense(
   const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-  const Tensor & noise, const Tensor & bg_color, const Route & route)
+  const Tensor & noise, const Tensor & bg_color, const Route & route, const Tensor & noise_rows)
 {
   const int n_rays = (int)rays_o.size(0);
   const int S = pts_sampler_->options_.max_samples;
   void * stream = f2n::current_stream(rays_o);
   Hash3DAnchored & field = *scene_field_;
-  SampleResultFlex all = pts_sampler_->get_samples(rays_o, rays_d, noise);
-  const int64_t n_all = all.pts.size(0);
+  // lean: contracted positions (all.x) and one direction per ray; all.pts / all.dirs stay undefined
+  SampleResultFlex all =
+    route.lean ? pts_sampler_->get_samples_dense(rays_o, rays_d, noise, noise_rows, route.noise_raw)
+               : pts_sampler_->get_samples(rays_o, rays_d, noise);
+  const int64_t n_all = all.dt.size(0);
   Tensor contracted_all, enc_all_cm;
   {
     torch::NoGradGuard no_grad;
-    // all.pts is the dense [n_rays, S] grid of the sampler: ray-tile mapping of the encode
-    enc_all_cm = field.encode(all.pts, S, &contracted_all).t();  // [C, n_all] contiguous storage
+    // the dense [n_rays, S] grid of the sampler: ray-tile mapping of the encode
+    if (route.lean) {
+      contracted_all = all.x;
+      enc_all_cm = field.encode_contracted(all.x, S).t();
+    } else {
+      enc_all_cm = field.encode(all.pts, S, &contracted_all).t();  // [C, n_all] contiguous storage
+    }
     TORCH_CHECK(enc_all_cm.is_contiguous(), "encode() must return channel-major storage");
   }
   // The number of survivors sizes everything downstream, so the host has to read it: one blocking
@@ -537,7 +585,22 @@ RenderResult Renderer::render_dense(
     all.pts_idx_bounds = bounds;
     return shade_and_composite(all, emb_idx, mode, bg_color, route, enc_all_cm, contracted_all);
   }
-  SampleResultFlex kept = compact_samples(rays_o, rays_d, noise, bounds, n_kept);
+  // rays terminate: from here on the existing kernels, which take the cooked noise in ray order
+  Tensor noise_k = noise;
+  if (route.lean && noise.defined()) {
+    torch::NoGradGuard no_grad;
+    if (route.noise_raw) noise_k = PtsSampler::cook_noise(noise);
+    if (noise_rows.defined()) {
+      Tensor rows = torch::empty_like(noise_k);
+      f2n::check(
+        f2n_gather_rows(
+          noise_k.data_ptr<float>(), rows.data_ptr<float>(), noise_rows.data_ptr<int32_t>(), n_rays,
+          S, stream),
+        "f2n_gather_rows");
+      noise_k = rows;
+    }
+  }
+  SampleResultFlex kept = compact_samples(rays_o, rays_d, noise_k, bounds, n_kept);
   const int64_t C = enc_all_cm.size(0);
   Tensor enc_kept_cm = torch::empty({C, n_kept}, rays_o.options());
   f2n::check(
@@ -618,15 +681,15 @@ std::optional<RenderResult> Renderer::shade_all_unless_near_threshold(
   const SampleResultFlex & all, const Tensor & emb_idx, RunningMode mode, const Tensor & bg_color,
   const Route & route, const Tensor & enc_cm, const Tensor & contracted)
 {
-  void * stream = f2n::current_stream(all.pts);
-  Tensor near_threshold = torch::zeros({1}, f2n::int_on(all.pts.device()));
+  void * stream = f2n::current_stream(all.dt);
+  Tensor near_threshold = torch::zeros({1}, f2n::int_on(all.dt.device()));
   Shaded shaded = shade(all, emb_idx, mode, route, enc_cm, contracted);
   const int S = pts_sampler_->options_.max_samples;
   const float limit = -std::log(options_.early_stop_trans) - 0.5f;
   f2n::check(
     f2n_density_margin(
       shaded.field_out.data_ptr<float>(), all.dt.data_ptr<float>(),
-      near_threshold.data_ptr<int32_t>(), (int)(all.pts.size(0) / S), S, 3.f, limit, stream),
+      near_threshold.data_ptr<int32_t>(), (int)(all.dt.size(0) / S), S, 3.f, limit, stream),
     "f2n_density_margin");
   survivors_.request(near_threshold, stream);
   RenderResult guess = composite(all, shaded, bg_color, route);
@@ -651,7 +714,7 @@ Renderer::Shaded Renderer::shade(
     return {scene_feat, shade_aten(scene_feat, kept, emb_idx, mode)};
   }
   // hash encode -> one kernel for field head + embedding + SH + colour MLP
-  const int64_t n_kept = kept.pts.size(0);
+  const int64_t n_kept = kept.dt.size(0);
   Tensor enc = enc_cm.defined() ? scene_field_->encode_cached(kept.pts, enc_cm, contracted)
                                 : scene_field_->encode(kept.pts);
   if (route.grad_rays.origins.defined()) {
@@ -670,9 +733,11 @@ Renderer::Shaded Renderer::shade(
   // shape of the samples alone, so every route that hands over the same samples gets the same bits.
   const int64_t n_rays = kept.pts_idx_bounds.size(0), S = pts_sampler_->options_.max_samples;
   if (f2n::shade_rays_applies(n_kept, n_rays, S)) {
+    const bool per_ray = kept.ray_dirs.defined();  // (the lean dense route)
     f2n::ShadeOut sh = f2n::shade_rays(
-      enc, kept.dirs, mode == RunningMode::TRAIN ? emb_idx : Tensor(), S,
-      scene_field_->mlp_->weight, scene_field_->mlp_->bias, mlp[0], mlp[1], mlp[2], mlp[3], emb);
+      enc, per_ray ? kept.ray_dirs : kept.dirs, mode == RunningMode::TRAIN ? emb_idx : Tensor(), S,
+      scene_field_->mlp_->weight, scene_field_->mlp_->bias, mlp[0], mlp[1], mlp[2], mlp[3], emb,
+      per_ray);
     return {sh.logit.unsqueeze(1), sh.rgb};
   }
   Tensor sample_img;
@@ -912,10 +977,11 @@ f2n::TrainStepResult f2n::train_step(
   bool run_backward)
 {
   RenderResult res =
-    renderer.render(rays_o, rays_d, emb_idx, RunningMode::TRAIN, noise, bg_color);
+    renderer.render_for_loss(rays_o, rays_d, emb_idx, RunningMode::TRAIN, noise, bg_color);
   // colour loss + variance loss + squared error in two launches (f2n_loss_fwd; the ATen spelling of
   // the reference, train_manager.cpp:78-96, is ~23 launches of a few microseconds each)
-  Tensor var = CustomOps::WeightVar(res.weights, res.idx_start_end);
+  Tensor var = res.weight_var.defined() ? res.weight_var
+                                        : CustomOps::WeightVar(res.weights, res.idx_start_end);
   // (a zero weight -- the reference's schedule starts there, train_manager.cpp:85-91 -- makes the
   // variance term's gradient exactly zero: its backward kernel is not run at all)
   if (var_loss_weight == 0.f) var = var.detach();

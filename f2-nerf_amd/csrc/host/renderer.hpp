@@ -67,6 +67,9 @@ struct RenderResult
   Tensor depths;
   Tensor weights;
   Tensor idx_start_end;
+  // Renderer::render_for_loss only, and only when it says so: CustomOps::WeightVar of the weights,
+  // [n_rays] in the caller's order; `weights` is then undefined
+  Tensor weight_var;
 };
 
 struct RendererOptions
@@ -143,6 +146,15 @@ public:
     const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
     const Tensor & noise, const Tensor & bg_color);
 
+  // render() for a caller that wants the weights only for their per-ray variance (f2n::train_step):
+  // on the lean bucketed dense route the variance is taken from the weights where they lie and its
+  // [n_rays] result travels back to the caller's order with colours and depths -- no [n, S] gather
+  // either way.  There `weight_var` is defined and `weights` is not; everywhere else this is
+  // render() and `weight_var` is undefined.
+  RenderResult render_for_loss(
+    const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
+    const Tensor & noise, const Tensor & bg_color);
+
   // The no-grad render as one kernel launch (f2n_render_rays): colours [n, 3], depths [n], last_trans
   // [n] (1 - opacity of the ray: an alpha mask) and kept [n] int32 (samples composited per ray).
   // mode, noise and bg_color as in render(); the attached occupancy grid is used.  Requires the fused
@@ -206,6 +218,12 @@ private:
     bool bucketed = false;   // Dense only: render_dense_bucketed instead of the caller's order
     bool fused_net = false;  // the fused per-sample network (f2n::shade) applies
     Rays grad_rays;          // the caller's rays when they carry a gradient, else undefined
+    // Dense only, F2N_OPT_DENSE_LEAN = 0, the ray-uniform network kernels apply and neither rays nor
+    // bg_color carry a gradient: f2n_sample_dense (contracted positions and one direction per ray;
+    // no world positions, no per-sample directions, the noise read in place)
+    bool lean = false;
+    bool noise_raw = false;  // lean: the noise is the renderer's own uniform draw, cooked in the sampler
+    bool want_var = false;   // lean and bucketed, render_for_loss: hand back weight_var, not weights
   };
   // What the shading pass hands to compositing: the field head's output ([n, 1] density logit of the
   // fused network, [n, 16] otherwise) and the colours [n, 3].
@@ -215,6 +233,9 @@ private:
   };
 
   Route choose_route(const Tensor & rays_o, const Tensor & rays_d, const Tensor & bg_color) const;
+  RenderResult render_routed(
+    const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
+    const Tensor & noise, const Tensor & bg_color, bool for_loss);
   bool fused_net_applies() const;
   // f2n_render_rays -- or, by options_.one_pass_head, the head or head + tail -- into preallocated
   // outputs (rows of one chunk)
@@ -230,9 +251,12 @@ private:
   RenderResult render_fused(
     const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
     const Tensor & noise, const Tensor & bg_color, const Route & route);
+  // noise_rows (lean, bucketed): ray r's noise is row noise_rows[r] of `noise`, which stays in the
+  // caller's order
   RenderResult render_dense(
     const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-    const Tensor & noise, const Tensor & bg_color, const Route & route);
+    const Tensor & noise, const Tensor & bg_color, const Route & route,
+    const Tensor & noise_rows = Tensor());
   RenderResult render_dense_bucketed(
     const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
     const Tensor & noise, const Tensor & bg_color, const Route & route);

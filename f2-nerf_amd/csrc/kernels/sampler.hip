@@ -57,6 +57,55 @@ __global__ __launch_bounds__(F2N_BLOCK) void sample_rays_kernel(
   }
 }
 
+// ---- f2n_sample_dense ---------------------------------------------------------------------------
+// sample_rays_kernel for a dense grid that goes straight to the encode: the contracted position is
+// written instead of the world position (contract_point on the registers make_stride filled: what
+// f2n_contract_fwd computes from the stored point), the direction once per ray instead of once per
+// sample, and the noise row is read where it lies -- through `noise_row` when the rays were
+// reordered, and as the raw uniform draw u when `affine` (the step multiplier (u - .5f) + 1.f, two
+// f32 roundings as the two ATen passes of PtsSampler::draw_noise make them).
+__global__ __launch_bounds__(F2N_BLOCK) void sample_dense_kernel(
+  const float * __restrict__ rays_o, const float * __restrict__ rays_d,
+  const float * __restrict__ noise, const int32_t * __restrict__ noise_row, int affine,
+  float * __restrict__ x, float * __restrict__ dt, float * __restrict__ t,
+  int32_t * __restrict__ bounds, float * __restrict__ ray_dirs, int n_rays, int S, float step)
+{
+  const int r = ray_of_wave();
+  if (r >= n_rays) return;
+  const int lane = lane_id();
+  const RayFrame rf = load_ray(rays_o, rays_d, r);
+  // (a map entry outside [0, n_rays) is clamped: no read leaves the noise array)
+  const int nr = noise_row ? min(max(noise_row[r], 0), n_rays - 1) : r;
+  const float * nrow = noise ? noise + (int64_t)nr * S : nullptr;
+  StrideCarry carry = {0.f, 0.f, 0.f, 0.f};
+  const int64_t base = (int64_t)r * S;
+  for (int k0 = 0; k0 < S; k0 += F2N_WAVE) {
+    float nz = 0.f;
+    if (nrow && k0 + lane < S) {
+      nz = nrow[k0 + lane];
+      if (affine) nz = (nz - .5f) + 1.f;
+    }
+    const StrideSample sm = make_stride_from(rf, nrow != nullptr, nz, k0, S, step, carry, lane);
+    if (sm.valid) {
+      const int64_t i = base + k0 + lane;
+      float cx = sm.px, cy = sm.py, cz = sm.pz;
+      contract_point(cx, cy, cz);
+      x[3 * i] = cx;
+      x[3 * i + 1] = cy;
+      x[3 * i + 2] = cz;
+      dt[i] = sm.dt;
+      t[i] = sm.t;
+    }
+  }
+  if (lane == 0) {
+    bounds[2 * r] = (int32_t)base;
+    bounds[2 * r + 1] = (int32_t)(base + S);
+    ray_dirs[3 * r] = rf.dx;
+    ray_dirs[3 * r + 1] = rf.dy;
+    ray_dirs[3 * r + 2] = rf.dz;
+  }
+}
+
 // ---- f2n_sample_compact -------------------------------------------------------------------------
 
 __global__ __launch_bounds__(F2N_BLOCK) void sample_compact_kernel(
@@ -688,6 +737,22 @@ extern "C" int f2n_sample_rays(
   hipLaunchKernelGGL(
     sample_rays_kernel, dim3(f2n_div_up(n_rays, F2N_WAVES_PER_BLOCK)), dim3(F2N_BLOCK), 0,
     (hipStream_t)stream, rays_o, rays_d, noise, pts, dirs, dt, t, bounds, n_rays, S, step);
+  return f2n_launch_status();
+}
+
+extern "C" int f2n_sample_dense(
+  const float * rays_o, const float * rays_d, const float * noise, const int32_t * noise_row,
+  int noise_affine, float * x, float * dt, float * t, int32_t * bounds, float * ray_dirs,
+  int n_rays, int S, float step, void * stream)
+{
+  if (n_rays < 0 || S < 1 || (noise_affine != 0 && noise_affine != 1)) return F2N_E_INVALID_ARG;
+  if ((int64_t)n_rays * S > INT32_MAX) return F2N_E_INVALID_ARG;  // bounds are int32
+  if (n_rays == 0) return F2N_OK;
+  if (!rays_o || !rays_d || !x || !dt || !t || !bounds || !ray_dirs) return F2N_E_INVALID_ARG;
+  hipLaunchKernelGGL(
+    sample_dense_kernel, dim3(f2n_div_up(n_rays, F2N_WAVES_PER_BLOCK)), dim3(F2N_BLOCK), 0,
+    (hipStream_t)stream, rays_o, rays_d, noise, noise_row, noise_affine, x, dt, t, bounds, ray_dirs,
+    n_rays, S, step);
   return f2n_launch_status();
 }
 

@@ -546,10 +546,11 @@ extern "C" int f2n_shade_bwd(
 
 // ---- the ray-uniform forms (shade_mfma.hip): a dense [n_rays, S] grid of samples, S % 64 == 0
 
-extern "C" int f2n_shade_fwd_rays(
+static int shade_fwd_rays_any(
   const float * enc_cm, int C, const float * dirs, const int32_t * ray_img, const float * w_h,
   const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
-  const float * app_emb, float * logit, float * rgb, int n_rays, int S, void * stream)
+  const float * app_emb, float * logit, float * rgb, int n_rays, int S, bool dir_per_ray,
+  void * stream)
 {
   if (n_rays < 0 || S <= 0 || S % 64 != 0) return F2N_E_INVALID_ARG;
   if (C != 8 && C != 16 && C != 32 && C != 64) return F2N_E_UNSUPPORTED;
@@ -559,15 +560,35 @@ extern "C" int f2n_shade_fwd_rays(
   if (!f2n_detail::shade_bwd_mfma_supports(C, (int64_t)n_rays * S)) return F2N_E_UNSUPPORTED;
   return f2n_detail::launch_shade_fwd_mfma_rays(
     enc_cm, C, dirs, ray_img, w_h, b_h, w1, b1, w2, b2, app_emb, logit, rgb, n_rays, S,
-    (hipStream_t)stream);
+    dir_per_ray, (hipStream_t)stream);
 }
 
-extern "C" int f2n_shade_bwd_rays(
+extern "C" int f2n_shade_fwd_rays(
+  const float * enc_cm, int C, const float * dirs, const int32_t * ray_img, const float * w_h,
+  const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
+  const float * app_emb, float * logit, float * rgb, int n_rays, int S, void * stream)
+{
+  return shade_fwd_rays_any(
+    enc_cm, C, dirs, ray_img, w_h, b_h, w1, b1, w2, b2, app_emb, logit, rgb, n_rays, S, false,
+    stream);
+}
+
+extern "C" int f2n_shade_fwd_raydirs(
+  const float * enc_cm, int C, const float * ray_dirs, const int32_t * ray_img, const float * w_h,
+  const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
+  const float * app_emb, float * logit, float * rgb, int n_rays, int S, void * stream)
+{
+  return shade_fwd_rays_any(
+    enc_cm, C, ray_dirs, ray_img, w_h, b_h, w1, b1, w2, b2, app_emb, logit, rgb, n_rays, S, true,
+    stream);
+}
+
+static int shade_bwd_rays_any(
   const float * enc_cm, int C, const float * dirs, const int32_t * ray_img, const float * w_h,
   const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
   const float * app_emb, const float * d_logit, const float * d_rgb, float * d_enc_cm,
   float * g_w_h, float * g_b_h, float * g_w1, float * g_b1, float * g_w2, float * g_b2,
-  float * g_app_emb, int n_rays, int S, void * stream)
+  float * g_app_emb, int n_rays, int S, bool dir_per_ray, void * stream)
 {
   if (n_rays < 0 || S <= 0 || S % 64 != 0) return F2N_E_INVALID_ARG;
   if (C != 8 && C != 16 && C != 32 && C != 64) return F2N_E_UNSUPPORTED;
@@ -579,5 +600,29 @@ extern "C" int f2n_shade_bwd_rays(
   if (!f2n_detail::shade_bwd_mfma_supports(C, (int64_t)n_rays * S)) return F2N_E_UNSUPPORTED;
   return f2n_detail::launch_shade_bwd_mfma_rays(
     enc_cm, C, dirs, ray_img, w_h, b_h, w1, b1, w2, b2, app_emb, d_logit, d_rgb, d_enc_cm, g_w_h,
-    g_b_h, g_w1, g_b1, g_w2, g_b2, g_app_emb, n_rays, S, (hipStream_t)stream);
+    g_b_h, g_w1, g_b1, g_w2, g_b2, g_app_emb, n_rays, S, dir_per_ray, (hipStream_t)stream);
+}
+
+extern "C" int f2n_shade_bwd_rays(
+  const float * enc_cm, int C, const float * dirs, const int32_t * ray_img, const float * w_h,
+  const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
+  const float * app_emb, const float * d_logit, const float * d_rgb, float * d_enc_cm,
+  float * g_w_h, float * g_b_h, float * g_w1, float * g_b1, float * g_w2, float * g_b2,
+  float * g_app_emb, int n_rays, int S, void * stream)
+{
+  return shade_bwd_rays_any(
+    enc_cm, C, dirs, ray_img, w_h, b_h, w1, b1, w2, b2, app_emb, d_logit, d_rgb, d_enc_cm, g_w_h,
+    g_b_h, g_w1, g_b1, g_w2, g_b2, g_app_emb, n_rays, S, false, stream);
+}
+
+extern "C" int f2n_shade_bwd_raydirs(
+  const float * enc_cm, int C, const float * ray_dirs, const int32_t * ray_img, const float * w_h,
+  const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
+  const float * app_emb, const float * d_logit, const float * d_rgb, float * d_enc_cm,
+  float * g_w_h, float * g_b_h, float * g_w1, float * g_b1, float * g_w2, float * g_b2,
+  float * g_app_emb, int n_rays, int S, void * stream)
+{
+  return shade_bwd_rays_any(
+    enc_cm, C, ray_dirs, ray_img, w_h, b_h, w1, b1, w2, b2, app_emb, d_logit, d_rgb, d_enc_cm,
+    g_w_h, g_b_h, g_w1, g_b1, g_w2, g_b2, g_app_emb, n_rays, S, true, stream);
 }

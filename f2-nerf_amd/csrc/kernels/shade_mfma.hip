@@ -189,7 +189,7 @@ __device__ __forceinline__ void shade_bwd_mfma_body(
   const float * __restrict__ d_logit, const float * __restrict__ d_rgb, float * __restrict__ d_enc,
   float * __restrict__ g_w_h, float * __restrict__ g_b_h, float * __restrict__ g_w1,
   float * __restrict__ g_b1, float * __restrict__ g_w2, float * __restrict__ g_b2,
-  float * __restrict__ g_emb, int64_t n, int n_per_ray)
+  float * __restrict__ g_emb, int64_t n, int n_per_ray, int dir_per_ray)
 {
   using S = MShape<C, TS>;
   constexpr int kS1 = S::kS1, kM6 = S::kM6, kP = S::kP, kStride = S::kStride;
@@ -318,13 +318,16 @@ __device__ __forceinline__ void shade_bwd_mfma_body(
       for (int t = 0; t < kS1; t++)
 #pragma unroll
         for (int T = 0; T < TS; T++) eB_[t][T] = ld_row(enc + (int64_t)t * n, (sc + 16 * T + m) * 4 + cE);
+      // the stride's ray (a scalar): its image id, and its row of a per-ray `dirs`
+      const uint32_t ray = (has_emb || dir_per_ray) ? sc / (uint32_t)n_per_ray : 0u;
       if (has_emb) {
-        const int id = sample_img[sc / (uint32_t)n_per_ray];
+        const int id = sample_img[ray];
 #pragma unroll
         for (int T = 0; T < TS; T++) img_[T] = id;
       }
+      const int64_t drow = dir_per_ray ? (int64_t)ray : (int64_t)sc;
 #pragma unroll
-      for (int k = 0; k < 3; k++) dir_[k] = dirs[(int64_t)sc * 3 + k];
+      for (int k = 0; k < 3; k++) dir_[k] = dirs[drow * 3 + k];
       return;
     }
     uint32_t off_[TS];
@@ -879,15 +882,16 @@ template <int C, int V, bool WIDE, int TS>
 __global__ __launch_bounds__((MShape<C, TS>::kWaves * 64)) void shade_bwd_mfma_kernel(
   F2N_SHADE_BWD_PARAMS(sample_img), int64_t n)
 {
-  shade_bwd_mfma_body<C, V, WIDE, TS, false>(F2N_SHADE_BWD_ARGS(sample_img), n, 0);
+  shade_bwd_mfma_body<C, V, WIDE, TS, false>(F2N_SHADE_BWD_ARGS(sample_img), n, 0, 0);
 }
 
-// ray-uniform form: n = n_rays * S samples in ray-major order, S % 64 == 0, one image id per ray
+// ray-uniform form: n = n_rays * S samples in ray-major order, S % 64 == 0, one image id per ray;
+// dir_per_ray: `dirs` is [n_rays, 3], one row per ray (0: [n, 3], the row of the stride's first sample)
 template <int C, int V, bool WIDE, int TS>
 __global__ __launch_bounds__((MShape<C, TS>::kWaves * 64)) void shade_bwd_mfma_rays_kernel(
-  F2N_SHADE_BWD_PARAMS(ray_img), int64_t n, int S)
+  F2N_SHADE_BWD_PARAMS(ray_img), int64_t n, int S, int dir_per_ray)
 {
-  shade_bwd_mfma_body<C, V, WIDE, TS, true>(F2N_SHADE_BWD_ARGS(ray_img), n, S);
+  shade_bwd_mfma_body<C, V, WIDE, TS, true>(F2N_SHADE_BWD_ARGS(ray_img), n, S, dir_per_ray);
 }
 #undef F2N_SHADE_BWD_PARAMS
 #undef F2N_SHADE_BWD_ARGS
@@ -914,7 +918,7 @@ __device__ __forceinline__ void shade_fwd_mfma_body(
   const float * __restrict__ p_b_h, const float * __restrict__ p_w1,
   const float * __restrict__ p_b1, const float * __restrict__ p_w2,
   const float * __restrict__ p_b2, const float * __restrict__ p_emb, float * __restrict__ logit,
-  float * __restrict__ rgb, float * __restrict__ pre_out, int64_t n, int n_per_ray)
+  float * __restrict__ rgb, float * __restrict__ pre_out, int64_t n, int n_per_ray, int dir_per_ray)
 {
   using S = FShape<C, W>;
   constexpr int kS1 = S::kS1, kP = S::kP;
@@ -953,9 +957,11 @@ __device__ __forceinline__ void shade_fwd_mfma_body(
     int img[4] = {0, 0, 0, 0};
     float dir[3];
     if constexpr (RAYS) {
-      if (has_emb) img[0] = sample_img[(uint32_t)s0 / (uint32_t)n_per_ray];
+      const uint32_t ray = (has_emb || dir_per_ray) ? (uint32_t)s0 / (uint32_t)n_per_ray : 0u;
+      if (has_emb) img[0] = sample_img[ray];
+      const int64_t drow = dir_per_ray ? (int64_t)ray : s0;
 #pragma unroll
-      for (int k = 0; k < 3; k++) dir[k] = dirs[s0 * 3 + k];
+      for (int k = 0; k < 3; k++) dir[k] = dirs[drow * 3 + k];
     } else {
       if (has_emb) {
 #pragma unroll
@@ -1092,16 +1098,18 @@ __global__ __launch_bounds__(W * 64) void shade_fwd_mfma_kernel(
   F2N_SHADE_FWD_PARAMS(sample_img), float * __restrict__ pre_out, int64_t n)
 {
   shade_fwd_mfma_body<C, WIDE, W, false>(
-    enc, dirs, sample_img, p_w_h, p_b_h, p_w1, p_b1, p_w2, p_b2, p_emb, logit, rgb, pre_out, n, 0);
+    enc, dirs, sample_img, p_w_h, p_b_h, p_w1, p_b1, p_w2, p_b2, p_emb, logit, rgb, pre_out, n, 0, 0);
 }
 
-// ray-uniform form: n = n_rays * S samples in ray-major order, S % 64 == 0, one image id per ray
+// ray-uniform form: n = n_rays * S samples in ray-major order, S % 64 == 0, one image id per ray;
+// dir_per_ray as in shade_bwd_mfma_rays_kernel
 template <int C, bool WIDE, int W>
 __global__ __launch_bounds__(W * 64) void shade_fwd_mfma_rays_kernel(
-  F2N_SHADE_FWD_PARAMS(ray_img), int64_t n, int S)
+  F2N_SHADE_FWD_PARAMS(ray_img), int64_t n, int S, int dir_per_ray)
 {
   shade_fwd_mfma_body<C, WIDE, W, true>(
-    enc, dirs, ray_img, p_w_h, p_b_h, p_w1, p_b1, p_w2, p_b2, p_emb, logit, rgb, nullptr, n, S);
+    enc, dirs, ray_img, p_w_h, p_b_h, p_w1, p_b1, p_w2, p_b2, p_emb, logit, rgb, nullptr, n, S,
+    dir_per_ray);
 }
 #undef F2N_SHADE_FWD_PARAMS
 
@@ -1122,13 +1130,14 @@ bool shade_bwd_mfma_supports(int C, int64_t n)
 }
 
 // S = 0: the per-sample kernels (img = one id per sample); S > 0: the ray-uniform kernels
-// (img = one id per ray, n = n_rays * S).  The same choice of form (TS, fences, WIDE) for both.
+// (img = one id per ray, n = n_rays * S; dir_per_ray: dirs [n_rays, 3] instead of [n, 3]).  The same
+// choice of form (TS, fences, WIDE) for both.
 static int launch_shade_bwd_mfma_any(
   const float * enc_cm, int C, const float * dirs, const int32_t * img, const float * w_h,
   const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
   const float * app_emb, const float * d_logit, const float * d_rgb, float * d_enc_cm,
   float * g_w_h, float * g_b_h, float * g_w1, float * g_b1, float * g_w2, float * g_b2,
-  float * g_app_emb, int64_t n, int S, hipStream_t stream)
+  float * g_app_emb, int64_t n, int S, int dir_per_ray, hipStream_t stream)
 {
   // the embedding rows are read as float4
   if (app_emb && (reinterpret_cast<uintptr_t>(app_emb) & 15u)) return F2N_E_INVALID_ARG;
@@ -1155,7 +1164,7 @@ static int launch_shade_bwd_mfma_any(
         hipLaunchKernelGGL(                                                                          \
           (shade_bwd_mfma_rays_kernel<CC, VV, WW, TT>), dim3(grid), dim3(MS::kWaves * 64), 0,        \
           stream, enc_cm, dirs, img, w_h, b_h, w1, b1, w2, b2, app_emb, d_logit, d_rgb, d_enc_cm,    \
-          g_w_h, g_b_h, g_w1, g_b1, g_w2, g_b2, g_app_emb, n, S);                                    \
+          g_w_h, g_b_h, g_w1, g_b1, g_w2, g_b2, g_app_emb, n, S, dir_per_ray);                       \
     } else                                                                                           \
       hipLaunchKernelGGL(                                                                            \
         (shade_bwd_mfma_kernel<CC, VV, WW, TT>), dim3(grid), dim3(MS::kWaves * 64), 0, stream,       \
@@ -1191,7 +1200,7 @@ int launch_shade_bwd_mfma(
 {
   return launch_shade_bwd_mfma_any(
     enc_cm, C, dirs, sample_img, w_h, b_h, w1, b1, w2, b2, app_emb, d_logit, d_rgb, d_enc_cm, g_w_h,
-    g_b_h, g_w1, g_b1, g_w2, g_b2, g_app_emb, n, 0, stream);
+    g_b_h, g_w1, g_b1, g_w2, g_b2, g_app_emb, n, 0, 0, stream);
 }
 
 int launch_shade_bwd_mfma_rays(
@@ -1199,12 +1208,12 @@ int launch_shade_bwd_mfma_rays(
   const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
   const float * app_emb, const float * d_logit, const float * d_rgb, float * d_enc_cm,
   float * g_w_h, float * g_b_h, float * g_w1, float * g_b1, float * g_w2, float * g_b2,
-  float * g_app_emb, int n_rays, int S, hipStream_t stream)
+  float * g_app_emb, int n_rays, int S, bool dir_per_ray, hipStream_t stream)
 {
   if (S <= 0 || S % 64 != 0 || n_rays <= 0) return F2N_E_INVALID_ARG;
   return launch_shade_bwd_mfma_any(
     enc_cm, C, dirs, ray_img, w_h, b_h, w1, b1, w2, b2, app_emb, d_logit, d_rgb, d_enc_cm, g_w_h,
-    g_b_h, g_w1, g_b1, g_w2, g_b2, g_app_emb, (int64_t)n_rays * S, S, stream);
+    g_b_h, g_w1, g_b1, g_w2, g_b2, g_app_emb, (int64_t)n_rays * S, S, dir_per_ray ? 1 : 0, stream);
 }
 
 
@@ -1213,7 +1222,7 @@ static int launch_shade_fwd_mfma_any(
   const float * enc_cm, int C, const float * dirs, const int32_t * img, const float * w_h,
   const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
   const float * app_emb, float * logit, float * rgb, float * pre_cm, int64_t n, int S,
-  hipStream_t stream)
+  int dir_per_ray, hipStream_t stream)
 {
   const int64_t n_strides = (n + 63) / 64;
   if (app_emb && (reinterpret_cast<uintptr_t>(app_emb) & 15u)) return F2N_E_INVALID_ARG;
@@ -1227,7 +1236,7 @@ static int launch_shade_fwd_mfma_any(
     if (S > 0)                                                                                     \
       hipLaunchKernelGGL(                                                                          \
         (shade_fwd_mfma_rays_kernel<CC, WW, KW>), dim3(grid), dim3(kW * 64), 0, stream, enc_cm,    \
-        dirs, img, w_h, b_h, w1, b1, w2, b2, app_emb, logit, rgb, n, S);                           \
+        dirs, img, w_h, b_h, w1, b1, w2, b2, app_emb, logit, rgb, n, S, dir_per_ray);              \
     else                                                                                           \
       hipLaunchKernelGGL(                                                                          \
         (shade_fwd_mfma_kernel<CC, WW, KW>), dim3(grid), dim3(kW * 64), 0, stream, enc_cm, dirs,   \
@@ -1256,18 +1265,20 @@ int launch_shade_fwd_mfma(
   const float * app_emb, float * logit, float * rgb, float * pre_cm, int64_t n, hipStream_t stream)
 {
   return launch_shade_fwd_mfma_any(
-    enc_cm, C, dirs, sample_img, w_h, b_h, w1, b1, w2, b2, app_emb, logit, rgb, pre_cm, n, 0, stream);
+    enc_cm, C, dirs, sample_img, w_h, b_h, w1, b1, w2, b2, app_emb, logit, rgb, pre_cm, n, 0, 0,
+    stream);
 }
 
 int launch_shade_fwd_mfma_rays(
   const float * enc_cm, int C, const float * dirs, const int32_t * ray_img, const float * w_h,
   const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
-  const float * app_emb, float * logit, float * rgb, int n_rays, int S, hipStream_t stream)
+  const float * app_emb, float * logit, float * rgb, int n_rays, int S, bool dir_per_ray,
+  hipStream_t stream)
 {
   if (S <= 0 || S % 64 != 0 || n_rays <= 0) return F2N_E_INVALID_ARG;
   return launch_shade_fwd_mfma_any(
     enc_cm, C, dirs, ray_img, w_h, b_h, w1, b1, w2, b2, app_emb, logit, rgb, nullptr,
-    (int64_t)n_rays * S, S, stream);
+    (int64_t)n_rays * S, S, dir_per_ray ? 1 : 0, stream);
 }
 
 }  // namespace f2n_detail

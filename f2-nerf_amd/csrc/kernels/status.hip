@@ -15,7 +15,8 @@ bool option_value_ok(int key, int value)
     case F2N_OPT_BWD_COMBINE:
     case F2N_OPT_BWD_PHASES:
     case F2N_OPT_RAY_ORDER:
-    case F2N_OPT_SHADE_RAYS: return value == 0 || value == 1;
+    case F2N_OPT_SHADE_RAYS:
+    case F2N_OPT_DENSE_LEAN: return value == 0 || value == 1;
     case F2N_OPT_MARCH: return value >= 0 && value <= 2;
     case F2N_OPT_SHADE_BWD_WAVES: return value >= 0 && value <= 3;
     case F2N_OPT_SHADE_VARIANT: return value >= 0 && value <= 3;

@@ -79,7 +79,16 @@ const char * f2n_status_string(int status);
                                   samples with S % 64 == 0: 0 the ray-uniform kernels
                                   (f2n_shade_fwd_rays / f2n_shade_bwd_rays), 1 always the per-sample
                                   kernels; same logit bit for bit, everything else within rounding    */
-#define F2N_OPT_COUNT 12
+#define F2N_OPT_DENSE_LEAN 12   /* Renderer, dense first pass with the ray-uniform network kernels and
+                                  no gradient into rays or bg_color: 0 one sampler kernel writes the
+                                  contracted positions and one direction per ray (f2n_sample_dense,
+                                  f2n_shade_*_raydirs; no world positions, no per-sample directions,
+                                  the noise read raw and in place), train_step takes the weight
+                                  variance in bucketed order and undefined gradients are not
+                                  materialised as zeros; 1 f2n_sample_rays + f2n_contract_fwd and the
+                                  per-sample arrays; same results bit for bit (network parameter
+                                  gradients: within the order of their float atomics)               */
+#define F2N_OPT_COUNT 13
 int f2n_set_option(int key, int value);
 int f2n_get_option(int key);
 
@@ -315,6 +324,24 @@ int f2n_sample_rays(
   const float * rays_o, const float * rays_d, const float * noise, float * pts, float * dirs,
   float * dt, float * t, int32_t * bounds, int n_rays, int S, float step, void * stream);
 
+/* f2n_sample_rays followed by f2n_contract_fwd for a dense grid that goes straight to the hash
+ * encode and the ray-uniform network kernels -- src/points_sampler.cpp:20-64 and the contraction of
+ * src/hash_3d_anchored.cpp:79-82 -- without the arrays only those two steps exchange:
+ *   noise      [n_rays, S] f32 or NULL (all ones), as f2n_sample_rays
+ *   noise_row  [n_rays] i32 or NULL: ray r reads row noise_row[r] of `noise` (rays reordered after
+ *              the noise was drawn; an entry outside [0, n_rays) is clamped); NULL = row r
+ *   noise_affine 1: `noise` holds the uniform draw u in [0, 1) and the step multiplier is
+ *              (u - .5f) + 1.f, rounded twice as the two ATen passes of src/points_sampler.cpp:35
+ *              round it; 0: `noise` holds the multiplier
+ *   outputs    x [n_rays*S, 3] CONTRACTED positions (f2n_contract_fwd of f2n_sample_rays' pts, bit for
+ *              bit), dt, t [n_rays*S] and bounds [n_rays, 2] as f2n_sample_rays, ray_dirs [n_rays, 3]
+ *              the unit direction of each ray (every row of f2n_sample_rays' dirs for that ray)
+ * No world positions and no per-sample directions are written. */
+int f2n_sample_dense(
+  const float * rays_o, const float * rays_d, const float * noise, const int32_t * noise_row,
+  int noise_affine, float * x, float * dt, float * t, int32_t * bounds, float * ray_dirs,
+  int n_rays, int S, float step, void * stream);
+
 /* Early-stop pass of Renderer::render fused into one march -- src/renderer.cpp:58-90 together with
  * src/points_sampler.cpp:20-64, src/hash_3d_anchored.cpp:79-86 (contraction, hash encode, row 0 of the
  * Linear) and src/CustomOps/CustomOps.cpp:10-14 (TruncExp fwd).  One wavefront walks one ray in 64-sample
@@ -537,6 +564,22 @@ int f2n_shade_fwd_rays(
  * order (d w1[:, 16:32] is summed over the samples of a stride before it is multiplied by SH(dir)). */
 int f2n_shade_bwd_rays(
   const float * enc_cm, int C, const float * dirs, const int32_t * ray_img, const float * w_h,
+  const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
+  const float * app_emb, const float * d_logit, const float * d_rgb, float * d_enc_cm,
+  float * g_w_h, float * g_b_h, float * g_w1, float * g_b1, float * g_w2, float * g_b2,
+  float * g_app_emb, int n_rays, int S, void * stream);
+
+/* f2n_shade_fwd_rays / f2n_shade_bwd_rays with ONE direction row per ray: ray_dirs [n_rays, 3] (what
+ * f2n_sample_dense writes) in place of the per-sample [n, 3] array, addressed per stride as ray_img
+ * is.  Same kernels (a scalar argument selects the row), same arguments otherwise, same status codes,
+ * and for equal directions the same bits as those entries. */
+int f2n_shade_fwd_raydirs(
+  const float * enc_cm, int C, const float * ray_dirs, const int32_t * ray_img, const float * w_h,
+  const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
+  const float * app_emb, float * logit, float * rgb, int n_rays, int S, void * stream);
+
+int f2n_shade_bwd_raydirs(
+  const float * enc_cm, int C, const float * ray_dirs, const int32_t * ray_img, const float * w_h,
   const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
   const float * app_emb, const float * d_logit, const float * d_rgb, float * d_enc_cm,
   float * g_w_h, float * g_b_h, float * g_w1, float * g_b1, float * g_w2, float * g_b2,
