@@ -65,6 +65,11 @@ py::tuple result_tuple(const RenderResult & r)
   return py::make_tuple(r.colors, r.depths, r.weights, r.idx_start_end);
 }
 
+c10::optional<Tensor> tensor_or_none(const Tensor & t)
+{
+  return t.defined() ? c10::optional<Tensor>(t) : c10::nullopt;
+}
+
 struct AdamHandle
 {
   std::shared_ptr<torch::optim::Optimizer> opt;
@@ -88,6 +93,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
   m.def("flex_sum", &FlexOps::Sum, "FlexOps::Sum(val, idx_start_end)");
   m.def("flex_accumulate_sum", &FlexOps::AccumulateSum, "FlexOps::AccumulateSum");
   m.def("weight_var", &CustomOps::WeightVar, "CustomOps::WeightVar");
+  m.def("weight_dist", &CustomOps::WeightDist, "CustomOps::WeightDist(weights, t, dt, idx_start_end)");
   m.def("scatter_add", &CustomOps::ScatterAdd, "CustomOps::ScatterAdd(emb, idx, to_add)");
   m.def("scatter_idx", &CustomOps::ScatterIdx, "CustomOps::ScatterIdx(n_all, idx_start_end, emb_idx)");
   m.def("trunc_exp", [](const Tensor & x) { return torch::autograd::TruncExp::apply(x)[0]; });
@@ -278,6 +284,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
       py::arg("rays_o"), py::arg("rays_d"), py::arg("emb_idx") = py::none(),
       py::arg("mode") = "validate", py::arg("noise") = py::none(), py::arg("bg_color") = py::none())
     .def(
+      "render_for_loss",
+      [](Renderer & r, const Tensor & o, const Tensor & d, const c10::optional<Tensor> & emb_idx,
+         const std::string & mode, const c10::optional<Tensor> & noise,
+         const c10::optional<Tensor> & bg, bool want_dist) {
+        RenderResult res;
+        {
+          py::gil_scoped_release no_gil;
+          res = r.render_for_loss(
+            o, d, opt_tensor(emb_idx), parse_mode(mode), opt_tensor(noise), opt_tensor(bg), want_dist);
+        }
+        return py::make_tuple(
+          res.colors, res.depths, tensor_or_none(res.weights), res.idx_start_end,
+          tensor_or_none(res.weight_var), tensor_or_none(res.weight_dist));
+      },
+      py::arg("rays_o"), py::arg("rays_d"), py::arg("emb_idx") = py::none(),
+      py::arg("mode") = "train", py::arg("noise") = py::none(), py::arg("bg_color") = py::none(),
+      py::arg("want_dist") = false,
+      "(colors, depths, weights | None, idx_start_end, weight_var | None, weight_dist | None): see "
+      "Renderer::render_for_loss")
+    .def(
       "render_rays",
       [](Renderer & r, const Tensor & o, const Tensor & d, const c10::optional<Tensor> & emb_idx,
          const std::string & mode, const c10::optional<Tensor> & noise,
@@ -303,20 +329,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
       "train_step",
       [](Renderer & r, const Tensor & o, const Tensor & d, const Tensor & emb_idx, const Tensor & gt,
          float var_loss_weight, const c10::optional<Tensor> & noise,
-         const c10::optional<Tensor> & bg, bool backward) {
+         const c10::optional<Tensor> & bg, bool backward, float dist_loss_weight) {
         f2n::TrainStepResult out;
         {
           // loss.backward() runs the autograd engine, which must not be entered holding the GIL
           py::gil_scoped_release no_gil;
           out = f2n::train_step(
-            r, o, d, emb_idx, gt, var_loss_weight, opt_tensor(noise), opt_tensor(bg), backward);
+            r, o, d, emb_idx, gt, var_loss_weight, dist_loss_weight, opt_tensor(noise),
+            opt_tensor(bg), backward);
         }
         return py::make_tuple(out.loss, out.sq_err_sum, out.n_values, out.n_samples);
       },
       py::arg("rays_o"), py::arg("rays_d"), py::arg("emb_idx"), py::arg("gt_colors"),
       py::arg("var_loss_weight") = 0.f, py::arg("noise") = py::none(),
       py::arg("bg_color") = py::none(), py::arg("backward") = true,
-      "reference train_manager.cpp:76-107 without the optimiser step")
+      py::arg("dist_loss_weight") = 0.f,
+      "reference train_manager.cpp:76-107 without the optimiser step; dist_loss_weight > 0 adds the "
+      "distortion loss (its mean: last_dist_loss)")
     .def("named_parameters", [](Renderer & r) { return named_params(r); })
     .def("zero_grad", [](Renderer & r) { r.zero_grad(); })
     .def(
@@ -353,6 +382,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def("set_deferred_check", [](Renderer & r, bool f) { r.options_.deferred_check = f; },
          "no host read in render(): see RendererOptions::deferred_check")
     .def("deferred_check_ok", &Renderer::deferred_check_ok)
+    .def_property_readonly(
+      "last_dist_loss", [](const Renderer & r) { return tensor_or_none(r.last_dist_loss_); },
+      "mean weight_dist of the last train_step with dist_loss_weight != 0 (device scalar) or None")
     .def_readonly("last_kept_fraction", &Renderer::last_kept_fraction_)
     .def_readonly("last_n_samples", &Renderer::last_n_samples_)
     .def_property_readonly("scene_field", [](Renderer & r) { return r.scene_field_; })

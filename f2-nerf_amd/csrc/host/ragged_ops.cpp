@@ -136,6 +136,50 @@ public:
   }
 };
 
+// The distortion loss per ray (f2n_weight_dist_fwd / _bwd; the reference has no such operator, it
+// stands beside WeightVar).  Differentiable in the weights only: t and dt are the sampler's, and
+// sample positions are data on every training route.
+class WeightDistFn : public torch::autograd::Function<WeightDistFn>
+{
+public:
+  static variable_list forward(AutogradContext * ctx, Tensor weights, Tensor t, Tensor dt, Tensor idx)
+  {
+    weights = f2n::dev_f32(weights, "CustomOps::WeightDist weights");
+    t = f2n::dev_f32(t, "CustomOps::WeightDist t");
+    dt = f2n::dev_f32(dt, "CustomOps::WeightDist dt");
+    idx = f2n::dev_i32(idx, "CustomOps::WeightDist idx_start_end");
+    TORCH_CHECK(
+      weights.dim() == 1 && t.numel() == weights.numel() && dt.numel() == weights.numel() &&
+        idx.dim() == 2 && idx.size(1) == 2,
+      "CustomOps::WeightDist expects weights, t, dt [n] and idx_start_end [n_rays, 2]");
+    const int n_rays = (int)idx.size(0);
+    Tensor out = torch::empty({n_rays}, weights.options());
+    f2n::check(
+      f2n_weight_dist_fwd(
+        f2n::fptr(weights), f2n::fptr(t), f2n::fptr(dt), f2n::iptr(idx), out.data_ptr<float>(),
+        n_rays, f2n::current_stream(weights)),
+      "f2n_weight_dist_fwd");
+    ctx->save_for_backward({weights, t, dt, idx});
+    ctx->set_materialize_grads(!f2n::lean_grads());
+    return {out};
+  }
+
+  static variable_list backward(AutogradContext * ctx, variable_list grad_output)
+  {
+    if (!grad_output[0].defined()) return {Tensor(), Tensor(), Tensor(), Tensor()};
+    Tensor d_out = f2n::dev_f32(grad_output[0], "CustomOps::WeightDist grad");
+    auto saved = ctx->get_saved_variables();
+    Tensor &weights = saved[0], &t = saved[1], &dt = saved[2], &idx = saved[3];
+    Tensor dw = torch::zeros_like(weights);
+    f2n::check(
+      f2n_weight_dist_bwd(
+        f2n::fptr(weights), f2n::fptr(t), f2n::fptr(dt), f2n::iptr(idx), f2n::fptr(d_out),
+        dw.data_ptr<float>(), (int)idx.size(0), f2n::current_stream(d_out)),
+      "f2n_weight_dist_bwd");
+    return {dw, Tensor(), Tensor(), Tensor()};
+  }
+};
+
 class ScatterAddFn : public torch::autograd::Function<ScatterAddFn>
 {
 public:
@@ -514,6 +558,13 @@ Tensor FlexOps::AccumulateSum(Tensor val, Tensor idx_start_end, bool include_thi
 Tensor CustomOps::WeightVar(Tensor weights, Tensor idx_start_end)
 {
   return WeightVarFn::apply(weights.contiguous(), idx_start_end.contiguous())[0];
+}
+
+Tensor CustomOps::WeightDist(Tensor weights, Tensor t, Tensor dt, Tensor idx_start_end)
+{
+  return WeightDistFn::apply(
+    weights.contiguous(), t.detach().contiguous(), dt.detach().contiguous(),
+    idx_start_end.contiguous())[0];
 }
 
 Tensor CustomOps::ScatterAdd(Tensor emb, Tensor idx, Tensor to_add)

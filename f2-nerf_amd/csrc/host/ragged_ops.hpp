@@ -1,6 +1,7 @@
 // ragged_ops.hpp -- the reference's free-function operator surface over ragged per-ray runs:
 //   FlexOps::Sum / FlexOps::AccumulateSum          (reference src/CustomOps/FlexOps.hpp:14-20)
 //   CustomOps::WeightVar                           (src/CustomOps/CustomOps.hpp:23-28)
+//   CustomOps::WeightDist                          (no counterpart: the distortion loss beside it)
 //   CustomOps::ScatterAdd / CustomOps::ScatterIdx  (src/CustomOps/Scatter.hpp:16-21)
 //   torch::autograd::TruncExp                      (src/CustomOps/CustomOps.hpp:13-19)
 // Same names, argument meaning and autograd behaviour; the kernels behind them are the wave-per-ray
@@ -30,6 +31,14 @@ torch::Tensor AccumulateSum(torch::Tensor val, torch::Tensor idx_start_end, bool
 namespace CustomOps
 {
 torch::Tensor WeightVar(torch::Tensor weights, torch::Tensor idx_start_end);
+// Not in the reference (it has WeightVar alone, src/CustomOps/CustomOps.cu:13-67, used at
+// src/main_functions/train_manager.cpp:80-93): the interval distortion loss of mip-NeRF 360 per ray,
+//   D_r = sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 dt_i,  m = t - dt / 2  ->  [n_rays]
+// over the kept samples' real positions (t: interval end as the sampler gives it, dt: width; m must
+// not decrease along a ray).  The gradient goes to `weights` only: t and dt are sample positions,
+// which are data on every training route, and receive none.
+torch::Tensor WeightDist(
+  torch::Tensor weights, torch::Tensor t, torch::Tensor dt, torch::Tensor idx_start_end);
 torch::Tensor ScatterAdd(torch::Tensor emb, torch::Tensor idx, torch::Tensor to_add);
 torch::Tensor ScatterIdx(int n_all_pts, torch::Tensor idx_start_end, torch::Tensor emb_idx);
 }  // namespace CustomOps
@@ -84,8 +93,8 @@ ShadeOut shade_rays(
   const Tensor & app_emb, bool dirs_per_ray = false);
 
 // F2N_OPT_DENSE_LEAN = 0: the autograd nodes between the per-ray results and the network
-// (CompositeFn, WeightVarFn, the Renderer's RayUnpermuteFn) take an undefined gradient as undefined
-// -- no zero tensor of n samples is made, gathered and read for it.
+// (CompositeFn, WeightVarFn, WeightDistFn, the Renderer's RayUnpermuteFn) take an undefined gradient
+// as undefined -- no zero tensor of n samples is made, gathered and read for it.
 bool lean_grads();
 
 // n samples form a dense [n_rays, S] grid that shade_rays serves, and no option asks for the

@@ -76,27 +76,33 @@ std::pair<Tensor, Tensor> bounds_from_counts(const Tensor & counts, void * strea
 
 // colors [n,3], depths [n] and weights (ragged) of the bucketed order back into the caller's order:
 // row i of the caller is row inv[i] of the bucketed storage; the backward is the inverse gather
-// (map perm).  `rows`: every ray kept all S samples, the weights are plain [n, S] rows.
+// (map perm).  `rows`: every ray kept all S samples, the weights are plain [n, S] rows.  `per_ray`:
+// one more float per ray that rides along (the distortion loss), or an empty tensor: nothing moves.
 class RayUnpermuteFn : public torch::autograd::Function<RayUnpermuteFn>
 {
 public:
   static torch::autograd::variable_list forward(
     torch::autograd::AutogradContext * ctx, Tensor colors, Tensor depths, Tensor weights,
-    Tensor perm, Tensor inv, Tensor bounds_sorted, Tensor bounds_caller, int64_t S, bool rows)
+    Tensor per_ray, Tensor perm, Tensor inv, Tensor bounds_sorted, Tensor bounds_caller, int64_t S,
+    bool rows)
   {
     colors = f2n::dev_f32(colors, "colors");
     depths = f2n::dev_f32(depths, "depths");
     weights = f2n::dev_f32(weights, "weights");
+    per_ray = f2n::dev_f32(per_ray, "per-ray term");
     const int n = (int)perm.size(0);
+    TORCH_CHECK(per_ray.numel() == 0 || per_ray.numel() == n, "per-ray term shape");
     void * s = f2n::current_stream(colors);
     Tensor c = torch::empty_like(colors), d = torch::empty_like(depths), w = torch::empty_like(weights);
+    Tensor x = torch::empty_like(per_ray);
     gather(colors, depths, weights, c, d, w, inv, bounds_sorted, bounds_caller, n, S, rows, s);
+    gather_per_ray(per_ray, x, inv, n, s);
     ctx->save_for_backward({perm, bounds_sorted, bounds_caller});
     ctx->saved_data["S"] = S;
     ctx->saved_data["rows"] = rows;
     // (the backward gathers the gradients that exist: no zeros made and moved for the others)
     ctx->set_materialize_grads(!f2n::lean_grads());
-    return {c, d, w};
+    return {c, d, w, x};
   }
 
   static torch::autograd::variable_list backward(
@@ -113,12 +119,23 @@ public:
     Tensor dc = gc.defined() ? torch::empty_like(gc) : Tensor();
     Tensor dd = gd.defined() ? torch::empty_like(gd) : Tensor();
     Tensor dw = gw.defined() ? torch::empty_like(gw) : Tensor();
+    Tensor gx = g[3].defined() ? f2n::dev_f32(g[3], "grad per-ray term") : Tensor();
+    Tensor dx = gx.defined() ? torch::empty_like(gx) : Tensor();
     void * s = f2n::current_stream(perm);
     gather(gc, gd, gw, dc, dd, dw, perm, saved[2], saved[1], n, S, rows, s);
-    return {dc, dd, dw, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    if (gx.defined()) gather_per_ray(gx, dx, perm, n, s);
+    return {dc, dd, dw, dx, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
   }
 
 private:
+  static void gather_per_ray(const Tensor & x, Tensor & x_out, const Tensor & map, int n, void * s)
+  {
+    if (x.numel() == 0) return;
+    f2n::check(
+      f2n_gather_rows(f2n::fptr(x), x_out.data_ptr<float>(), map.data_ptr<int32_t>(), n, 1, s),
+      "f2n_gather_rows");
+  }
+
   // dst = src through `map` for each defined pair; segment bounds src_b -> dst_b
   static void gather(
     const Tensor & c, const Tensor & d, const Tensor & w, Tensor & c_out, Tensor & d_out,
@@ -241,19 +258,26 @@ RenderResult Renderer::render(
   const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
   const Tensor & noise_in, const Tensor & bg_in)
 {
-  return render_routed(rays_o, rays_d, emb_idx, mode, noise_in, bg_in, false);
+  return render_routed(rays_o, rays_d, emb_idx, mode, noise_in, bg_in, false, false);
 }
 
 RenderResult Renderer::render_for_loss(
   const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
   const Tensor & noise_in, const Tensor & bg_in)
 {
-  return render_routed(rays_o, rays_d, emb_idx, mode, noise_in, bg_in, true);
+  return render_routed(rays_o, rays_d, emb_idx, mode, noise_in, bg_in, true, false);
+}
+
+RenderResult Renderer::render_for_loss(
+  const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
+  const Tensor & noise_in, const Tensor & bg_in, bool want_dist)
+{
+  return render_routed(rays_o, rays_d, emb_idx, mode, noise_in, bg_in, true, want_dist);
 }
 
 RenderResult Renderer::render_routed(
   const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-  const Tensor & noise_in, const Tensor & bg_in, bool for_loss)
+  const Tensor & noise_in, const Tensor & bg_in, bool for_loss, bool want_dist)
 {
   const int64_t n_rays = rays_o.size(0);
   const auto fopt = f2n::float_on(rays_o.device());
@@ -266,11 +290,15 @@ RenderResult Renderer::render_routed(
                                                    : torch::ones({n_rays, 3}, fopt) * .5f;
   if (n_rays <= 0) {
     record_kept(0);
-    return {bg_color, torch::zeros({n_rays}, fopt), torch::full({n_rays}, 512.f, fopt), Tensor()};
+    RenderResult none{
+      bg_color, torch::zeros({n_rays}, fopt), torch::full({n_rays}, 512.f, fopt), Tensor()};
+    if (want_dist) none.weight_dist = torch::zeros({n_rays}, fopt);
+    return none;
   }
   Route route = choose_route(rays_o, rays_d, bg_color);
   route.noise_raw = route.lean && raw.defined();
   route.want_var = route.lean && route.bucketed && for_loss;
+  route.want_dist = want_dist;
   const Tensor noise = noise_in.defined() ? noise_in
                        : route.noise_raw  ? raw
                                           : PtsSampler::cook_noise(raw);
@@ -379,7 +407,9 @@ RenderResult Renderer::render_op_by_op(
   Tensor colors = FlexOps::Sum(weights.unsqueeze(-1) * sampled_colors, idx) +
                   last_trans.unsqueeze(-1) * bg_color;
   Tensor depths = FlexOps::Sum(weights * sampled_t, idx) / (1.f - last_trans + 1e-4f);
-  return {colors, depths, weights, idx};
+  RenderResult res{colors, depths, weights, idx};
+  if (route.want_dist) res.weight_dist = CustomOps::WeightDist(weights, kept.t, kept.dt, idx);
+  return res;
 }
 
 // ---- fused routes --------------------------------------------------------------------------------
@@ -493,17 +523,20 @@ RenderResult Renderer::render_dense_bucketed(
       "f2n_counts_through");
     bounds = bounds_from_counts(counts, stream).first;
   }
+  // the distortion loss was taken in composite(), where the weights, t and dt of the bucketed order
+  // lie: one float per ray rides back (nothing, when it was not asked for)
+  const Tensor dist = route.want_dist ? r.weight_dist : torch::empty({0}, rays_o.options());
   if (route.want_var) {
     // the variance is a per-ray quantity: taken where the weights lie, its [n_rays] result goes back
     // with colours and depths as rows of one float -- no [n, S] gather forward or backward
     Tensor var = CustomOps::WeightVar(r.weights, r.idx_start_end);
     auto out = RayUnpermuteFn::apply(
-      r.colors, r.depths, var, perm, inv, r.idx_start_end, bounds, /*S=*/1, /*rows=*/true);
-    return {out[0], out[1], Tensor(), bounds, out[2]};
+      r.colors, r.depths, var, dist, perm, inv, r.idx_start_end, bounds, /*S=*/1, /*rows=*/true);
+    return {out[0], out[1], Tensor(), bounds, out[2], route.want_dist ? out[3] : Tensor()};
   }
   auto out = RayUnpermuteFn::apply(
-    r.colors, r.depths, r.weights, perm, inv, r.idx_start_end, bounds, S, rows);
-  return {out[0], out[1], out[2], bounds};
+    r.colors, r.depths, r.weights, dist, perm, inv, r.idx_start_end, bounds, S, rows);
+  return {out[0], out[1], out[2], bounds, Tensor(), route.want_dist ? out[3] : Tensor()};
 }
 
 // Dense first pass: every sample is encoded once (level-major kernel), the keep-prefix comes from
@@ -773,7 +806,12 @@ RenderResult Renderer::composite(
   // ranges tile [0, n))
   f2n::CompositeOut out = f2n::composite(
     shaded.field_out, shaded.rgb, kept.dt, kept.t, kept.pts_idx_bounds, bg_color, route.fused_net);
-  return {out.colors, out.depths, out.weights, kept.pts_idx_bounds};
+  RenderResult res{out.colors, out.depths, out.weights, kept.pts_idx_bounds};
+  // (here the kept samples' weights, t and dt lie side by side on every fused route, thinned by an
+  // occupancy grid or not; t and dt get no gradient)
+  if (route.want_dist)
+    res.weight_dist = CustomOps::WeightDist(out.weights, kept.t, kept.dt, kept.pts_idx_bounds);
+  return res;
 }
 
 // ---- one-pass inference render ---------------------------------------------------------------------
@@ -976,8 +1014,20 @@ f2n::TrainStepResult f2n::train_step(
   const Tensor & gt_colors, float var_loss_weight, const Tensor & noise, const Tensor & bg_color,
   bool run_backward)
 {
-  RenderResult res =
-    renderer.render_for_loss(rays_o, rays_d, emb_idx, RunningMode::TRAIN, noise, bg_color);
+  return train_step(
+    renderer, rays_o, rays_d, emb_idx, gt_colors, var_loss_weight, 0.f, noise, bg_color,
+    run_backward);
+}
+
+f2n::TrainStepResult f2n::train_step(
+  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
+  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
+  const Tensor & bg_color, bool run_backward)
+{
+  // (a zero distortion weight: the term is not computed and the call is the one without it)
+  const bool want_dist = dist_loss_weight != 0.f;
+  RenderResult res = renderer.render_for_loss(
+    rays_o, rays_d, emb_idx, RunningMode::TRAIN, noise, bg_color, want_dist);
   // colour loss + variance loss + squared error in two launches (f2n_loss_fwd; the ATen spelling of
   // the reference, train_manager.cpp:78-96, is ~23 launches of a few microseconds each)
   Tensor var = res.weight_var.defined() ? res.weight_var
@@ -987,6 +1037,12 @@ f2n::TrainStepResult f2n::train_step(
   if (var_loss_weight == 0.f) var = var.detach();
   Tensor stats = f2n::train_loss(res.colors, gt_colors, var, var_loss_weight);  // {loss, c, v, sq}
   Tensor loss = stats[0];
+  renderer.last_dist_loss_ = Tensor();
+  if (want_dist && res.weight_dist.numel() > 0) {
+    Tensor dist_loss = res.weight_dist.mean();
+    loss = loss + dist_loss_weight * dist_loss;
+    renderer.last_dist_loss_ = dist_loss.detach();
+  }
   TrainStepResult out;
   out.loss = loss.detach();
   out.sq_err_sum = stats[3].detach();

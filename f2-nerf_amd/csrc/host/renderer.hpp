@@ -70,6 +70,9 @@ struct RenderResult
   // Renderer::render_for_loss only, and only when it says so: CustomOps::WeightVar of the weights,
   // [n_rays] in the caller's order; `weights` is then undefined
   Tensor weight_var;
+  // Renderer::render_for_loss with want_dist only: CustomOps::WeightDist of the kept samples'
+  // weights, t and dt, [n_rays] in the caller's order, on every route; undefined otherwise
+  Tensor weight_dist;
 };
 
 struct RendererOptions
@@ -154,6 +157,14 @@ public:
   RenderResult render_for_loss(
     const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
     const Tensor & noise, const Tensor & bg_color);
+  // ... and, with want_dist, for their per-ray distortion loss as well: `weight_dist` is defined on
+  // every route (op by op, march, dense, lean bucketed, with an occupancy grid attached), taken where
+  // the kept samples' weights, t and dt lie; on the bucketed routes its [n_rays] result rides back
+  // with colours and depths, nothing per-sample is gathered for it.  t and dt get no gradient (sample
+  // positions are data on every training route).  Everything else is what the call above returns.
+  RenderResult render_for_loss(
+    const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
+    const Tensor & noise, const Tensor & bg_color, bool want_dist);
 
   // The no-grad render as one kernel launch (f2n_render_rays): colours [n, 3], depths [n], last_trans
   // [n] (1 - opacity of the ray: an alpha mask) and kept [n] int32 (samples composited per ray).
@@ -209,6 +220,10 @@ public:
   Tensor deferred_bad_;
   bool deferred_check_ok();
 
+  // mean over the rays of weight_dist in the most recent f2n::train_step with a distortion weight
+  // (device scalar, detached, no host read); undefined after a step without one
+  Tensor last_dist_loss_;
+
 private:
   // Everything the routes branch on, decided once per render() call (choose_route).
   struct Route
@@ -224,6 +239,7 @@ private:
     bool lean = false;
     bool noise_raw = false;  // lean: the noise is the renderer's own uniform draw, cooked in the sampler
     bool want_var = false;   // lean and bucketed, render_for_loss: hand back weight_var, not weights
+    bool want_dist = false;  // render_for_loss: hand back weight_dist too
   };
   // What the shading pass hands to compositing: the field head's output ([n, 1] density logit of the
   // fused network, [n, 16] otherwise) and the colours [n, 3].
@@ -235,7 +251,7 @@ private:
   Route choose_route(const Tensor & rays_o, const Tensor & rays_d, const Tensor & bg_color) const;
   RenderResult render_routed(
     const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-    const Tensor & noise, const Tensor & bg_color, bool for_loss);
+    const Tensor & noise, const Tensor & bg_color, bool for_loss, bool want_dist);
   bool fused_net_applies() const;
   // f2n_render_rays -- or, by options_.one_pass_head, the head or head + tail -- into preallocated
   // outputs (rows of one chunk)
@@ -313,5 +329,15 @@ TrainStepResult train_step(
   Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
   const Tensor & gt_colors, float var_loss_weight, const Tensor & noise, const Tensor & bg_color,
   bool run_backward);
+
+// ... with the distortion loss: loss = colour + var_loss_weight * var_loss + dist_loss_weight *
+// mean_r D_r (CustomOps::WeightDist; the mean is left in Renderer::last_dist_loss_).  A weight of
+// exactly 0 is the call above, launch for launch and bit for bit: the term is neither computed nor
+// differentiated, as for var_loss_weight == 0.  The schedule stays with the caller, like the
+// reference's variance-loss ramp (src/main_functions/train_manager.cpp:85-91).
+TrainStepResult train_step(
+  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
+  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
+  const Tensor & bg_color, bool run_backward);
 
 }  // namespace f2n

@@ -205,6 +205,100 @@ __global__ __launch_bounds__(F2N_BLOCK) void weight_var_bwd_kernel(
   }
 }
 
+// ---- WeightDist ---------------------------------------------------------------------------------
+//
+// The interval distortion loss of a ray (include/f2nerf_hip.h has the definition) in its O(n) form:
+// with m non-decreasing along the ray, x_i = m_i - m_s and the exclusive prefix sums P_i = sum_{j<i}
+// w_j, Q_i = sum_{j<i} w_j x_j,
+//     D   = 2 sum_i w_i (x_i P_i - Q_i) + 1/3 sum_i w_i^2 dt_i
+//     g_i = 2 [(x_i P_i - Q_i) + (Q_tot - Q_<=i) - x_i (P_tot - P_<=i)] + 2/3 w_i dt_i.
+// A 64-sample stride forms its part of P and Q with two DPP scans; two scalar carries link the
+// strides.  No atomics, no LDS: the same bits on every run.
+
+// One stride's sample as the lane sees it: w, dt and the anchored midpoint x (zeros past the end).
+struct DistSample
+{
+  float w, x, dt;
+};
+
+__device__ __forceinline__ DistSample dist_sample(
+  const float * __restrict__ w, const float * __restrict__ t, const float * __restrict__ dt, int i,
+  int e, float m_first)
+{
+  DistSample v = {0.f, 0.f, 0.f};
+  if (i < e) {
+    v.w = w[i];
+    v.dt = dt[i];
+    v.x = (t[i] - 0.5f * v.dt) - m_first;  // 0.5 dt is exact: one rounding for m_i, one for x_i
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(F2N_BLOCK) void weight_dist_fwd_kernel(
+  const float * __restrict__ w, const float * __restrict__ t, const float * __restrict__ dt,
+  const int32_t * __restrict__ idx, float * __restrict__ out, int n_rays)
+{
+  const int r = ray_of_wave();
+  if (r >= n_rays) return;
+  const int lane = lane_id();
+  const int s = idx[2 * r], e = idx[2 * r + 1];
+  if (s >= e) {
+    if (lane == 0) out[r] = 0.f;
+    return;
+  }
+  const float m_first = t[s] - 0.5f * dt[s];
+  float carry_p = 0.f, carry_q = 0.f, pair = 0.f, self = 0.f;
+  for (int c = s; c < e; c += F2N_WAVE) {
+    const DistSample v = dist_sample(w, t, dt, c + lane, e, m_first);
+    const float p_incl = wave_incl_scan(v.w), q_incl = wave_incl_scan(v.w * v.x);
+    const float p = carry_p + wave_shift_up1(p_incl, 0.f);
+    const float q = carry_q + wave_shift_up1(q_incl, 0.f);
+    pair = fmaf(v.w, fmaf(v.x, p, -q), pair);
+    self = fmaf(v.w * v.w, v.dt, self);
+    carry_p += wave_bcast_last(p_incl);
+    carry_q += wave_bcast_last(q_incl);
+  }
+  const float d = fmaf(2.f, wave_sum(pair), wave_sum(self) * (1.f / 3.f));
+  if (lane == 0) out[r] = d;
+}
+
+__global__ __launch_bounds__(F2N_BLOCK) void weight_dist_bwd_kernel(
+  const float * __restrict__ w, const float * __restrict__ t, const float * __restrict__ dt,
+  const int32_t * __restrict__ idx, const float * __restrict__ d_out, float * __restrict__ dw,
+  int n_rays)
+{
+  const int r = ray_of_wave();
+  if (r >= n_rays) return;
+  const int lane = lane_id();
+  const int s = idx[2 * r], e = idx[2 * r + 1];
+  if (s >= e) return;
+  const float m_first = t[s] - 0.5f * dt[s];
+  // the ray's totals first ...
+  float p_tot = 0.f, q_tot = 0.f;
+  for (int c = s; c < e; c += F2N_WAVE) {
+    const DistSample v = dist_sample(w, t, dt, c + lane, e, m_first);
+    p_tot += v.w;
+    q_tot = fmaf(v.w, v.x, q_tot);
+  }
+  p_tot = wave_sum(p_tot);
+  q_tot = wave_sum(q_tot);
+  // ... then the prefix walk: what lies before the sample, and the totals less what lies up to it
+  const float g = d_out[r];
+  float carry_p = 0.f, carry_q = 0.f;
+  for (int c = s; c < e; c += F2N_WAVE) {
+    const int i = c + lane;
+    const DistSample v = dist_sample(w, t, dt, i, e, m_first);
+    const float p_scan = wave_incl_scan(v.w), q_scan = wave_incl_scan(v.w * v.x);
+    const float p = carry_p + wave_shift_up1(p_scan, 0.f), p_incl = carry_p + p_scan;
+    const float q = carry_q + wave_shift_up1(q_scan, 0.f), q_incl = carry_q + q_scan;
+    const float before = fmaf(v.x, p, -q);
+    const float after = (q_tot - q_incl) - v.x * (p_tot - p_incl);
+    if (i < e) dw[i] = g * fmaf(2.f, before + after, (2.f / 3.f) * v.w * v.dt);
+    carry_p += wave_bcast_last(p_scan);
+    carry_q += wave_bcast_last(q_scan);
+  }
+}
+
 inline dim3 ray_grid(int n_rays) { return dim3(f2n_div_up(n_rays, F2N_WAVES_PER_BLOCK)); }
 
 }  // namespace
@@ -278,4 +372,20 @@ extern "C" int f2n_weight_var_bwd(
 {
   if (!idx || !dvars || n_rays < 0) return F2N_E_INVALID_ARG;
   F2N_RAY_LAUNCH(weight_var_bwd_kernel, 0, weights, idx, dvars, dw, n_rays);
+}
+
+extern "C" int f2n_weight_dist_fwd(
+  const float * weights, const float * t, const float * dt, const int32_t * idx, float * out,
+  int n_rays, void * stream)
+{
+  if (!idx || !out || n_rays < 0) return F2N_E_INVALID_ARG;
+  F2N_RAY_LAUNCH(weight_dist_fwd_kernel, 0, weights, t, dt, idx, out, n_rays);
+}
+
+extern "C" int f2n_weight_dist_bwd(
+  const float * weights, const float * t, const float * dt, const int32_t * idx,
+  const float * d_out, float * dw, int n_rays, void * stream)
+{
+  if (!idx || !d_out || !dw || n_rays < 0) return F2N_E_INVALID_ARG;
+  F2N_RAY_LAUNCH(weight_dist_bwd_kernel, 0, weights, t, dt, idx, d_out, dw, n_rays);
 }

@@ -225,6 +225,34 @@ int f2n_weight_var_bwd(
   const float * weights, const int32_t * idx, const float * dvars, float * dw, int n_rays,
   void * stream);
 
+/* The interval distortion loss of mip-NeRF 360 (eq. 15) per ray.  The reference has NO such kernel:
+ * these stand beside its one weight regulariser, WeightVarLoss*Kernel (src/CustomOps/CustomOps.cu:13-67),
+ * and are used where it is used (src/main_functions/train_manager.cpp:80-93).  WeightVar measures the
+ * spread of the weights in sample INDEX (x_i = i/16); with an occupancy grid or jittered steps list
+ * neighbours are no longer equally far apart, and this term works on the samples' real positions.
+ *   weights, t, dt [n] f32: compositing weight, interval END (the raw t, without compositing's
+ *   t_shift) and interval width of every kept sample; midpoint m_k = t_k - dt_k / 2.
+ * For ray r with kept samples [s, e) = idx[r]:
+ *     D_r       = sum_i sum_j w_i w_j |m_i - m_j|  +  1/3 sum_i w_i^2 dt_i       (i, j in [s, e))
+ *     dD_r/dw_i = 2 sum_j w_j |m_i - m_j|  +  2/3 w_i dt_i
+ * PRECONDITION: m is non-decreasing along a ray (the sampler guarantees it, thinned by a grid or
+ * not).  Under it the double sum is evaluated in O(n) by prefix sums over positions taken relative to
+ * the ray's FIRST midpoint (x_i = m_i - m_s, one f32 subtraction each), so a ray that starts far from
+ * the origin pays no cancellation for its offset.  One wavefront per ray, no atomics and no LDS: the
+ * same bits on every run.
+ *   f2n_weight_dist_fwd: out[r] = D_r; an empty ray gives 0.
+ *   f2n_weight_dist_bwd: dw[k] = d_out[r] * dD_r/dw_k for k in ray r's range, nothing is written
+ *     outside the ranges (the caller zeroes dw if it needs zeros there).  Recomputed from the inputs;
+ *     no state is saved by the forward.
+ * t and dt receive no gradient: sample positions are data on every training route.
+ * A null idx or output, or n_rays < 0: F2N_E_INVALID_ARG before any HIP work; n_rays == 0: F2N_OK. */
+int f2n_weight_dist_fwd(
+  const float * weights, const float * t, const float * dt, const int32_t * idx, float * out,
+  int n_rays, void * stream);
+int f2n_weight_dist_bwd(
+  const float * weights, const float * t, const float * dt, const int32_t * idx,
+  const float * d_out, float * dw, int n_rays, void * stream);
+
 /* ------------------------------------------------------------------ scatter (row A9) ---------- */
 
 /* ScatterIdxKernal -- src/CustomOps/Scatter.cu:111-132 */
