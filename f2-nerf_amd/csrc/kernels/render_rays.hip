@@ -11,10 +11,11 @@
 // Mapping: one wavefront per ray (persistent workgroups of kWaves waves walk the ray list), lanes =
 // 64 consecutive samples, as in the march (sampler.hip).  Per stride:
 //   1. make_stride, contract_point, the optional occupancy bit -- the march's;
-//   2. the level loop of density_march[_occ]_kernel.  Its F f16-rounded values per level go two ways:
+//   2. the level loop of the march (density_chain).  Its F f16-rounded values per level go two ways:
 //      into the march's density chain  logit_c = fmaf(enc, w_h[0][c], logit_c)  from b_h[0], same
 //      order, same bits; and into a per-wave f16 LDS tile [C][kPitch], lane = sample;
-//   3. the march's keep decision on logit_c (scan, carry, ballot): the kept set EQUALS the march's;
+//   3. the march's keep decision on logit_c (keep_step: scan, carry, ballot): the kept set EQUALS the
+//      march's;
 //   4. if the stride holds a kept, occupied sample: the tile is read back in the Q-layout of
 //      shade_mfma.hip and the head, hidden and output layers of the ray-uniform forward run on the
 //      matrix cores.  SH16(dir), the embedding row and b1 + w1[:, 16:32] . SH(dir) are formed once
@@ -38,7 +39,6 @@ __global__ __launch_bounds__(RShape<C>::kWaves * 64) void render_rays_kernel(
 {
   using R = RShape<C>;
   using FS = typename R::FS;
-  constexpr int L = C / F, kS1 = FS::kS1, kPitch = R::kPitch;
   __shared__ __attribute__((aligned(16))) float lds_all[R::kLdsFloats];
   float * lds_w = lds_all;
   stage_fwd_weights<C, R::kWaves>(lds_w, p_w_h, p_b_h, p_w1, p_b1, p_w2, p_b2);

@@ -3,23 +3,23 @@
 // render_rays_kernel (render_rays.hip) gives one wavefront to one ray and walks it 64 samples at a
 // time: a ray that keeps three samples still pays a 64-sample stride and a full pass of the network
 // (an 800 x 800 view keeping 3.1 samples per ray: 16x the default route).  Here the HEAD of every ray
-// -- its first n_head samples -- is walked with density_march8_kernel's mapping (sampler.hip): a ray
-// owns half a DPP row, g = lane >> 3 is the ray of the wave, m = lane & 7 the sample of an 8-sample
-// stride.  Replaces the same reference sites as f2n_render_rays: Renderer::render
-// (src/renderer.cpp:33-123) as render_all_rays (:125-151) and Localizer::evaluate_poses
-// (src/localizer.cpp:172) use it.
+// -- its first n_head samples -- is walked with the eight-ray march's mapping (RayLanes<8>,
+// sampler.hiph): a ray owns half a DPP row, g = lane >> 3 is the ray of the wave, m = lane & 7 the
+// sample of an 8-sample stride.  Replaces the same reference sites as f2n_render_rays:
+// Renderer::render (src/renderer.cpp:33-123) as render_all_rays (:125-151) and
+// Localizer::evaluate_poses (src/localizer.cpp:172) use it.
 //
 //   f2n_render_rays_head  per 8-sample stride of 8 rays: sample, contract, occupancy bit, the level
-//     loop with the march's chain logit and the f16 tile (column = lane), the march's keep decision
-//     by half_scan_step (sampler.hiph: the 64-lane scan's additions, so kept / len are the march's
-//     bit for bit), then -- if any of the 64 columns is a kept, occupied sample -- the network on
-//     the 64 columns and the compositing sums inside each 8-lane group.  Column c belongs to ray
-//     c >> 3 for the whole life of the wave: SH16(dir) and the embedding row of the 8 rays sit in a
-//     small LDS block per wave, written once per ray group.  b1 + W1[:, 16:32] . SH is RECOMPUTED per
-//     stride (4 more matrix instructions per 16 x 16 block, in the one-ray form's order: the same
-//     bits per column): held per column it would be 64 registers and cost the register class.
-//     A ray that ends inside the head gets its outputs here; one that is still alive at
-//     k0 == n_head leaves its state (below) and a pending flag.
+//     loop with the march's chain logit (density_chain) and the f16 tile (column = lane), the
+//     march's keep decision (keep_step, sampler.hiph: the 64-lane scan's additions, so kept / len
+//     are the march's bit for bit), then -- if any of the 64 columns is a kept, occupied sample --
+//     the network on the 64 columns and the compositing sums inside each 8-lane group.  Column c
+//     belongs to ray c >> 3 for the whole life of the wave: SH16(dir) and the embedding row of the 8
+//     rays sit in a small LDS block per wave, written once per ray group.  b1 + W1[:, 16:32] . SH is
+//     RECOMPUTED per stride (4 more matrix instructions per 16 x 16 block, in the one-ray form's
+//     order: the same bits per column): held per column it would be 64 registers and cost the
+//     register class.  A ray that ends inside the head gets its outputs here; one that is still
+//     alive at k0 == n_head leaves its state (below) and a pending flag.
 //   f2n_render_rays_tail  render_one_ray (render_rays.hiph), resumed from that state at k0 = n_head
 //     for the pending rays; the others are skipped on a scalar flag load.
 //
@@ -71,7 +71,7 @@ __device__ __forceinline__ float group_incl_scan(float v, int m)
 
 __device__ __forceinline__ float group_sum(float v, int m, int lane)
 {
-  return group_last(group_incl_scan(v, m), lane);
+  return RayLanes<8>::last(group_incl_scan(v, m), lane);
 }
 
 template <int C, int F, bool POW2>
@@ -81,6 +81,7 @@ __global__ __launch_bounds__(HShape<C>::kWaves * 64) void render_rays_head_kerne
   using H = HShape<C>;
   using R = RShape<C>;
   using FS = typename R::FS;
+  using RL = RayLanes<8>;
   constexpr int L = C / F, kS1 = FS::kS1, kPitch = R::kPitch;
   __shared__ __attribute__((aligned(16))) float lds_all[H::kLdsFloats];
   float * lds_w = lds_all;
@@ -130,82 +131,39 @@ __global__ __launch_bounds__(HShape<C>::kWaves * 64) void render_rays_head_kerne
     }
     wave_lds_sync();
 
-    HalfScan ns = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, ds = ns;
-    float lx = 0.f, ly = 0.f, lz = 0.f;  // last sample point of the previous stride
+    StrideState<8> carry = {};
+    DepthState<8> ds = {};
     float comp_carry = 0.f;              // the compositing optical depth (head logit), per ray
     float cr = 0.f, cg = 0.f, cb = 0.f, cd = 0.f;
     int n_kept = 0, n_len = 0;
     bool done = !has_ray;
     for (int k0 = 0; k0 < k_end; k0 += 8) {
-      // ---- 1. sample and test: density_march8_kernel's stride
-      const int j = (k0 >> 4) & 3, h = (k0 >> 3) & 1;
-      const int k = k0 + m;
-      const bool valid = k < S;
-      float cum, dummy;
-      if (nrow) {
-        const float nz = valid ? nrow[k] : 0.f;
-        cum = half_scan_step(nz, j, h, m, lane, ns, dummy);
-        if (j == 3 && h == 1) ns.carry = ns.carry + group_last(dummy, lane);  // (T3 + T2) + (T1 + T0)
-      } else {
-        cum = (float)(min(k, S - 1) + 1);
-      }
-      const float t = cum * step;
-      const float mx = rf.dx * t, my = rf.dy * t, mz = rf.dz * t;
-      const float px = rf.ox + mx, py = rf.oy + my, pz = rf.oz + mz;
-      const float sx = dpp_get<0x111, 0xf, 0xf>(px, 0.f), sy = dpp_get<0x111, 0xf, 0xf>(py, 0.f),
-                  sz = dpp_get<0x111, 0xf, 0xf>(pz, 0.f);  // (moved by all lanes, then selected)
-      const float qx = m >= 1 ? sx : lx, qy = m >= 1 ? sy : ly, qz = m >= 1 ? sz : lz;
-      const float ex = px - qx, ey = py - qy, ez = pz - qz;
-      const float dt = (k == 0) ? 0.f : sqrtf(fmaf(ez, ez, fmaf(ey, ey, ex * ex)));
-      lx = group_last(px, lane);
-      ly = group_last(py, lane);
-      lz = group_last(pz, lane);
-      float x = px, y = py, z = pz;
+      // ---- 1. sample and test
+      const StrideSample sm = make_stride(rf, nrow, k0, S, step, carry, lane);
+      float x = sm.px, y = sm.py, z = sm.pz;
       contract_point(x, y, z);
       // finished, absent and unoccupied samples do not gather
-      const bool occ = valid && !done && (!has_grid || occ_test_contracted(x, y, z, bits, G));
+      const bool occ = sm.valid && !done && (!has_grid || occ_test_contracted(x, y, z, bits, G));
       const unsigned long long om = __ballot(occ);
       // ---- 2. encode: the march's chain, and the values parked for the network
       float sec = 0.f;
       if (om != 0ull) {  // (wave-uniform)
         if (occ) {       // (no cross-lane move inside)
-          float logit = bias0;
-#pragma unroll 1
-          for (int l = 0; l < L; l++) {
-            const LevelParams lp = load_level(primes, bias, mul, l);
-            uint32_t row[8];
-            float w[8], acc[F];
-            corner_rows_and_weights<POW2>(x, y, z, lp, T, row, w);
-            gather_blend<F>(table + level_stride * l, row, w, acc);
-#pragma unroll
-            for (int kk = 0; kk < F; kk++) {
-              __half hv;
-              logit = fmaf(round_f16_keep(acc[kk], hv), p_w_h[l * F + kk], logit);
-              tile[(l * F + kk) * kPitch + lane] = hv;
-            }
-          }
+          const float logit = density_chain<F, POW2>(
+            x, y, z, table, primes, bias, mul, p_w_h, bias0, L, T, level_stride,
+            [&](int c, __half hv) { tile[c * kPitch + lane] = hv; });
           const float sigma = expf(logit - density_shift);
-          sec = sigma * dt;
+          sec = sigma * sm.dt;
         }
       }
-      // ---- 3. the keep decision, exactly the march's (unoccupied lanes feed 0.f, outside any branch)
-      float incl;
-      half_scan_step(sec, j, h, m, lane, ds, incl);
-      const float before = (j == 0 && h == 0) ? 0.f : ds.last;
-      const float shifted = dpp_get<0x111, 0xf, 0xf>(incl, 0.f);
-      const float prev = m >= 1 ? shifted : before;
-      const float depth = ds.carry + prev;
-      ds.last = group_last(incl, lane);
-      if (j == 3 && h == 1) ds.carry = ds.carry + ds.last;
-      const float trans_c = expf(-depth);
-      const bool keep = valid && !done && (trans_c > t_thresh);
-      const unsigned long long km = __ballot(keep);
-      const bool use = keep && occ;  // this lane's sample is one of its ray's list
+      // ---- 3. the keep decision, the march's (unoccupied lanes feed 0.f, outside any branch)
+      const KeepStep ks = keep_step(sec, sm.valid && !done, k0, S, t_thresh, ds, lane);
+      const unsigned long long km = ks.mask;
+      const bool use = ks.keep && occ;  // this lane's sample is one of its ray's list
       if (!done) {
-        const int cnt = __popc((uint32_t)(km >> (8 * g)) & 0xffu);
-        n_len += cnt;
-        n_kept += __popc((uint32_t)((km & om) >> (8 * g)) & 0xffu);
-        if (cnt < min(8, S - k0)) done = true;  // the mask is a prefix: nothing later survives
+        n_len += ks.n;
+        n_kept += RL::count(km & om, lane);
+        done = ks.ends;  // nothing later survives
       }
 
       if ((km & om) != 0ull) {  // (wave-uniform)
@@ -278,19 +236,18 @@ __global__ __launch_bounds__(HShape<C>::kWaves * 64) void render_rays_head_kerne
         const float o0 = OUT[64 + lane], o1 = OUT[128 + lane], o2 = OUT[192 + lane];
         wave_lds_sync();  // (the next stride's tile and OUT writes stay behind these reads)
         float sec2 = 0.f;
-        if (use) sec2 = expf(hl - density_shift) * dt;
+        if (use) sec2 = expf(hl - density_shift) * sm.dt;
         const float incl2 = group_incl_scan(sec2, m);
-        const float sh2 = dpp_get<0x111, 0xf, 0xf>(incl2, 0.f);
-        const float trans = expf(-(comp_carry + (m >= 1 ? sh2 : 0.f)));
+        const float trans = expf(-(comp_carry + RL::prev(incl2, 0.f, lane)));
         if (use) {
           const float alpha = 1.f - expf(-sec2);
           const float w = trans * alpha;
           cr = fmaf(w, (1.f + 2.f * kEps) / (1.f + expf(-o0)) - kEps, cr);
           cg = fmaf(w, (1.f + 2.f * kEps) / (1.f + expf(-o1)) - kEps, cg);
           cb = fmaf(w, (1.f + 2.f * kEps) / (1.f + expf(-o2)) - kEps, cb);
-          cd = fmaf(w, t + t_shift, cd);
+          cd = fmaf(w, sm.t + t_shift, cd);
         }
-        comp_carry += group_last(incl2, lane);
+        comp_carry += RL::last(incl2, lane);
       }
       if (__ballot(!done) == 0ull) break;
     }
@@ -313,8 +270,8 @@ __global__ __launch_bounds__(HShape<C>::kWaves * 64) void render_rays_head_kerne
         if (hand_over) state[(int64_t)r * kStateWords] = __int_as_float(0);
       } else {
         f32x4 * st = reinterpret_cast<f32x4 *>(state + (int64_t)r * kStateWords);
-        const f32x4 s0 = {__int_as_float(1), ns.carry, lx, ly};
-        const f32x4 s1 = {lz, ds.carry, comp_carry, cr};
+        const f32x4 s0 = {__int_as_float(1), carry.noise, carry.lx, carry.ly};
+        const f32x4 s1 = {carry.lz, ds.carry, comp_carry, cr};
         const f32x4 s2 = {cg, cb, cd, __int_as_float(n_kept)};
         const f32x4 s3 = {__int_as_float(n_len), 0.f, 0.f, 0.f};
         st[0] = s0;

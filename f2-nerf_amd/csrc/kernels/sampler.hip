@@ -22,6 +22,21 @@ __device__ __forceinline__ int ray_of_wave()
   return (int)blockIdx.x * F2N_WAVES_PER_BLOCK + (int)(threadIdx.x >> 6);
 }
 
+// sample i of the output arrays: what f2n_sample_rays and f2n_sample_compact[_occ] write per sample
+__device__ __forceinline__ void store_sample(
+  float * __restrict__ pts, float * __restrict__ dirs, float * __restrict__ dt,
+  float * __restrict__ t, int64_t i, const RayFrame & rf, const StrideSample & sm)
+{
+  pts[3 * i] = sm.px;
+  pts[3 * i + 1] = sm.py;
+  pts[3 * i + 2] = sm.pz;
+  dirs[3 * i] = rf.dx;
+  dirs[3 * i + 1] = rf.dy;
+  dirs[3 * i + 2] = rf.dz;
+  dt[i] = sm.dt;
+  t[i] = sm.t;
+}
+
 // ---- f2n_sample_rays ----------------------------------------------------------------------------
 
 __global__ __launch_bounds__(F2N_BLOCK) void sample_rays_kernel(
@@ -39,17 +54,7 @@ __global__ __launch_bounds__(F2N_BLOCK) void sample_rays_kernel(
   const int64_t base = (int64_t)r * S;
   for (int k0 = 0; k0 < S; k0 += F2N_WAVE) {
     const StrideSample sm = make_stride(rf, nrow, k0, S, step, carry, lane);
-    if (sm.valid) {
-      const int64_t i = base + k0 + lane;
-      pts[3 * i] = sm.px;
-      pts[3 * i + 1] = sm.py;
-      pts[3 * i + 2] = sm.pz;
-      dirs[3 * i] = rf.dx;
-      dirs[3 * i + 1] = rf.dy;
-      dirs[3 * i + 2] = rf.dz;
-      dt[i] = sm.dt;
-      t[i] = sm.t;
-    }
+    if (sm.valid) store_sample(pts, dirs, dt, t, base + k0 + lane, rf, sm);
   }
   if (lane == 0) {
     bounds[2 * r] = (int32_t)base;
@@ -106,45 +111,13 @@ __global__ __launch_bounds__(F2N_BLOCK) void sample_dense_kernel(
   }
 }
 
-// ---- f2n_sample_compact -------------------------------------------------------------------------
-
-__global__ __launch_bounds__(F2N_BLOCK) void sample_compact_kernel(
-  const float * __restrict__ rays_o, const float * __restrict__ rays_d,
-  const float * __restrict__ noise, const int32_t * __restrict__ bounds, float * __restrict__ pts,
-  float * __restrict__ dirs, float * __restrict__ dt, float * __restrict__ t, int n_rays, int S,
-  float step)
-{
-  const int r = ray_of_wave();
-  if (r >= n_rays) return;
-  const int lane = lane_id();
-  const int start = bounds[2 * r];
-  const int cnt = bounds[2 * r + 1] - start;
-  if (cnt <= 0) return;
-  const RayFrame rf = load_ray(rays_o, rays_d, r);
-  const float * nrow = noise ? noise + (int64_t)r * S : nullptr;
-  StrideCarry carry = {0.f, 0.f, 0.f, 0.f};
-  for (int k0 = 0; k0 < cnt; k0 += F2N_WAVE) {
-    const StrideSample sm = make_stride(rf, nrow, k0, S, step, carry, lane);
-    if (k0 + lane < cnt) {
-      const int64_t i = (int64_t)start + k0 + lane;
-      pts[3 * i] = sm.px;
-      pts[3 * i + 1] = sm.py;
-      pts[3 * i + 2] = sm.pz;
-      dirs[3 * i] = rf.dx;
-      dirs[3 * i + 1] = rf.dy;
-      dirs[3 * i + 2] = rf.dz;
-      dt[i] = sm.dt;
-      t[i] = sm.t;
-    }
-  }
-}
-
-// ---- f2n_sample_compact_occ ---------------------------------------------------------------------
-// f2n_sample_compact for a ray list thinned by the occupancy bitfield: the ray's samples are
-// {k < len_r : occupied(p_k)} in order of k.  Walks the same strides as the march, tests the same bit
-// on the same point, and writes sample k at start + rank (rank = occupied samples before it).
-
-__global__ __launch_bounds__(F2N_BLOCK) void sample_compact_occ_kernel(
+// ---- f2n_sample_compact, f2n_sample_compact_occ -------------------------------------------------
+// The kept samples of every ray, re-created where the compacted list wants them.  OCC: the ray list
+// was thinned by the occupancy bitfield, the ray's samples are {k < len_r : occupied(p_k)} in order of
+// k.  Walks the same strides as the march, tests the same bit on the same point, and writes sample k
+// at start + rank (rank = occupied samples before it).  Without a grid the rank is k itself.
+template <bool OCC>
+__device__ __forceinline__ void sample_compact_rays(
   const float * __restrict__ rays_o, const float * __restrict__ rays_d,
   const float * __restrict__ noise, const int32_t * __restrict__ bounds,
   const int32_t * __restrict__ len, const uint32_t * __restrict__ bits, int G,
@@ -156,91 +129,68 @@ __global__ __launch_bounds__(F2N_BLOCK) void sample_compact_occ_kernel(
   const int lane = lane_id();
   const int start = bounds[2 * r];
   const int cnt = bounds[2 * r + 1] - start;
-  const int n_len = min(len[r], S);
+  const int n_len = OCC ? min(len[r], S) : cnt;
   if (cnt <= 0 || n_len <= 0) return;
   const RayFrame rf = load_ray(rays_o, rays_d, r);
   const float * nrow = noise ? noise + (int64_t)r * S : nullptr;
   StrideCarry carry = {0.f, 0.f, 0.f, 0.f};
-  int base = 0;  // occupied samples of the earlier strides
+  int base = 0;  // samples written by the earlier strides
   for (int k0 = 0; k0 < n_len && base < cnt; k0 += F2N_WAVE) {
     const StrideSample sm = make_stride(rf, nrow, k0, S, step, carry, lane);
-    const bool occ = (k0 + lane < n_len) && occ_test_point(sm.px, sm.py, sm.pz, bits, G);
-    const unsigned long long m = __ballot(occ);
-    const int rank = base + __popcll(m & ((1ull << lane) - 1ull));
-    if (occ && rank < cnt) {  // (rank < cnt always when bounds and len come from the same grid)
-      const int64_t i = (int64_t)start + rank;
-      pts[3 * i] = sm.px;
-      pts[3 * i + 1] = sm.py;
-      pts[3 * i + 2] = sm.pz;
-      dirs[3 * i] = rf.dx;
-      dirs[3 * i + 1] = rf.dy;
-      dirs[3 * i + 2] = rf.dz;
-      dt[i] = sm.dt;
-      t[i] = sm.t;
+    bool mine = k0 + lane < n_len;
+    int rank = k0 + lane;
+    if constexpr (OCC) {
+      mine = mine && occ_test_point(sm.px, sm.py, sm.pz, bits, G);
+      const unsigned long long m = __ballot(mine);
+      rank = base + __popcll(m & ((1ull << lane) - 1ull));
+      base += __popcll(m);
+    } else {
+      base += F2N_WAVE;
     }
-    base += __popcll(m);
+    // (rank < cnt always when bounds and len come from the same grid)
+    if (mine && rank < cnt) store_sample(pts, dirs, dt, t, (int64_t)start + rank, rf, sm);
   }
 }
 
-// ---- f2n_density_march --------------------------------------------------------------------------
-
-template <int F, bool POW2>
-__global__ __launch_bounds__(F2N_BLOCK) void density_march_kernel(
+__global__ __launch_bounds__(F2N_BLOCK) void sample_compact_kernel(
   const float * __restrict__ rays_o, const float * __restrict__ rays_d,
-  const float * __restrict__ noise, const uint16_t * __restrict__ table,
-  const int32_t * __restrict__ primes, const float * __restrict__ bias,
-  const float * __restrict__ mul, const float * __restrict__ w0, const float * __restrict__ b0,
-  int32_t * __restrict__ kept, int n_rays, int S, float step, int L, uint32_t T,
-  int64_t level_stride, float t_thresh, float density_shift)
+  const float * __restrict__ noise, const int32_t * __restrict__ bounds, float * __restrict__ pts,
+  float * __restrict__ dirs, float * __restrict__ dt, float * __restrict__ t, int n_rays, int S,
+  float step)
 {
-  const int r = ray_of_wave();
-  if (r >= n_rays) return;
-  const int lane = lane_id();
-  const RayFrame rf = load_ray(rays_o, rays_d, r);
-  const float * nrow = noise ? noise + (int64_t)r * S : nullptr;
-  const float bias0 = b0[0];
-  StrideCarry carry = {0.f, 0.f, 0.f, 0.f};
-  float depth_carry = 0.f;  // optical depth accumulated by earlier strides
-  int n_kept = 0;
-  for (int k0 = 0; k0 < S; k0 += F2N_WAVE) {
-    const StrideSample sm = make_stride(rf, nrow, k0, S, step, carry, lane);
-    float x = sm.px, y = sm.py, z = sm.pz;
-    contract_point(x, y, z);
-    // density logit = row 0 of Linear(L*F -> 16) applied to the f16-rounded encoding
-    float logit = bias0;
-    for (int l = 0; l < L; l++) {
-      const LevelParams lp = load_level(primes, bias, mul, l);
-      uint32_t row[8];
-      float w[8], acc[F];
-      corner_rows_and_weights<POW2>(x, y, z, lp, T, row, w);
-      gather_blend<F>(table + level_stride * l, row, w, acc);
-#pragma unroll
-      for (int k = 0; k < F; k++) logit = fmaf(round_f16(acc[k]), w0[l * F + k], logit);
-    }
-    const float sigma = expf(logit - density_shift);   // TruncExp forward
-    const float sec = sm.valid ? sigma * sm.dt : 0.f;  // sigma * dt
-    const float incl = wave_incl_scan(sec);
-    const float depth = depth_carry + wave_shift_up1(incl, 0.f);  // exclusive scan
-    const float trans = expf(-depth);
-    const bool keep = sm.valid && (trans > t_thresh);
-    const unsigned long long m = __ballot(keep);
-    n_kept += __popcll(m);
-    const int n_valid = min(F2N_WAVE, S - k0);
-    if (__popcll(m) < n_valid) break;  // the mask is a prefix: nothing later survives
-    depth_carry += wave_bcast_last(incl);
-  }
-  if (lane == 0) kept[r] = n_kept;
+  sample_compact_rays<false>(
+    rays_o, rays_d, noise, bounds, nullptr, nullptr, 0, pts, dirs, dt, t, n_rays, S, step);
 }
 
-// ---- f2n_density_march_occ ----------------------------------------------------------------------
-// density_march_kernel with the density of every sample in an unoccupied cell set to exactly zero:
-// the lane tests its bit before the level loop, a stride without an occupied sample skips the level
-// loop as a whole (wave-uniform) and only advances make_stride's carries, and unoccupied lanes feed
-// 0.f into the same wave scan -- the scan's additions stay those of density_march_kernel, so an
-// all-ones grid gives its counts bit for bit.  len[r] = leading samples with T > t_thresh (still a
-// prefix), kept[r] = the occupied ones among them.
-template <int F, bool POW2>
-__global__ __launch_bounds__(F2N_BLOCK) void density_march_occ_kernel(
+__global__ __launch_bounds__(F2N_BLOCK) void sample_compact_occ_kernel(
+  const float * __restrict__ rays_o, const float * __restrict__ rays_d,
+  const float * __restrict__ noise, const int32_t * __restrict__ bounds,
+  const int32_t * __restrict__ len, const uint32_t * __restrict__ bits, int G,
+  float * __restrict__ pts, float * __restrict__ dirs, float * __restrict__ dt,
+  float * __restrict__ t, int n_rays, int S, float step)
+{
+  sample_compact_rays<true>(
+    rays_o, rays_d, noise, bounds, len, bits, G, pts, dirs, dt, t, n_rays, S, step);
+}
+
+// ---- f2n_density_march, f2n_density_march_occ ---------------------------------------------------
+// One body for every lane mapping (RayLanes<W>, sampler.hiph: W = 64, 16 or 8 lanes to a ray) and for
+// the march with and without the occupancy grid.  Per stride: make_stride, contract_point, the density
+// chain, keep_step.
+//
+// OCC: the density of every sample in an unoccupied cell is exactly zero.  The lane tests its bit
+// before the level loop, a stride without an occupied sample skips the level loop as a whole
+// (wave-uniform) and only advances make_stride's carries, and unoccupied lanes feed 0.f into the same
+// scan -- the scan's additions stay those of the plain march, so an all-ones grid gives its counts
+// bit for bit.  len[r] = leading samples with T above t_thresh (still a prefix), kept[r] = the occupied
+// ones among them.  Without OCC the grid test compiles away and kept[r] = that prefix.
+//
+// W < 64: a ray that stops after a handful of samples (a trained scene seen from close by; the
+// bench's terminating regime keeps 3.5 samples per ray) costs a 16- or 8-sample stride instead of a
+// 64-sample one -- the wave scans are row scans anyway, and the gathers of a stride touch as many
+// lines either way.  Same counts whatever W, bit for bit (tests/test_gpu_fused.py).
+template <int F, bool POW2, int W, bool OCC>
+__device__ __forceinline__ void march_rays(
   const float * __restrict__ rays_o, const float * __restrict__ rays_d,
   const float * __restrict__ noise, const uint16_t * __restrict__ table,
   const int32_t * __restrict__ primes, const float * __restrict__ bias,
@@ -249,278 +199,103 @@ __global__ __launch_bounds__(F2N_BLOCK) void density_march_occ_kernel(
   int32_t * __restrict__ len, int n_rays, int S, float step, int L, uint32_t T,
   int64_t level_stride, float t_thresh, float density_shift)
 {
-  const int r = ray_of_wave();
-  if (r >= n_rays) return;
+  using RL = RayLanes<W>;
+  const int r0 = ray_of_wave() * RL::kRays;
+  if (r0 >= n_rays) return;
   const int lane = lane_id();
-  const RayFrame rf = load_ray(rays_o, rays_d, r);
-  const float * nrow = noise ? noise + (int64_t)r * S : nullptr;
-  const float bias0 = b0[0];
-  StrideCarry carry = {0.f, 0.f, 0.f, 0.f};
-  float depth_carry = 0.f;
-  int n_kept = 0, n_len = 0;
-  for (int k0 = 0; k0 < S; k0 += F2N_WAVE) {
-    const StrideSample sm = make_stride(rf, nrow, k0, S, step, carry, lane);
-    float x = sm.px, y = sm.py, z = sm.pz;
-    contract_point(x, y, z);
-    const bool occ = sm.valid && occ_test_contracted(x, y, z, bits, G);
-    const unsigned long long om = __ballot(occ);
-    float sec = 0.f;
-    if (om != 0ull) {  // (wave-uniform: an empty stride costs no gathers at all)
-      if (occ) {       // (no cross-lane move inside: the scan below runs with every lane on)
-        float logit = bias0;
-        for (int l = 0; l < L; l++) {
-          const LevelParams lp = load_level(primes, bias, mul, l);
-          uint32_t row[8];
-          float w[8], acc[F];
-          corner_rows_and_weights<POW2>(x, y, z, lp, T, row, w);
-          gather_blend<F>(table + level_stride * l, row, w, acc);
-#pragma unroll
-          for (int k = 0; k < F; k++) logit = fmaf(round_f16(acc[k]), w0[l * F + k], logit);
-        }
-        const float sigma = expf(logit - density_shift);
-        sec = sigma * sm.dt;
-      }
-    }
-    const float incl = wave_incl_scan(sec);
-    const float depth = depth_carry + wave_shift_up1(incl, 0.f);
-    const float trans = expf(-depth);
-    const bool keep = sm.valid && (trans > t_thresh);
-    const unsigned long long m = __ballot(keep);
-    n_len += __popcll(m);
-    n_kept += __popcll(m & om);
-    const int n_valid = min(F2N_WAVE, S - k0);
-    if (__popcll(m) < n_valid) break;  // the mask is a prefix: nothing later survives
-    depth_carry += wave_bcast_last(incl);
-  }
-  if (lane == 0) {
-    kept[r] = n_kept;
-    len[r] = n_len;
-  }
-}
-
-// Four rays per wavefront, one per 16-lane DPP row, strides of 16 samples: a ray that stops after a
-// handful of samples (a trained scene seen from close by; the bench's terminating regime keeps 3.5
-// samples per ray) costs a 16-sample stride instead of a 64-sample one -- the wave scans are row
-// scans anyway, and the gathers of a stride touch as many lines either way.
-//
-// Bit-identical to density_march_kernel (and to make_stride, which f2n_sample_compact uses to
-// re-create the kept samples): the 64-lane Kogge-Stone scan adds, for the lanes of its row j,
-//   row 0: rs            row 1: rs + T0          row 2: rs + (T1 + T0)     row 3: (rs + T2) + (T1 + T0)
-// (rs = scan inside the row, Tj = total of row j) and carries carry + ((T3 + T2) + (T1 + T0)) to the
-// next 64 samples; stride j of a 64-sample block does exactly those additions here.
-struct RowScan
-{
-  float carry;    // inclusive total of the completed 64-sample blocks
-  float t0, t1p, t2;  // T0, T1 + T0, T2 of the current block
-  float last;     // inclusive value (within the block) of the previous stride's last lane
-};
-
-__device__ __forceinline__ float row_incl_scan(float v)
-{
-  v += dpp_get<0x111, 0xf, 0xf>(v, 0.f);
-  v += dpp_get<0x112, 0xf, 0xf>(v, 0.f);
-  v += dpp_get<0x114, 0xf, 0xf>(v, 0.f);
-  v += dpp_get<0x118, 0xf, 0xf>(v, 0.f);
-  return v;
-}
-// lane 15 of the own row in every lane of the row (row_newbcast:15)
-__device__ __forceinline__ float row_last(float v) { return dpp_get<0x15F, 0xf, 0xf>(v, 0.f); }
-// previous lane of the own row, `fill` in the row's first lane (row_shr:1)
-__device__ __forceinline__ float row_shift_up1(float v, float fill) { return dpp_get<0x111, 0xf, 0xf>(v, fill); }
-
-// inclusive value, within its 64-sample block, of this lane's element of stride j (0..3); updates st
-__device__ __forceinline__ float row_scan_step(float v, int j, RowScan & st, float & incl_in_block)
-{
-  const float rs = row_incl_scan(v);
-  const float tj = row_last(rs);
-  float inner;
-  if (j == 0) {
-    inner = rs;
-    st.t0 = tj;
-  } else if (j == 1) {
-    inner = rs + st.t0;
-    st.t1p = tj + st.t0;
-  } else if (j == 2) {
-    inner = rs + st.t1p;
-    st.t2 = tj;
-  } else {
-    inner = (rs + st.t2) + st.t1p;
-  }
-  incl_in_block = inner;
-  return st.carry + inner;
-}
-
-template <int F, bool POW2>
-__global__ __launch_bounds__(F2N_BLOCK) void density_march16_kernel(
-  const float * __restrict__ rays_o, const float * __restrict__ rays_d,
-  const float * __restrict__ noise, const uint16_t * __restrict__ table,
-  const int32_t * __restrict__ primes, const float * __restrict__ bias,
-  const float * __restrict__ mul, const float * __restrict__ w0, const float * __restrict__ b0,
-  int32_t * __restrict__ kept, int n_rays, int S, float step, int L, uint32_t T,
-  int64_t level_stride, float t_thresh, float density_shift)
-{
-  const int lane = lane_id(), q = lane >> 4, m = lane & 15;
-  const int r_raw = (ray_of_wave() << 2) + q;
-  const bool has_ray = r_raw < n_rays;
-  const int r = has_ray ? r_raw : n_rays - 1;  // (the spare rows of the last wave redo the last ray)
-  const RayFrame rf = load_ray(rays_o, rays_d, r);
-  const float * nrow = noise ? noise + (int64_t)r * S : nullptr;
-  const float bias0 = b0[0];
-  RowScan ns = {0.f, 0.f, 0.f, 0.f, 0.f}, ds = {0.f, 0.f, 0.f, 0.f, 0.f};
-  float lx = 0.f, ly = 0.f, lz = 0.f;  // last sample point of the previous stride
-  int n_kept = 0;
-  bool done = !has_ray;
-  for (int k0 = 0; k0 < S; k0 += 16) {
-    const int j = (k0 >> 4) & 3;
-    const int k = k0 + m;
-    const bool valid = k < S;
-    // ---- the samples of this stride: make_stride, row by row
-    float cum, dummy;
-    if (nrow) {
-      const float nz = valid ? nrow[k] : 0.f;
-      cum = row_scan_step(nz, j, ns, dummy);
-      const float block_last = row_last(dummy);  // (T3 + T2) + (T1 + T0) once j = 3
-      if (j == 3) ns.carry = ns.carry + block_last;
-    } else {
-      cum = (float)(min(k, S - 1) + 1);
-    }
-    const float t = cum * step;
-    const float mx = rf.dx * t, my = rf.dy * t, mz = rf.dz * t;
-    const float px = rf.ox + mx, py = rf.oy + my, pz = rf.oz + mz;
-    const float qx = row_shift_up1(px, lx), qy = row_shift_up1(py, ly), qz = row_shift_up1(pz, lz);
-    const float ex = px - qx, ey = py - qy, ez = pz - qz;
-    const float dt = (k == 0) ? 0.f : sqrtf(fmaf(ez, ez, fmaf(ey, ey, ex * ex)));
-    lx = row_last(px);
-    ly = row_last(py);
-    lz = row_last(pz);
-    // ---- density, as in density_march_kernel
-    float x = px, y = py, z = pz;
-    contract_point(x, y, z);
-    float logit = bias0;
-    for (int l = 0; l < L; l++) {
-      const LevelParams lp = load_level(primes, bias, mul, l);
-      uint32_t row[8];
-      float w[8], acc[F];
-      corner_rows_and_weights<POW2>(x, y, z, lp, T, row, w);
-      gather_blend<F>(table + level_stride * l, row, w, acc);
-#pragma unroll
-      for (int kk = 0; kk < F; kk++) logit = fmaf(round_f16(acc[kk]), w0[l * F + kk], logit);
-    }
-    const float sigma = expf(logit - density_shift);
-    const float sec = valid ? sigma * dt : 0.f;
-    // ---- exclusive optical depth: depth_carry + wave_shift_up1(incl, 0) of the 64-lane scan
-    float incl;
-    row_scan_step(sec, j, ds, incl);
-    const float prev = row_shift_up1(incl, (j == 0) ? 0.f : ds.last);
-    const float depth = ds.carry + prev;
-    ds.last = row_last(incl);
-    if (j == 3) ds.carry = ds.carry + ds.last;
-    const float trans = expf(-depth);
-    const bool keep = valid && !done && (trans > t_thresh);
-    const unsigned long long mk = __ballot(keep);
-    const int cnt = __popc((uint32_t)(mk >> (16 * q)) & 0xffffu);
-    if (!done) {
-      n_kept += cnt;
-      if (cnt < min(16, S - k0)) done = true;  // the mask is a prefix: nothing later survives
-    }
-    if (__ballot(!done) == 0ull) break;
-  }
-  if (has_ray && m == 0) kept[r_raw] = n_kept;
-}
-
-// ---- eight rays per wavefront --------------------------------------------------------------------
-// A ray that stops after three or four samples still pays for the 16 of its first stride above.
-// Here a ray owns HALF a DPP row (8 lanes) and strides are 8 samples: half the evaluations where
-// rays stop early.  The 64-lane scan's additions are reproduced as before, now half a row at a
-// time: the first half of a row is the row scan's steps 1, 2, 4 (step 8 adds nothing below lane 8);
-// the second half needs, for its first lanes, what the first half's lanes 7 / 6,7 / 4..7 held after
-// steps 0 / 1 / 2 (kept in registers, fetched with row_shl) and adds the first half's own result at
-// step 8.  Same counts, bit for bit (tests/test_gpu_fused.py).
-// (HalfScan, group_last, half_row_scan and half_scan_step live in sampler.hiph: render_rays_head.hip
-// walks its rays with the same helpers)
-
-template <int F, bool POW2>
-__global__ __launch_bounds__(F2N_BLOCK) void density_march8_kernel(
-  const float * __restrict__ rays_o, const float * __restrict__ rays_d,
-  const float * __restrict__ noise, const uint16_t * __restrict__ table,
-  const int32_t * __restrict__ primes, const float * __restrict__ bias,
-  const float * __restrict__ mul, const float * __restrict__ w0, const float * __restrict__ b0,
-  int32_t * __restrict__ kept, int n_rays, int S, float step, int L, uint32_t T,
-  int64_t level_stride, float t_thresh, float density_shift)
-{
-  const int lane = lane_id(), g = lane >> 3, m = lane & 7;
-  const int r_raw = (ray_of_wave() << 3) + g;
+  const int r_raw = r0 + RL::group(lane);
   const bool has_ray = r_raw < n_rays;
   const int r = has_ray ? r_raw : n_rays - 1;  // (the spare groups of the last wave redo the last ray)
   const RayFrame rf = load_ray(rays_o, rays_d, r);
   const float * nrow = noise ? noise + (int64_t)r * S : nullptr;
   const float bias0 = b0[0];
-  HalfScan ns = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, ds = ns;
-  float lx = 0.f, ly = 0.f, lz = 0.f;  // last sample point of the previous stride
-  int n_kept = 0;
+  StrideState<W> carry = {};
+  DepthState<W> ds = {};
+  int n_kept = 0, n_len = 0;
   bool done = !has_ray;
-  for (int k0 = 0; k0 < S; k0 += 8) {
-    const int j = (k0 >> 4) & 3, h = (k0 >> 3) & 1;
-    const int k = k0 + m;
-    const bool valid = k < S;
-    float cum, dummy;
-    if (nrow) {
-      const float nz = valid ? nrow[k] : 0.f;
-      cum = half_scan_step(nz, j, h, m, lane, ns, dummy);
-      if (j == 3 && h == 1) ns.carry = ns.carry + group_last(dummy, lane);  // (T3 + T2) + (T1 + T0)
-    } else {
-      cum = (float)(min(k, S - 1) + 1);
-    }
-    const float t = cum * step;
-    const float mx = rf.dx * t, my = rf.dy * t, mz = rf.dz * t;
-    const float px = rf.ox + mx, py = rf.oy + my, pz = rf.oz + mz;
-    const float sx = dpp_get<0x111, 0xf, 0xf>(px, 0.f), sy = dpp_get<0x111, 0xf, 0xf>(py, 0.f),
-                sz = dpp_get<0x111, 0xf, 0xf>(pz, 0.f);  // (moved by all lanes, then selected)
-    const float qx = m >= 1 ? sx : lx, qy = m >= 1 ? sy : ly, qz = m >= 1 ? sz : lz;
-    const float ex = px - qx, ey = py - qy, ez = pz - qz;
-    const float dt = (k == 0) ? 0.f : sqrtf(fmaf(ez, ez, fmaf(ey, ey, ex * ex)));
-    lx = group_last(px, lane);
-    ly = group_last(py, lane);
-    lz = group_last(pz, lane);
-    float x = px, y = py, z = pz;
+  for (int k0 = 0; k0 < S; k0 += W) {
+    const StrideSample sm = make_stride(rf, nrow, k0, S, step, carry, lane);
+    float x = sm.px, y = sm.py, z = sm.pz;
     contract_point(x, y, z);
-    float logit = bias0;
-    for (int l = 0; l < L; l++) {
-      const LevelParams lp = load_level(primes, bias, mul, l);
-      uint32_t row[8];
-      float w[8], acc[F];
-      corner_rows_and_weights<POW2>(x, y, z, lp, T, row, w);
-      gather_blend<F>(table + level_stride * l, row, w, acc);
-#pragma unroll
-      for (int kk = 0; kk < F; kk++) logit = fmaf(round_f16(acc[kk]), w0[l * F + kk], logit);
+    bool occ = true;
+    unsigned long long om = ~0ull;
+    if constexpr (OCC) {
+      occ = sm.valid && occ_test_contracted(x, y, z, bits, G);
+      om = __ballot(occ);
     }
-    const float sigma = expf(logit - density_shift);
-    const float sec = valid ? sigma * dt : 0.f;
-    float incl;
-    half_scan_step(sec, j, h, m, lane, ds, incl);
-    const float before = (j == 0 && h == 0) ? 0.f : ds.last;
-    const float shifted = dpp_get<0x111, 0xf, 0xf>(incl, 0.f);
-    const float prev = m >= 1 ? shifted : before;
-    const float depth = ds.carry + prev;
-    ds.last = group_last(incl, lane);
-    if (j == 3 && h == 1) ds.carry = ds.carry + ds.last;
-    const float trans = expf(-depth);
-    const bool keep = valid && !done && (trans > t_thresh);
-    const unsigned long long mk = __ballot(keep);
-    const int cnt = __popc((uint32_t)(mk >> (8 * g)) & 0xffu);
+    float sec = 0.f;
+    if (om != 0ull) {  // (wave-uniform: an empty stride costs no gathers at all)
+      if (occ) {       // (no cross-lane move inside: the scan below runs with every lane on)
+        const float logit = density_chain<F, POW2>(
+          x, y, z, table, primes, bias, mul, w0, bias0, L, T, level_stride, [](int, __half) {});
+        const float sigma = expf(logit - density_shift);   // TruncExp forward
+        sec = sm.valid ? sigma * sm.dt : 0.f;               // sigma * dt
+      }
+    }
+    const KeepStep ks = keep_step(sec, sm.valid && !done, k0, S, t_thresh, ds, lane);
     if (!done) {
-      n_kept += cnt;
-      if (cnt < min(8, S - k0)) done = true;  // the mask is a prefix: nothing later survives
+      n_len += ks.n;
+      n_kept += RL::count(ks.mask & om, lane);
+      done = ks.ends;  // nothing later survives
     }
     if (__ballot(!done) == 0ull) break;
   }
-  if (has_ray && m == 0) kept[r_raw] = n_kept;
+  if (has_ray && RL::sample(lane) == 0) {
+    kept[r_raw] = n_kept;
+    if constexpr (OCC) len[r_raw] = n_len;
+  }
+}
+
+#define F2N_MARCH_PARAMS                                                                           \
+  const float * __restrict__ rays_o, const float * __restrict__ rays_d,                            \
+    const float * __restrict__ noise, const uint16_t * __restrict__ table,                         \
+    const int32_t * __restrict__ primes, const float * __restrict__ bias,                          \
+    const float * __restrict__ mul, const float * __restrict__ w0, const float * __restrict__ b0
+#define F2N_MARCH_TAIL_PARAMS                                                                      \
+  int n_rays, int S, float step, int L, uint32_t T, int64_t level_stride, float t_thresh,          \
+    float density_shift
+#define F2N_MARCH_HEAD_ARGS rays_o, rays_d, noise, table, primes, bias, mul, w0, b0
+#define F2N_MARCH_TAIL_ARGS n_rays, S, step, L, T, level_stride, t_thresh, density_shift
+
+// one ray per wavefront (F2N_OPT_MARCH = 1)
+template <int F, bool POW2>
+__global__ __launch_bounds__(F2N_BLOCK) void density_march_kernel(
+  F2N_MARCH_PARAMS, int32_t * __restrict__ kept, F2N_MARCH_TAIL_PARAMS)
+{
+  march_rays<F, POW2, 64, false>(
+    F2N_MARCH_HEAD_ARGS, nullptr, 0, kept, nullptr, F2N_MARCH_TAIL_ARGS);
+}
+
+template <int F, bool POW2>
+__global__ __launch_bounds__(F2N_BLOCK) void density_march_occ_kernel(
+  F2N_MARCH_PARAMS, const uint32_t * __restrict__ bits, int G, int32_t * __restrict__ kept,
+  int32_t * __restrict__ len, F2N_MARCH_TAIL_PARAMS)
+{
+  march_rays<F, POW2, 64, true>(F2N_MARCH_HEAD_ARGS, bits, G, kept, len, F2N_MARCH_TAIL_ARGS);
+}
+
+// four rays per wavefront (F2N_OPT_MARCH = 2)
+template <int F, bool POW2>
+__global__ __launch_bounds__(F2N_BLOCK) void density_march16_kernel(
+  F2N_MARCH_PARAMS, int32_t * __restrict__ kept, F2N_MARCH_TAIL_PARAMS)
+{
+  march_rays<F, POW2, 16, false>(
+    F2N_MARCH_HEAD_ARGS, nullptr, 0, kept, nullptr, F2N_MARCH_TAIL_ARGS);
+}
+
+// eight rays per wavefront (the default)
+template <int F, bool POW2>
+__global__ __launch_bounds__(F2N_BLOCK) void density_march8_kernel(
+  F2N_MARCH_PARAMS, int32_t * __restrict__ kept, F2N_MARCH_TAIL_PARAMS)
+{
+  march_rays<F, POW2, 8, false>(
+    F2N_MARCH_HEAD_ARGS, nullptr, 0, kept, nullptr, F2N_MARCH_TAIL_ARGS);
 }
 
 // ---- f2n_density_scan ---------------------------------------------------------------------------
 // The keep-prefix of every ray from an ALREADY COMPUTED encoding of all its samples (channel-major
-// [C, n_all]): same logit FMA chain, same scan and same threshold test as density_march_kernel, so
-// both give identical counts.  Used when most samples survive anyway: the encoding is then computed
+// [C, n_all]): same logit FMA chain as density_chain and the march's own keep_step, so both give
+// identical counts.  Used when most samples survive anyway: the encoding is then computed
 // once by the level-major f2n_hash_fwd (L2-resident table levels) and reused by the shading pass,
 // instead of being evaluated by the march and again by the second pass.
 template <int C>
@@ -534,7 +309,7 @@ __global__ __launch_bounds__(F2N_BLOCK) void density_scan_kernel(
   const int lane = lane_id();
   const float bias0 = b0[0];
   const int64_t base = (int64_t)r * S;
-  float depth_carry = 0.f;
+  DepthState<64> ds = {};
   int n_kept = 0;
   for (int k0 = 0; k0 < S; k0 += F2N_WAVE) {
     const int k = k0 + lane;
@@ -545,15 +320,9 @@ __global__ __launch_bounds__(F2N_BLOCK) void density_scan_kernel(
     for (int c = 0; c < C; c++) logit = fmaf(enc[(int64_t)c * n_all + i], w0[c], logit);
     const float sigma = expf(logit - density_shift);
     const float sec = valid ? sigma * dt[i] : 0.f;
-    const float incl = wave_incl_scan(sec);
-    const float depth = depth_carry + wave_shift_up1(incl, 0.f);
-    const float trans = expf(-depth);
-    const bool keep = valid && (trans > t_thresh);
-    const unsigned long long m = __ballot(keep);
-    n_kept += __popcll(m);
-    const int n_valid = min(F2N_WAVE, S - k0);
-    if (__popcll(m) < n_valid) break;
-    depth_carry += wave_bcast_last(incl);
+    const KeepStep ks = keep_step(sec, valid, k0, S, t_thresh, ds, lane);
+    n_kept += ks.n;
+    if (ks.ends) break;
   }
   if (lane == 0) kept[r] = n_kept;
 }
@@ -791,21 +560,12 @@ extern "C" int f2n_density_march(
   f2n_dispatch_field(F, T, [&](auto ff, auto p2) {
     constexpr int FF = decltype(ff)::value;
     constexpr bool P2 = decltype(p2)::value;
-    if (route == 0)
-      hipLaunchKernelGGL(
-        (density_march8_kernel<FF, P2>), grid, block, 0, s, rays_o, rays_d, noise, table_f16,
-        primes, bias, mul, w0, b0, kept, n_rays, S, step, L, T, level_stride, t_thresh,
-        density_shift);
-    else if (rows)
-      hipLaunchKernelGGL(
-        (density_march16_kernel<FF, P2>), grid, block, 0, s, rays_o, rays_d, noise, table_f16,
-        primes, bias, mul, w0, b0, kept, n_rays, S, step, L, T, level_stride, t_thresh,
-        density_shift);
-    else
-      hipLaunchKernelGGL(
-        (density_march_kernel<FF, P2>), grid, block, 0, s, rays_o, rays_d, noise, table_f16,
-        primes, bias, mul, w0, b0, kept, n_rays, S, step, L, T, level_stride, t_thresh,
-        density_shift);
+    const auto kernel = route == 0 ? density_march8_kernel<FF, P2>
+                        : rows     ? density_march16_kernel<FF, P2>
+                                   : density_march_kernel<FF, P2>;
+    hipLaunchKernelGGL(
+      kernel, grid, block, 0, s, rays_o, rays_d, noise, table_f16, primes, bias, mul, w0, b0, kept,
+      n_rays, S, step, L, T, level_stride, t_thresh, density_shift);
   });
   return f2n_launch_status();
 }

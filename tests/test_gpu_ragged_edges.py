@@ -313,3 +313,33 @@ def test_compact_rows_cm(capi, dev, C):
     for r in range(R):
         want[:, start[r]:start[r] + counts[r]] = src.numpy()[:, r * S:r * S + counts[r]]
     assert _bits_equal(dst.cpu().numpy(), want)
+
+
+# ---- sample_compact ------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("with_noise", [True, False])
+@pytest.mark.parametrize("S", [100, 192])
+def test_sample_compact_rows_are_sample_rays_rows(capi, dev, S, with_noise):
+    """The first cnt_r rows f2n_sample_compact writes for ray r are f2n_sample_rays' rows
+    r S .. r S + cnt_r bit for bit, in pts, dirs, dt and t (the claim of include/f2nerf_hip.h), at the
+    counts where a stride walk goes wrong; behind the last ray the sentinel stays."""
+    counts = np.array([0, 1, 8, 63, 64, 65, 72, S - 1, S], dtype=np.int64)
+    R, step, pad = counts.shape[0], 4.0 / S, 70
+    g = torch.Generator().manual_seed(S)
+    o = (torch.randn(R, 3, generator=g) * 0.25).to(dev)
+    d = torch.randn(R, 3, generator=g).to(dev)
+    noise = (torch.rand(R, S, generator=g) + 0.5).to(dev) if with_noise else None
+    full = [_sent(dev, R * S, 3), _sent(dev, R * S, 3), _sent(dev, R * S), _sent(dev, R * S)]
+    capi.call("sample_rays", o, d, noise, *full, torch.zeros(R, 2, dtype=torch.int32, device=dev), R, S,
+              step)
+    start = np.cumsum(counts) - counts
+    n = int(counts.sum())
+    bounds = torch.from_numpy(np.stack([start, start + counts], 1).astype(np.int32)).to(dev)
+    got = [_sent(dev, n + pad, 3), _sent(dev, n + pad, 3), _sent(dev, n + pad), _sent(dev, n + pad)]
+    capi.call("sample_compact", o, d, noise, bounds, *got, R, S, step)
+    for what, a, b in zip(("pts", "dirs", "dt", "t"), got, full):
+        a, b = a.cpu().numpy(), b.cpu().numpy()
+        want = np.full_like(a, rc.SENTINEL)
+        for r in range(R):
+            want[start[r]:start[r] + counts[r]] = b[r * S:r * S + counts[r]]
+        assert _bits_equal(a, want), what
