@@ -9,6 +9,7 @@
 #include "localizer.hpp"
 #include "occupancy_grid.hpp"
 #include "points_sampler.hpp"
+#include "pose_refiner.hpp"
 #include "ragged_ops.hpp"
 #include "rays.hpp"
 #include "scene_files.hpp"
@@ -139,6 +140,29 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     },
     py::arg("poses"), py::arg("intrinsics"), py::arg("h"), py::arg("w"), py::arg("batch_size"),
     py::arg("images") = py::none(), py::arg("dist") = py::none());
+  m.def(
+    "get_rays_from_cameras",
+    [](const Tensor & poses, const Tensor & intr, const Tensor & cam_idx, const Tensor & ij,
+       const c10::optional<Tensor> & dist, bool sorted) {
+      Rays r = get_rays_from_cameras(poses, intr, cam_idx, ij, opt_tensor(dist), sorted);
+      return py::make_tuple(r.origins, r.dirs);
+    },
+    py::arg("poses"), py::arg("intrinsics"), py::arg("cam_idx"), py::arg("ij"),
+    py::arg("dist") = py::none(), py::arg("sorted") = false,
+    "rays of a batch with one camera per ray, differentiable in the poses (f2n_cam_pose_grad)");
+  m.def(
+    "pose_compose",
+    [](const Tensor & base, const Tensor & delta, const c10::optional<Tensor> & fixed) {
+      return pose_compose(base, delta, opt_tensor(fixed));
+    },
+    py::arg("base"), py::arg("delta"), py::arg("fixed") = py::none(),
+    "f2n_pose_compose: R' = Exp(omega) R, t' = t + tau -> [E,3,4], differentiable in delta");
+  m.def(
+    "pose_compose_bwd",
+    [](const Tensor & base, const Tensor & delta, const c10::optional<Tensor> & fixed,
+       const Tensor & d_out) { return pose_compose_bwd(base, delta, opt_tensor(fixed), d_out); },
+    py::arg("base"), py::arg("delta"), py::arg("fixed"), py::arg("d_out"),
+    "f2n_pose_compose_bwd: d_out [E,3,4] -> d_delta [E,6]");
   m.def(
     "project_points",
     [](const Tensor & points, const Tensor & pose, const Tensor & intr,
@@ -553,6 +577,45 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def("infer_width", &Localizer::infer_width)
     .def_property_readonly("renderer", &Localizer::renderer)
     .def_property_readonly("intrinsic", [](Localizer & l) { return l.intrinsic(); });
+
+  // ---- PoseRefiner -------------------------------------------------------------------------------
+  py::class_<PoseRefiner, std::shared_ptr<PoseRefiner>>(m, "PoseRefiner")
+    .def(py::init([](const Tensor & base) { return std::make_shared<PoseRefiner>(base); }),
+         py::arg("base_poses"), "per-image SE(3) corrections of base_poses [E,3|4,4]; see pose_refiner.hpp")
+    .def("poses", &PoseRefiner::poses, "the refined poses [E,3,4], differentiable in delta")
+    .def("set_fixed", &PoseRefiner::set_fixed, py::arg("mask"))
+    .def(
+      "sample_random_rays",
+      [](PoseRefiner & r, const Tensor & intr, int h, int w, int64_t n,
+         const c10::optional<Tensor> & images, const c10::optional<Tensor> & dist,
+         const c10::optional<Tensor> & cam_idx, const c10::optional<Tensor> & ij) {
+        auto [rays, gt, cam] = r.sample_random_rays(
+          intr, h, w, n, opt_tensor(images), opt_tensor(dist), opt_tensor(cam_idx), opt_tensor(ij));
+        return py::make_tuple(rays.origins, rays.dirs, gt, cam);
+      },
+      py::arg("intrinsics"), py::arg("h"), py::arg("w"), py::arg("batch_size"),
+      py::arg("images") = py::none(), py::arg("dist") = py::none(), py::arg("cam_idx") = py::none(),
+      py::arg("ij") = py::none())
+    .def(
+      "make_adam",
+      [](PoseRefiner & r, float lr) {
+        AdamHandle h;
+        h.opt = std::make_shared<torch::optim::Adam>(r.optim_param_groups(lr));
+        return h;
+      },
+      "torch::optim::Adam over optim_param_groups(lr)")
+    .def("correction_norms", &PoseRefiner::correction_norms, "[E,2]: |omega|, |tau|")
+    .def("zero_grad", [](PoseRefiner & r) { r.zero_grad(); })
+    .def_property_readonly("n_cameras", &PoseRefiner::n_cameras)
+    .def_property_readonly("delta", [](PoseRefiner & r) { return r.delta_; })
+    .def_property_readonly("base", [](PoseRefiner & r) { return r.base_; })
+    .def_property_readonly("fixed", [](PoseRefiner & r) { return r.fixed_; })
+    .def(
+      "save",
+      [](std::shared_ptr<PoseRefiner> r, const std::string & path) { torch::save(r, path); })
+    .def(
+      "load",
+      [](std::shared_ptr<PoseRefiner> r, const std::string & path) { torch::load(r, path); });
 
   py::class_<AdamHandle>(m, "Adam")
     .def("step", [](AdamHandle & h) { h.opt->step(); }, py::call_guard<py::gil_scoped_release>())

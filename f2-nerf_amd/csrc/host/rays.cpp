@@ -136,7 +136,82 @@ Rays gen_rays(
   return {out[0], out[1]};
 }
 
+// launch_gen_rays with a camera per ray and a backward to the poses: the per-camera sums of
+// f2n_cam_pose_grad.  cam_start (the E + 1 segment bounds of the camera-sorted rays) is made with ATen
+// ops on the device; `order` is empty when cam_idx is already sorted.
+class CamRaysFn : public torch::autograd::Function<CamRaysFn>
+{
+public:
+  static torch::autograd::variable_list forward(
+    torch::autograd::AutogradContext * ctx, Tensor poses, Tensor intrinsics, Tensor cam_idx,
+    Tensor ij, Tensor dist, bool sorted)
+  {
+    if (dist.numel() == 0) dist = Tensor();
+    dist = dist_rows(dist, poses.size(0), poses);
+    const int64_t n = cam_idx.size(0), E = poses.size(0);
+    Rays rays = launch_gen_rays(poses, intrinsics, cam_idx, ij, 0, 1, n, dist);
+    Tensor order = torch::empty({0}, cam_idx.options());
+    Tensor cam_sorted = cam_idx;
+    if (!sorted && n > 0) {
+      // stable: equal cameras keep the caller's order, so the sums' order is fixed by cam_idx alone
+      auto [vals, idx] = at::sort(cam_idx, /*stable=*/true, /*dim=*/0, /*descending=*/false);
+      cam_sorted = vals;
+      order = idx.to(torch::kInt32);
+    }
+    // cam_start[c] = number of rays whose camera is below c
+    Tensor cam_start = torch::searchsorted(
+      cam_sorted, torch::arange(E + 1, cam_idx.options()), /*out_int32=*/true, /*right=*/false);
+    ctx->save_for_backward({f2n::dev_f32(intrinsics, "intrinsics"), ij, dist, cam_start, order});
+    ctx->saved_data["pose_shape"] = poses.sizes().vec();
+    return {rays.origins, rays.dirs};
+  }
+
+  static torch::autograd::variable_list backward(
+    torch::autograd::AutogradContext * ctx, torch::autograd::variable_list grad)
+  {
+    auto saved = ctx->get_saved_variables();
+    const Tensor & K = saved[0];
+    const Tensor & ij = saved[1];
+    const Tensor & dist = saved[2];
+    const Tensor & cam_start = saved[3];
+    const Tensor & order = saved[4];
+    const auto shape = ctx->saved_data["pose_shape"].toIntVector();
+    const int64_t E = shape[0], n = ij.size(0);
+    const int pose_ld = (int)(shape[1] * 4);
+    const auto opt = K.options();
+    Tensor d_o = grad[0].defined() ? f2n::dev_f32(grad[0], "grad rays_o") : torch::zeros({n, 3}, opt);
+    Tensor d_d = grad[1].defined() ? f2n::dev_f32(grad[1], "grad rays_d") : torch::zeros({n, 3}, opt);
+    Tensor ws = torch::empty({f2n_cam_pose_grad_workspace_floats(n, E)}, opt);
+    Tensor d_poses = torch::empty(shape, opt);
+    f2n::check(
+      f2n_cam_pose_grad(
+        K.data_ptr<float>(), f2n::fptr(dist), ij.data_ptr<int32_t>(), d_o.data_ptr<float>(),
+        d_d.data_ptr<float>(), cam_start.data_ptr<int32_t>(),
+        order.numel() ? order.data_ptr<int32_t>() : nullptr, d_poses.data_ptr<float>(), pose_ld,
+        ws.data_ptr<float>(), n, E, f2n::current_stream(K)),
+      "f2n_cam_pose_grad");
+    return {d_poses, Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+  }
+};
+
 }  // namespace
+
+Rays get_rays_from_cameras(
+  const Tensor & poses, const Tensor & intrinsics, const Tensor & cam_idx, const Tensor & ij,
+  const Tensor & dist, bool sorted)
+{
+  TORCH_CHECK(ij.dim() == 2 && ij.size(1) == 2, "ij must be [n,2]");
+  TORCH_CHECK(cam_idx.dim() == 1 && cam_idx.size(0) == ij.size(0), "cam_idx must be [n]");
+  Tensor cam = f2n::dev_i32(cam_idx, "cam_idx");
+  Tensor ij32 = f2n::dev_i32(ij, "ij");
+  if (!(torch::GradMode::is_enabled() && poses.requires_grad()))
+    return launch_gen_rays(poses, intrinsics, cam, ij32, 0, 1, cam.size(0), dist);
+  TORCH_CHECK(poses.size(0) >= 1, "get_rays_from_cameras: no cameras");
+  const Tensor lens =
+    dist.defined() ? dist.detach() : torch::empty({0}, f2n::float_on(poses.device()));
+  auto out = CamRaysFn::apply(poses, intrinsics.detach(), cam, ij32, lens, sorted);
+  return {out[0], out[1]};
+}
 
 Rays get_rays_from_pose(
   const Tensor & pose, const Tensor & intrinsic, const Tensor & ij, const Tensor & dist)

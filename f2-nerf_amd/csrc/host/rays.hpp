@@ -59,6 +59,18 @@ std::tuple<Rays, torch::Tensor, torch::Tensor> sample_random_rays(
   const torch::Tensor & poses, const torch::Tensor & intrinsics, int h, int w, int64_t batch_size,
   const torch::Tensor & images = {}, const torch::Tensor & dist = {});
 
+// The rays of a batch in which ray r comes from camera cam_idx[r] and pixel ij[r]: the launch that
+// sample_random_rays makes (the same bits), and differentiable in the poses when grad mode is on and
+// poses.requires_grad().  poses [E,3,4] (or [E,4,4]), intrinsics [E,3,3], cam_idx [n] i32 in 0..E-1,
+// ij [n,2] i32, dist [E,4].  The backward is f2n_cam_pose_grad: d(poses) in the poses' shape, one sum
+// per camera in a fixed order, without float atomics and without a host read (a training step that
+// refines its poses stays capturable).  A cam_idx that is not known to be sorted gets its order from a
+// stable sort; pass sorted = true when it is non-decreasing, and no permutation is made at all.
+// Undefined gradients of the origins or the directions count as zeros.
+Rays get_rays_from_cameras(
+  const torch::Tensor & poses, const torch::Tensor & intrinsics, const torch::Tensor & cam_idx,
+  const torch::Tensor & ij, const torch::Tensor & dist = {}, bool sorted = false);
+
 // The forward model, world point -> pixel (f2n_project_points): points [N,3]; pose [B,3,4] (or
 // [B,4,4], or one [3,4] / [4,4]), intrinsic [B,3,3] (or [3,3]), dist [B,4] (or [4]; undefined =
 // pinhole); B == 1 or B == N.  Returns {pix [N,2] f32 continuous (row, col) with pixel (i, j) centred

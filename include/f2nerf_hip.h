@@ -330,6 +330,58 @@ int f2n_gen_rays_dist_bwd(
   int64_t first_pixel, int width, const float * d_rays_o, const float * d_rays_d, float * d_poses,
   int pose_ld, float * workspace, int64_t n, void * stream);
 
+/* The backward of f2n_gen_rays / f2n_gen_rays_dist for a batch in which every ray names its own
+ * camera: the random training batch of Dataset::sample_random_rays (src/dataset.cpp:150-171), whose
+ * rays src/rays.cpp:7-28 forms from index_select'ed poses.  It is what joint refinement of the
+ * training poses needs and what f2n_gen_rays_bwd (n_cams 1 or n) cannot give: one pose gradient per
+ * camera, summed over that camera's rays.
+ *   intrinsics [n_cams, 3, 3];  dist [n_cams, 4] or NULL (pinhole; a row of zeros gives its bits)
+ *   ij         [n, 2] i32 (row, col), required
+ *   d_rays_o, d_rays_d [n, 3]
+ *   cam_start  [n_cams + 1] i32, non-decreasing from 0 to n: camera c owns positions
+ *              cam_start[c] .. cam_start[c+1] of the camera-sorted ray list
+ *   order      [n] i32: position p of that list is caller ray order[p]; NULL: the identity (the
+ *              caller's rays are already sorted by camera)
+ *   d_poses    [n_cams] blocks of pose_ld floats (12 or 16), every element overwritten:
+ *                d_pose_c[i][3] = sum d_rays_o[r][i],  d_pose_c[i][j] = sum d_rays_d[r][i] * v_r[j]
+ *              over the rays of camera c, v_r as the forward forms it; a camera without rays gets
+ *              exact zeros; row 3 of a [4,4] block is zero.
+ *   workspace  f2n_cam_pose_grad_workspace_floats(n, n_cams) floats, contents undefined on entry.
+ * The list is cut into pieces of 1024 positions, one wavefront each; a camera inside one piece is
+ * finished there, one that spans pieces has its partials added in piece order by a second kernel.
+ * No float atomics, a partition and an order that depend on cam_start alone (the same bits on every
+ * run), no host read, two launches.  n == 0 returns F2N_OK and zero-fills d_poses.  Values of
+ * cam_start and order outside 0..n are clamped or skipped, never used as an address. */
+int64_t f2n_cam_pose_grad_workspace_floats(int64_t n, int64_t n_cams);
+int f2n_cam_pose_grad(
+  const float * intrinsics, const float * dist, const int32_t * ij, const float * d_rays_o,
+  const float * d_rays_d, const int32_t * cam_start, const int32_t * order, float * d_poses,
+  int pose_ld, float * workspace, int64_t n, int64_t n_cams, void * stream);
+
+/* A rigid correction of each camera pose by a 6-vector, the parameterisation of a camera optimiser.
+ * The reference's only pose optimisation runs Adam on the twelve raw entries of a [3,4] matrix
+ * (src/localizer.cpp:142-167), which leaves SO(3) after the first step; this stays on it.
+ *   base   [n_cams] blocks of pose_ld floats (12 or 16; rows 0..2 are [R | t])
+ *   delta  [n_cams, 6] = (omega_x, omega_y, omega_z, tau_x, tau_y, tau_z)
+ *   fixed  [n_cams] i32 or NULL: a camera with a non-zero entry is not corrected (the gauge)
+ *   out    [n_cams, 3, 4]:  R' = Exp(omega) R,  t' = t + tau -- left multiplication in the NeRF
+ *          frame, the frame f2n_perturb_poses perturbs in (src/localizer.cpp:88-118).
+ * Exp is Rodrigues' formula with its Taylor polynomial below |omega| = 1e-2, f64 inside, rounded once
+ * to f32.  A camera whose six numbers are all zero, and every fixed camera, gets its base rows bit
+ * for bit.  One thread per camera. */
+int f2n_pose_compose(
+  const float * base, int pose_ld, const float * delta, const int32_t * fixed, float * out,
+  int64_t n_cams, void * stream);
+
+/* Backward of f2n_pose_compose with respect to delta (what autograd would assemble from a Rodrigues
+ * chain of ATen ops under src/localizer.cpp:142-167's Adam loop): d_out [n_cams, 3, 4] ->
+ * d_delta [n_cams, 6], the analytic derivative of Exp at the given omega (not only at zero), f64
+ * inside.  d tau = d_out[:, :, 3].  A fixed camera gets exact zeros.  The base poses receive no
+ * gradient. */
+int f2n_pose_compose_bwd(
+  const float * base, int pose_ld, const float * delta, const int32_t * fixed, const float * d_out,
+  float * d_delta, int64_t n_cams, void * stream);
+
 /* The forward model of the same camera, the inverse of f2n_gen_rays_dist (the projection that
  * src/rays.cpp:7-28 inverts, with the coefficients of src/dataset.cpp:59-63): world point -> pixel.
  *   points  [n, 3]; poses, pose_ld, intrinsics, dist (NULL = pinhole), n_cams, cam_idx: addressed as
