@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from oracle import kernels as K
-from tests import util
+from tests import ray_grad_model, util
 
 pytestmark = pytest.mark.gpu
 
@@ -198,6 +198,13 @@ def test_hash_bwd_parity(capi, dev, L, F, log2_T, stride_mode, pts_grad):
     if pts_grad:
         s = ref_pg.abs().max().item()
         assert (pg.cpu() - ref_pg).abs().max().item() <= 1e-5 * s + 1e-12
+        # element by element against the float64 sum of the terms, at twice its rounding bound (the
+        # cells are the oracle's own float32 chain on these very points: nothing is ambiguous here)
+        G, _, E, lev = ray_grad_model.point_grad(fld, pts.numpy(), grad)
+        assert lev["finite"]
+        worst = float(ray_grad_model.ratio(pg, G, E).max())
+        print("\npts_grad: largest |err| / E %.3f" % worst)
+        assert worst <= ray_grad_model.BAR, worst
     # accumulate semantics: a second call doubles the table gradient
     capi.call("hash_bwd", *d, L * F, 1, tg, None, n, L, F, T, fld["stride"], 128.0)
     assert (tg.cpu() - 2 * ref_tg).abs().max().item() <= 2e-5 * scale

@@ -10,6 +10,7 @@ import torch
 
 from oracle import kernels as K
 from oracle import ref_render as R
+from tests import ray_grad_model as M
 from tests.test_gpu_render import _close, _setup
 
 pytestmark = pytest.mark.gpu
@@ -95,7 +96,10 @@ def _field(L, F, T, disjoint, seed):
                 bias=torch.rand(L, 3, generator=g) * 1000.0 + 100.0, mul=K.level_mul(L))
 
 
-def _rays_and_samples(n_rays, seed):
+def _rays_and_samples(n_rays, seed, fld=None):
+    """fld: samples whose cell a rounding of the contraction could decide (tests/ray_grad_model.py,
+    `ambiguous`) get a new t until none is left -- no seed gives 4000 samples without one (1-3 % of
+    them are), so the samples are redrawn and nothing is left out of a comparison."""
     g = torch.Generator().manual_seed(seed)
     o = torch.randn(n_rays, 3, generator=g) * 0.25
     d = torch.randn(n_rays, 3, generator=g) * 2.0
@@ -110,6 +114,14 @@ def _rays_and_samples(n_rays, seed):
     t = torch.rand(n, generator=g) * 3.0 + 0.01
     nhat = d / d.norm(dim=1, keepdim=True)
     pts = (o[ray] + nhat[ray] * t[:, None]).contiguous()
+    for _ in range(100 if fld is not None else 0):
+        amb = torch.from_numpy(M.ambiguous(fld, pts))
+        if not bool(amb.any()):
+            break
+        t[amb] = torch.rand(int(amb.sum()), generator=g) * 3.0 + 0.01
+        pts = (o[ray] + nhat[ray] * t[:, None]).contiguous()
+    else:
+        assert fld is None, "ambiguous samples left after 100 draws"
     return o, d, bounds, ray, t, pts
 
 
@@ -135,9 +147,12 @@ def _oracle_rays_grad(fld, L, F, T, o, d, ray, t, pts, x, g):
 @pytest.mark.parametrize("L,T,disjoint", [(16, 5000, False), (32, 5000, False), (16, 5000, True),
                                           (32, 1 << 12, True), (16, 1 << 12, False)])
 def test_hash_rays_grad_matches_oracle(capi, dev, F, L, T, disjoint):
-    fld = _field(L, F, T, disjoint, seed=F * 100 + L)
+    """Against the float32 oracle composition at 5 % + 0.2 % of the largest element, and element by
+    element against the float64 model of tests/ray_grad_model.py at twice its rounding bound (the
+    cases built to corner the kernel are tests/test_gpu_ray_grad_f64.py)."""
+    fld = dict(_field(L, F, T, disjoint, seed=F * 100 + L), L=L, F=F, T=T)
     n_rays = 40
-    o, d, bounds, ray, t, pts = _rays_and_samples(n_rays, seed=L + F)
+    o, d, bounds, ray, t, pts = _rays_and_samples(n_rays, seed=L + F, fld=fld)
     n = pts.shape[0]
     gen = torch.Generator().manual_seed(3)
     g = torch.randn(n, L * F, generator=gen) * 5e-3
@@ -166,6 +181,12 @@ def test_hash_rays_grad_matches_oracle(capi, dev, F, L, T, disjoint):
     _close(got_o, ref_o, 5e-2, 2e-3)
     _close(got_d, ref_d, 5e-2, 2e-3)
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+    m = M.model(M.Inputs(fld, pts, t, bounds, d, g))
+    assert m["finite"] and not M.ambiguous(fld, pts).any()
+    r_o = float(M.ratio(got_o, m["d_o"], m["E"]["d_o"]).max())
+    r_d = float(M.ratio(got_d, m["d_d"], m["E"]["d_d"]).max())
+    print("\nlargest |err| / E: d_o %.3f, d_d %.3f" % (r_o, r_d))
+    assert r_o <= M.BAR and r_d <= M.BAR, (r_o, r_d)
 
 
 # ---- Renderer::render with fused_ray_grad --------------------------------------------------------
@@ -187,7 +208,9 @@ def _loss(colors, depths):
 @pytest.mark.parametrize("dense", [0, 1])
 @pytest.mark.parametrize("mode", ["validate", "train"])
 def test_fused_ray_grad_matches_oracle(host, dev, dense, mode):
-    """The setup of test_gpu_render.test_pose_gradient_path, on the fused path."""
+    """The setup of test_gpu_render.test_pose_gradient_path, on the fused path.  Whole renders against
+    the oracle's own sampler roundings, hence the 5 % bar here and in the two tests below; the kernel
+    itself is held to float64 element by element in tests/test_gpu_ray_grad_f64.py."""
     oracle, hr, o, d, noise, bg, gt, emb = _setup(host, 8, 2, 14, 64, 4.0 / 64, 24, 3.0, 11)
     o_r, d_r = o.clone().requires_grad_(True), d.clone().requires_grad_(True)
     if mode == "train":
