@@ -86,10 +86,20 @@ def option_keys(path=HEADER):
     return keys
 
 
+def later_option_keys(path=HEADER):
+    """{'GATHER_PAIRED': 64, ...}: the options numbered from F2N_OPT2_FIRST, which the first table
+    (option_keys) does not hold."""
+    text = open(path).read()
+    first = int(re.search(r"#define\s+F2N_OPT2_FIRST\s+(\d+)", text).group(1))
+    return {m.group(1): first + int(m.group(2))
+            for m in re.finditer(r"#define\s+F2N_OPT_(\w+)\s+\(F2N_OPT2_FIRST \+ (\d+)\)", text)}
+
+
 def set_option(name, value):
     """f2n_set_option by name (e.g. set_option("SHADE_BWD", 1)); returns the previous value."""
     L = lib()
-    prev = L.cdll.f2n_set_option(option_keys()[name.upper()], int(value))
+    keys = {**option_keys(), **later_option_keys()}
+    prev = L.cdll.f2n_set_option(keys[name.upper()], int(value))
     if prev < 0:
         raise F2NError("f2n_set_option(%s, %r) rejected" % (name, value))
     return prev

@@ -93,7 +93,7 @@ __global__ __launch_bounds__(F2N_BLOCK) void hash_fwd_raytile_kernel(
   const float * __restrict__ pts, const uint16_t * __restrict__ table,
   const int32_t * __restrict__ primes, const float * __restrict__ bias,
   const float * __restrict__ mul, float * __restrict__ out, int n_rays, int S, uint32_t T,
-  int64_t level_stride, int walk)
+  int64_t level_stride, int walk, int corner_order)
 {
   static_assert(F2N_BLOCK == 256 && SAMPLES % 16 == 0, "4 waves, float4 runs");
   constexpr int RAYS = 64, kPitch = SAMPLES + 4, kPPitch = 3 * SAMPLES + 1;
@@ -183,24 +183,38 @@ __global__ __launch_bounds__(F2N_BLOCK) void hash_fwd_raytile_kernel(
     __syncthreads();
   }
   constexpr int kRaysPerIter = 64 / SAMPLES;  // along: rays one wave instruction covers
+  // The 8 corner loads of a sample, in vertex-parity order (corner_order 0: lanes in neighbouring
+  // cells ask for the vertices they share in the same load, see gather_blend_paired) or in corner
+  // order (1).  The same rows and the same sum either way; the whole walk is written once per order
+  // so that neither body carries the other's registers.
+  auto walk_tile = [&](auto paired) {
 #pragma unroll
-  for (int j = 0; j < SAMPLES / 4; j++) {
-    int ks = along ? (lane % SAMPLES) : (j * 4 + wave);
-    int ray = along ? ((j * 4 + wave) * kRaysPerIter + lane / SAMPLES) : lane;
-    if (sorted) {
-      const int pair = order[(j * 4 + wave) * 64 + lane];
-      ray = pair / SAMPLES;
-      ks = pair % SAMPLES;
+    for (int j = 0; j < SAMPLES / 4; j++) {
+      int ks = along ? (lane % SAMPLES) : (j * 4 + wave);
+      int ray = along ? ((j * 4 + wave) * kRaysPerIter + lane / SAMPLES) : lane;
+      if (sorted) {
+        const int pair = order[(j * 4 + wave) * 64 + lane];
+        ray = pair / SAMPLES;
+        ks = pair % SAMPLES;
+      }
+      const float x = ptile[ray][3 * ks], y = ptile[ray][3 * ks + 1], z = ptile[ray][3 * ks + 2];
+      uint32_t row[8];
+      float w[8], acc[F];
+      if constexpr (decltype(paired)::value) {
+        const uint32_t m = slot_rows_and_weights<POW2>(x, y, z, lp, T, row, w);
+        gather_blend_paired<F>(table + level_stride * l, row, m, w, acc);
+      } else {
+        corner_rows_and_weights<POW2>(x, y, z, lp, T, row, w);
+        gather_blend<F>(table + level_stride * l, row, w, acc);
+      }
+#pragma unroll
+      for (int k = 0; k < F; k++) tile[k][ray][ks] = round_f16(acc[k]);
     }
-    const float x = ptile[ray][3 * ks], y = ptile[ray][3 * ks + 1], z = ptile[ray][3 * ks + 2];
-    uint32_t row[8];
-    float w[8];
-    corner_rows_and_weights<POW2>(x, y, z, lp, T, row, w);
-    float acc[F];
-    gather_blend<F>(table + level_stride * l, row, w, acc);
-#pragma unroll
-    for (int k = 0; k < F; k++) tile[k][ray][ks] = round_f16(acc[k]);
-  }
+  };
+  if (corner_order == 0)
+    walk_tile(std::true_type{});
+  else
+    walk_tile(std::false_type{});
   __syncthreads();
   // RAYS x (SAMPLES / 4) float4 per channel, SAMPLES / 16 per thread
 #pragma unroll
@@ -481,6 +495,7 @@ extern "C" int f2n_hash_fwd_raytile(
   if (reinterpret_cast<uintptr_t>(out_cm) & 15u) return F2N_E_INVALID_ARG;
   if (n == 0) return F2N_OK;
   const int walk = f2n_get_option(F2N_OPT_RAYTILE_WALK);
+  const int corner_order = f2n_get_option(F2N_OPT_GATHER_PAIRED);
   const int want = f2n_get_option(F2N_OPT_RAYTILE);  // samples per tile: 16 | 32 (measurements)
   const int ts = (want == 16) ? 16 : (S % 32 == 0 ? 32 : 16);
   const int64_t tiles = (int64_t)f2n_div_up(n_rays, 64) * (S / ts);
@@ -493,11 +508,11 @@ extern "C" int f2n_hash_fwd_raytile(
     if (ts == 16)
       hipLaunchKernelGGL(
         (hash_fwd_raytile_kernel<FF, P2, 16>), grid, block, 0, s, pts, table_f16, primes, bias, mul,
-        out_cm, n_rays, S, T, level_stride, walk);
+        out_cm, n_rays, S, T, level_stride, walk, corner_order);
     else
       hipLaunchKernelGGL(
         (hash_fwd_raytile_kernel<FF, P2, 32>), grid, block, 0, s, pts, table_f16, primes, bias, mul,
-        out_cm, n_rays, S, T, level_stride, walk);
+        out_cm, n_rays, S, T, level_stride, walk, corner_order);
   });
   return f2n_launch_status();
 }

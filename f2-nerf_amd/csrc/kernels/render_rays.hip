@@ -35,7 +35,7 @@ namespace
 
 template <int C, int F, bool POW2>
 __global__ __launch_bounds__(RShape<C>::kWaves * 64) void render_rays_kernel(
-  F2N_RENDER_PARAMS)
+  F2N_RENDER_PARAMS, int corner_order)
 {
   using R = RShape<C>;
   using FS = typename R::FS;
@@ -53,7 +53,7 @@ __global__ __launch_bounds__(RShape<C>::kWaves * 64) void render_rays_kernel(
   const RenderArgs a = {rays_o, rays_d, noise,      table, primes,     bias,  mul, p_w_h,
                         p_emb,  ray_img, bits,      G,     bg,         colors, depths, last_trans,
                         kept,   len,     S,         step,  T,          level_stride, t_thresh,
-                        density_shift,   t_shift};
+                        density_shift,   t_shift, corner_order};
   const RayResume whole = {0, {0.f, 0.f, 0.f, 0.f}, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0, 0};
   __half * tile = reinterpret_cast<__half *>(lds_all + FS::kWFloats + wave * R::kWaveFloats);
   float * OUT = lds_all + FS::kWFloats + wave * R::kWaveFloats + R::kTileFloats;
@@ -83,7 +83,8 @@ extern "C" int f2n_render_rays(
     const unsigned grid = std::min<unsigned>(f2n_div_up(n_rays, R::kWaves), 512u);
     hipLaunchKernelGGL(
       (render_rays_kernel<decltype(cc)::value, decltype(ff)::value, decltype(p2)::value>),
-      dim3(grid), dim3(R::kWaves * 64), 0, s, F2N_RENDER_KARGS);
+      dim3(grid), dim3(R::kWaves * 64), 0, s, F2N_RENDER_KARGS,
+      f2n_get_option(F2N_OPT_GATHER_PAIRED));
   });
   return f2n_launch_status();
 }

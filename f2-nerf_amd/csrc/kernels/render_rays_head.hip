@@ -76,7 +76,7 @@ __device__ __forceinline__ float group_sum(float v, int m, int lane)
 
 template <int C, int F, bool POW2>
 __global__ __launch_bounds__(HShape<C>::kWaves * 64) void render_rays_head_kernel(
-  F2N_RENDER_PARAMS, float * __restrict__ state, int n_head)
+  F2N_RENDER_PARAMS, float * __restrict__ state, int n_head, int corner_order)
 {
   using H = HShape<C>;
   using R = RShape<C>;
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(HShape<C>::kWaves * 64) void render_rays_head_kerne
       if (om != 0ull) {  // (wave-uniform)
         if (occ) {       // (no cross-lane move inside)
           const float logit = density_chain<F, POW2>(
-            x, y, z, table, primes, bias, mul, p_w_h, bias0, L, T, level_stride,
+            x, y, z, table, primes, bias, mul, p_w_h, bias0, L, T, level_stride, corner_order,
             [&](int c, __half hv) { tile[c * kPitch + lane] = hv; });
           const float sigma = expf(logit - density_shift);
           sec = sigma * sm.dt;
@@ -285,7 +285,7 @@ __global__ __launch_bounds__(HShape<C>::kWaves * 64) void render_rays_head_kerne
 
 template <int C, int F, bool POW2>
 __global__ __launch_bounds__(RShape<C>::kWaves * 64) void render_rays_tail_kernel(
-  F2N_RENDER_PARAMS, const float * __restrict__ state, int n_head)
+  F2N_RENDER_PARAMS, const float * __restrict__ state, int n_head, int corner_order)
 {
   using R = RShape<C>;
   using FS = typename R::FS;
@@ -302,7 +302,7 @@ __global__ __launch_bounds__(RShape<C>::kWaves * 64) void render_rays_tail_kerne
   const RenderArgs a = {rays_o, rays_d, noise,      table, primes,     bias,  mul, p_w_h,
                         p_emb,  ray_img, bits,      G,     bg,         colors, depths, last_trans,
                         kept,   len,     S,         step,  T,          level_stride, t_thresh,
-                        density_shift,   t_shift};
+                        density_shift,   t_shift, corner_order};
   __half * tile = reinterpret_cast<__half *>(lds_all + FS::kWFloats + wave * R::kWaveFloats);
   float * OUT = lds_all + FS::kWFloats + wave * R::kWaveFloats + R::kTileFloats;
 
@@ -343,7 +343,7 @@ extern "C" int f2n_render_rays_head(
     hipLaunchKernelGGL(
       (render_rays_head_kernel<decltype(cc)::value, decltype(ff)::value, decltype(p2)::value>),
       dim3(grid), dim3(H::kWaves * 64), 0, s, F2N_RENDER_KARGS, static_cast<float *>(state),
-      n_head);
+      n_head, f2n_get_option(F2N_OPT_GATHER_PAIRED));
   });
   return f2n_launch_status();
 }
@@ -368,7 +368,7 @@ extern "C" int f2n_render_rays_tail(
     hipLaunchKernelGGL(
       (render_rays_tail_kernel<decltype(cc)::value, decltype(ff)::value, decltype(p2)::value>),
       dim3(grid), dim3(R::kWaves * 64), 0, s, F2N_RENDER_KARGS, static_cast<const float *>(state),
-      n_head);
+      n_head, f2n_get_option(F2N_OPT_GATHER_PAIRED));
   });
   return f2n_launch_status();
 }

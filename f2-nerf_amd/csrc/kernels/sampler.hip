@@ -197,7 +197,7 @@ __device__ __forceinline__ void march_rays(
   const float * __restrict__ mul, const float * __restrict__ w0, const float * __restrict__ b0,
   const uint32_t * __restrict__ bits, int G, int32_t * __restrict__ kept,
   int32_t * __restrict__ len, int n_rays, int S, float step, int L, uint32_t T,
-  int64_t level_stride, float t_thresh, float density_shift)
+  int64_t level_stride, float t_thresh, float density_shift, int corner_order)
 {
   using RL = RayLanes<W>;
   const int r0 = ray_of_wave() * RL::kRays;
@@ -227,7 +227,8 @@ __device__ __forceinline__ void march_rays(
     if (om != 0ull) {  // (wave-uniform: an empty stride costs no gathers at all)
       if (occ) {       // (no cross-lane move inside: the scan below runs with every lane on)
         const float logit = density_chain<F, POW2>(
-          x, y, z, table, primes, bias, mul, w0, bias0, L, T, level_stride, [](int, __half) {});
+          x, y, z, table, primes, bias, mul, w0, bias0, L, T, level_stride, corner_order,
+          [](int, __half) {});
         const float sigma = expf(logit - density_shift);   // TruncExp forward
         sec = sm.valid ? sigma * sm.dt : 0.f;               // sigma * dt
       }
@@ -253,9 +254,10 @@ __device__ __forceinline__ void march_rays(
     const float * __restrict__ mul, const float * __restrict__ w0, const float * __restrict__ b0
 #define F2N_MARCH_TAIL_PARAMS                                                                      \
   int n_rays, int S, float step, int L, uint32_t T, int64_t level_stride, float t_thresh,          \
-    float density_shift
+    float density_shift, int corner_order
 #define F2N_MARCH_HEAD_ARGS rays_o, rays_d, noise, table, primes, bias, mul, w0, b0
-#define F2N_MARCH_TAIL_ARGS n_rays, S, step, L, T, level_stride, t_thresh, density_shift
+#define F2N_MARCH_TAIL_ARGS                                                                        \
+  n_rays, S, step, L, T, level_stride, t_thresh, density_shift, corner_order
 
 // one ray per wavefront (F2N_OPT_MARCH = 1)
 template <int F, bool POW2>
@@ -553,6 +555,7 @@ extern "C" int f2n_density_march(
   // eight rays per wavefront (8-sample strides) unless F2N_OPT_MARCH asks for one (1: 64-sample
   // strides, round 2) or four (2: 16-sample strides)
   const int route = f2n_get_option(F2N_OPT_MARCH);
+  const int corner_order = f2n_get_option(F2N_OPT_GATHER_PAIRED);
   const bool rows = route == 2;
   const int rays_per_wave = route == 1 ? 1 : route == 2 ? 4 : 8;
   const dim3 grid(f2n_div_up(n_rays, F2N_WAVES_PER_BLOCK * rays_per_wave)), block(F2N_BLOCK);
@@ -565,7 +568,7 @@ extern "C" int f2n_density_march(
                                    : density_march_kernel<FF, P2>;
     hipLaunchKernelGGL(
       kernel, grid, block, 0, s, rays_o, rays_d, noise, table_f16, primes, bias, mul, w0, b0, kept,
-      n_rays, S, step, L, T, level_stride, t_thresh, density_shift);
+      n_rays, S, step, L, T, level_stride, t_thresh, density_shift, corner_order);
   });
   return f2n_launch_status();
 }
@@ -585,11 +588,12 @@ extern "C" int f2n_density_march_occ(
   if (reinterpret_cast<uintptr_t>(table_f16) % (2u * F)) return F2N_E_INVALID_ARG;
   const dim3 grid(f2n_div_up(n_rays, F2N_WAVES_PER_BLOCK)), block(F2N_BLOCK);
   hipStream_t s = (hipStream_t)stream;
+  const int corner_order = f2n_get_option(F2N_OPT_GATHER_PAIRED);
   f2n_dispatch_field(F, T, [&](auto ff, auto p2) {
     hipLaunchKernelGGL(
       (density_march_occ_kernel<decltype(ff)::value, decltype(p2)::value>), grid, block, 0, s,
       rays_o, rays_d, noise, table_f16, primes, bias, mul, w0, b0, bits, G, kept, len, n_rays, S,
-      step, L, T, level_stride, t_thresh, density_shift);
+      step, L, T, level_stride, t_thresh, density_shift, corner_order);
   });
   return f2n_launch_status();
 }

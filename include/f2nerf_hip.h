@@ -89,6 +89,18 @@ const char * f2n_status_string(int status);
                                   per-sample arrays; same results bit for bit (network parameter
                                   gradients: within the order of their float atomics)               */
 #define F2N_OPT_COUNT 13
+/* Keys 0 .. F2N_OPT_COUNT - 1 are the first table, closed with ABI 2: key 13 stays rejected.  Options
+ * added since are numbered from F2N_OPT2_FIRST, F2N_OPT2_COUNT of them; same calls, same rules. */
+#define F2N_OPT2_FIRST 64
+#define F2N_OPT_GATHER_PAIRED (F2N_OPT2_FIRST + 0)
+                                /* the order of a sample's 8 corner loads in f2n_hash_fwd_raytile and in
+                                  the density chain of the march and the one-pass render (f2n_density_march,
+                                  _march_occ, f2n_render_rays, _head, _tail): 0 by vertex parity (load j
+                                  fetches the vertex of the lane's cell whose coordinate parities are j,
+                                  so lanes in neighbouring cells ask for a shared vertex in the same
+                                  load), 1 by corner (load d fetches corner d of the lane's own cell);
+                                  the same rows, the same sum, the same bits                         */
+#define F2N_OPT2_COUNT 1
 int f2n_set_option(int key, int value);
 int f2n_get_option(int key);
 

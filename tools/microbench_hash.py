@@ -3,6 +3,13 @@
 torch.cuda events on the current stream (the stream the kernels are launched on).
 
   python tools/microbench_hash.py [--config c2|c5|c1] [--n N] [--reps R]
+  python tools/microbench_hash.py --corner-order [--levels 0,4,8,10,12,14,15] [--reps R]
+
+--corner-order: f2n_hash_fwd_raytile on the contracted points of one chunk of the benchmark's
+headline (65 536 rays of an 800 x 800 view in pixel-compact bundles, 128 jittered samples), ONE level
+at a time (L = 1 with that level's mul), with the corner loads in corner order (GATHER_PAIRED = 1) and
+in vertex-parity order (= 0), the two arms alternating call by call; one JSON line per level, to be
+set beside the line counts of tools/gather_lines_model.py.
 
 Reports ms and algorithmic GB/s (SURVEY.md 8d bytes) per variant; used to choose layouts/kernels.
 """
@@ -30,6 +37,71 @@ def timeit(fn, reps):
     return ts[len(ts) // 2], ts[0]
 
 
+def alternating(fns, reps, warmup=2):
+    """{arm: [ms, ...]}: the arms take turns call by call, each call timed between synchronisations"""
+    ms = {k: [] for k in fns}
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    for it in range(warmup + reps):
+        for k, fn in fns.items():
+            torch.cuda.synchronize()
+            ev[0].record()
+            fn()
+            ev[1].record()
+            torch.cuda.synchronize()
+            if it >= warmup:
+                ms[k].append(ev[0].elapsed_time(ev[1]))
+    return ms
+
+
+def corner_order_arm(args, capi, dev):
+    import json
+
+    sys.path.insert(0, ROOT)
+    from bench import fox_like_poses
+
+    H = importlib.import_module("f2-nerf_amd").load_host()
+    n_rays, S, F, log2_T, Lfull = 65536, 128, 2, 19, 16
+    T = 1 << log2_T
+    g = torch.Generator(device=dev).manual_seed(0)
+    intr = torch.tensor([[1111.1, 0, 400.0], [0, 1111.1, 400.0], [0, 0, 1.0]], device=dev)
+    o, d = H.get_view_rays(fox_like_poses(50)[7].to(dev), intr, 800, 800)
+    lo = 4 * n_rays                                           # the view's fifth chunk: image rows 327-409
+    o, d = o[lo:lo + n_rays], d[lo:lo + n_rays]
+    order = H.ray_order(d.contiguous())                       # the Renderer's pixel-compact bundles
+    o, d = o[order].contiguous(), d[order].contiguous()
+    n = n_rays * S
+    u = torch.rand(n_rays, S, device=dev, generator=g)        # the raw draw: sample_dense cooks it (TRAIN)
+    pts, dt, t = torch.empty(n, 3, device=dev), torch.empty(n, device=dev), torch.empty(n, device=dev)
+    bounds = torch.empty(n_rays, 2, device=dev, dtype=torch.int32)
+    dirs = torch.empty(n_rays, 3, device=dev)
+    capi.call("sample_dense", o, d, u, None, 1, pts, dt, t, bounds, dirs, n_rays, S, 4.0 / S)
+    table = torch.randn(T * F, device=dev, generator=g) * 0.1
+    table16 = torch.empty(T * F, dtype=torch.int16, device=dev)
+    capi.call("table_to_f16", table, table16, T * F)
+    out = torch.empty(F, n, device=dev)
+    for l in [int(v) for v in args.levels.split(",")]:
+        primes = (torch.randint(1 << 28, 1 << 30, (1, 3), device=dev, generator=g).to(torch.int32) | 1)
+        bias = torch.rand(1, 3, device=dev, generator=g) * 1000 + 100
+        mul = torch.tensor([2.0 ** (7.0 * l / (Lfull - 1) + 3.0)], device=dev)
+
+        def run(order_value):
+            def fn():
+                capi.set_option("GATHER_PAIRED", order_value)
+                capi.call("hash_fwd_raytile", pts, table16, primes, bias, mul, out, n_rays, S, 1, F, T, T * F)
+            return fn
+
+        ms = alternating({"corner": run(1), "parity": run(0)}, args.reps)
+        capi.set_option("GATHER_PAIRED", 0)
+        med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+        print(json.dumps(dict(
+            what="hash_fwd_raytile, one level", level=l, mul=round(float(mul[0]), 2), rays=n_rays, samples=S,
+            ms_corner=round(med["corner"], 4), ms_parity=round(med["parity"], 4),
+            ratio=round(med["parity"] / med["corner"], 3),
+            ms_corner_all=[round(v, 4) for v in ms["corner"]], ms_parity_all=[round(v, 4) for v in ms["parity"]],
+            ggathers_per_s_corner=round(8 * n / med["corner"] / 1e6, 1),
+            ggathers_per_s_parity=round(8 * n / med["parity"] / 1e6, 1))), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c2")
@@ -40,9 +112,14 @@ def main():
                          "an 800-wide pinhole view (focal 1111, camera at distance 1), ray-major as the "
                          "renderer emits them; view_sm: the same points sample-major (lane = adjacent pixel)")
     ap.add_argument("--fwd-only", action="store_true")
+    ap.add_argument("--corner-order", action="store_true",
+                    help="only the per-level arm of the two corner orders on one headline chunk")
+    ap.add_argument("--levels", default="0,4,8,10,12,14,15")
     args = ap.parse_args()
     capi = importlib.import_module("f2-nerf_amd").capi
     dev = torch.device("cuda:0")
+    if args.corner_order:
+        return corner_order_arm(args, capi, dev)
     cfg = {"c2": (16, 2, 19, None, 65536 * 128), "c1": (4, 2, 19, None, 65536 * 64),
            "c4": (16, 2, 19, None, 512 * 1024),
            "c5": (16, 8, 22, "disjoint", 1 << 24)}[args.config]

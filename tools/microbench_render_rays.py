@@ -20,8 +20,11 @@ first 64 samples eight rays to a wavefront and the survivors one wavefront each,
 a wavefront); all arms -- off, on, and these -- alternate call by call, and the lines are appended to
 profiles/render_rays_head_ab.jsonl unless --out names another file.
 
+--corner-order doubles every arm: once with the density chain's corner loads in vertex-parity order
+(F2N_OPT_GATHER_PAIRED = 0, the default) and once in corner order (= 1, arms named "...+corner").
+
   python tools/microbench_render_rays.py [--shapes a,b,c] [--reps 5] [--warmup 2] [--out FILE]
-                                         [--head 0,64,-1] [--profile DIR]
+                                         [--head 0,64,-1] [--corner-order] [--profile DIR]
 """
 import argparse
 import importlib
@@ -42,17 +45,22 @@ def _median(v):
 
 
 HEADS = []   # --head: further arms "head=<n>" after "off" and "on"
+CORNER = []  # --corner-order: every arm again as "<arm>+corner" with F2N_OPT_GATHER_PAIRED = 1
 
 
 def _arms():
-    return ["off", "on"] + ["head=%d" % h for h in HEADS]
+    arms = ["off", "on"] + ["head=%d" % h for h in HEADS]
+    return arms + [a + "+corner" for a in arms] if CORNER else arms
 
 
 def _ab(torch, hr, fn, reps, warmup):
     """{arm: [ms, ...]} with the arms alternating call by call"""
+    capi = importlib.import_module("f2-nerf_amd").capi
     ms = {arm: [] for arm in _arms()}
     for it in range(warmup + reps):
-        for arm in _arms():
+        for arm_order in _arms():
+            arm = arm_order.replace("+corner", "")
+            capi.set_option("GATHER_PAIRED", int(arm_order.endswith("+corner")))
             hr.set_one_pass(arm != "off")
             hr.set_one_pass_head(int(arm[5:]) if arm.startswith("head=") else 0)
             torch.cuda.synchronize()
@@ -60,7 +68,8 @@ def _ab(torch, hr, fn, reps, warmup):
             fn()
             torch.cuda.synchronize()
             if it >= warmup:
-                ms[arm].append((time.perf_counter() - t0) * 1e3)
+                ms[arm_order].append((time.perf_counter() - t0) * 1e3)
+    capi.set_option("GATHER_PAIRED", 0)
     hr.set_one_pass(False)
     hr.set_one_pass_head(0)
     return ms
@@ -141,14 +150,19 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--head", default="", metavar="N,N,..",
                     help="further arms: one_pass with one_pass_head = N (0, -1 or a multiple of 64)")
+    ap.add_argument("--corner-order", action="store_true",
+                    help="every arm also with F2N_OPT_GATHER_PAIRED = 1 (the density chain in corner order)")
     ap.add_argument("--profile", default="", metavar="DIR",
                     help="also one rocprofv3 --kernel-trace --stats run of shape a into DIR")
     args = ap.parse_args()
     HEADS[:] = [int(v) for v in args.head.split(",") if v]
+    CORNER[:] = [True] if args.corner_order else []
     if args.shape:
         run_shape(args.shape, args.reps, args.warmup)
         return 0
     me = [sys.executable, os.path.abspath(__file__), "--reps", str(args.reps), "--warmup", str(args.warmup)]
+    if CORNER:
+        me += ["--corner-order"]
     if HEADS:
         me += ["--head=" + args.head]
         if not args.out:
