@@ -8,6 +8,9 @@
 // workgroup is level-uniform: mul/bias/primes/level base live in SGPRs (scalar loads), and because
 // x is the fast grid dimension the chip works through one level at a time -- the live part of the
 // table is one level (T*F*2 bytes: 2 MiB at the reference size), which an XCD's 4 MiB L2 holds.
+// The dense-grid forward's default route (hash_fwd_raytile_kernel_groups) has blockIdx.y = a group
+// of consecutive levels instead: several where a level touches few lines, one or two where the
+// table levels are what fills the L2.
 #include "hash_grid.hiph"
 
 
@@ -72,6 +75,88 @@ __global__ __launch_bounds__(F2N_BLOCK) void hash_fwd_kernel(
 }
 
 
+// ---- what a ray tile decides from its own points, for both tile kernels below -------------------
+// ptile: the tile's points in LDS, [64 rays][3 * SAMPLES + 1] floats, complete (behind a barrier).
+
+// Which way do the 64 lanes of a gather walk the tile?  The cost of a gather instruction is its
+// number of distinct 128-byte lines (tools/probes/gather_policy.hip), i.e. of distinct cells:
+//   across  lane = ray, all at one sample index: neighbouring pixels of a view sit 1-4 fine cells
+//           apart at one depth (image-ordered batches, the renderer's whole-view chunks);
+//   along   lane = consecutive samples of one ray (64 / SAMPLES rays per instruction): the
+//           reference's 1024 steps of 1/256 put up to 32 consecutive samples in one coarse cell
+//           (random training rays: neighbouring rays share nothing).
+// Decided per tile from its own points: the walk with the smaller extent touches fewer cells.
+// sorted: across, third variant (walk 3, and the default when a tile that walks across has
+// drifted), see raytile_depth_order.  walk: F2N_OPT_RAYTILE_WALK.
+template <int SAMPLES>
+__device__ __forceinline__ void raytile_walk_choice(
+  const float * ptile, int walk, bool & along, bool & sorted)
+{
+  constexpr int RAYS = 64, kPPitch = 3 * SAMPLES + 1;
+  // Distinct cells of size c touched by one gather: across ~ (e / c + 1) for rays strung along a
+  // pixel row of extent e, times the depth cloud the TRAIN jitter adds (neighbouring rays then sit
+  // a random e1 apart at one sample index); along ~ 2 rays x (s / c + 1) for a ray segment of
+  // length s.  Across wins when e + 8 e1 < 2 s: image-ordered batches, jittered (0.15 + 8 x 0.07
+  // against 2 x 1.0 at 128 samples) or not, near or far; random rays (e, e1 ~ 1.5) walk along.
+  constexpr int m = SAMPLES / 2;
+  auto dist = [&](int ra, int sa, int rb, int sb) {
+    const float * a = ptile + ra * kPPitch + 3 * sa, * b = ptile + rb * kPPitch + 3 * sb;
+    const float dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
+    return sqrtf(dx * dx + dy * dy + dz * dz);
+  };
+  const float e = dist(RAYS - 1, m, 0, m), e1 = dist(1, m, 0, m), sl = dist(0, SAMPLES - 1, 0, 0);
+  along = !(e + 8.f * e1 < 2.f * sl);
+  if (walk) along = (walk == 2);
+  // neighbouring rays more than a third of a step apart at one sample index: jittered depths
+  // (un-jittered views sit a pixel apart there, 0.06 steps: nothing to sort, 4 % to lose)
+  // (three pairs of neighbours: one pair is that close by chance in a fifth of the jittered tiles)
+  const float apart =
+    fmaxf(e1, fmaxf(dist(RAYS / 2 + 1, m, RAYS / 2, m), dist(RAYS - 1, m, RAYS - 2, m)));
+  const bool drifted = apart * (float)(SAMPLES - 1) > 0.35f * sl;
+  sorted = !along && (walk == 3 || (walk == 0 && drifted));
+}
+
+// The tile's 64 x SAMPLES (ray, sample) pairs in DEPTH order: order[i] = ray * SAMPLES + sample.
+// TRAIN jitter lets the rays of a tile drift +-2.5 steps apart in depth by mid-ray, so "all rays at
+// one sample index" is a cloud 5 steps deep and the mid levels (cells of 0.3-1 step) stop sharing
+// lines; 64 pairs taken from a counting sort by depth along the middle ray (64 bins of half a step)
+// form a slab one step thick instead.  The order of the pairs means nothing to the result.  Called
+// by the whole workgroup; order [64 * SAMPLES] and bin_at [64] in LDS; ends with a barrier.
+template <int SAMPLES>
+__device__ __forceinline__ void raytile_depth_order(
+  const float * ptile, uint16_t * order, uint32_t * bin_at)
+{
+  constexpr int RAYS = 64, kPPitch = 3 * SAMPLES + 1;
+  constexpr int kPairs = RAYS * SAMPLES / 256;  // per thread
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float * mid = ptile + (RAYS / 2) * kPPitch;
+  const float ax = mid[3 * (SAMPLES - 1)] - mid[0], ay = mid[3 * (SAMPLES - 1) + 1] - mid[1],
+              az = mid[3 * (SAMPLES - 1) + 2] - mid[2];
+  const float inv = 64.f / fmaxf(ax * ax + ay * ay + az * az, 1e-30f);
+  const float ox = mid[0], oy = mid[1], oz = mid[2];
+  if (threadIdx.x < 64) bin_at[threadIdx.x] = 0u;
+  __syncthreads();
+  int my_bin[kPairs];
+#pragma unroll
+  for (int i = 0; i < kPairs; i++) {
+    const int pair = threadIdx.x + 256 * i, ray = pair / SAMPLES, ks = pair % SAMPLES;
+    const float * p = ptile + ray * kPPitch + 3 * ks;
+    const float d = (p[0] - ox) * ax + (p[1] - oy) * ay + (p[2] - oz) * az;
+    my_bin[i] = min(max((int)(d * inv), 0), 63);  // (a NaN point lands in bin 0)
+    atomicAdd(&bin_at[my_bin[i]], 1u);
+  }
+  __syncthreads();
+  if (wave == 0) {
+    const int c = (int)bin_at[lane];
+    bin_at[lane] = (uint32_t)(wave_incl_scan_i32(c) - c);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < kPairs; i++)
+    order[atomicAdd(&bin_at[my_bin[i]], 1u)] = (uint16_t)(threadIdx.x + 256 * i);
+  __syncthreads();
+}
+
 // Forward for a dense [n_rays, S] sample grid (ray-major in memory, as the sampler emits it) whose
 // rays are neighbouring pixels.  Consecutive samples of ONE ray are ~40 finest-level cells apart,
 // the same sample index on ADJACENT pixels ~1-4 cells: with lane = ray at a fixed depth the
@@ -113,75 +198,11 @@ __global__ __launch_bounds__(F2N_BLOCK) void hash_fwd_raytile_kernel(
   }
   const LevelParams lp = load_level(primes, bias, mul, l);
   __syncthreads();
-  // Which way do the 64 lanes of a gather walk the tile?  The cost of a gather instruction is its
-  // number of distinct 128-byte lines (tools/probes/gather_policy.hip), i.e. of distinct cells:
-  //   across  lane = ray, all at one sample index: neighbouring pixels of a view sit 1-4 fine cells
-  //           apart at one depth (image-ordered batches, the renderer's whole-view chunks);
-  //   along   lane = consecutive samples of one ray (64 / SAMPLES rays per instruction): the
-  //           reference's 1024 steps of 1/256 put up to 32 consecutive samples in one coarse cell
-  //           (random training rays: neighbouring rays share nothing).
-  // Decided per tile from its own points: the walk with the smaller extent touches fewer cells.
-  bool along, drifted;
-  {
-    // Distinct cells of size c touched by one gather: across ~ (e / c + 1) for rays strung along a
-    // pixel row of extent e, times the depth cloud the TRAIN jitter adds (neighbouring rays then sit
-    // a random e1 apart at one sample index); along ~ 2 rays x (s / c + 1) for a ray segment of
-    // length s.  Across wins when e + 8 e1 < 2 s: image-ordered batches, jittered (0.15 + 8 x 0.07
-    // against 2 x 1.0 at 128 samples) or not, near or far; random rays (e, e1 ~ 1.5) walk along.
-    constexpr int m = SAMPLES / 2;
-    auto dist = [&](int ra, int sa, int rb, int sb) {
-      const float dx = ptile[ra][3 * sa] - ptile[rb][3 * sb], dy = ptile[ra][3 * sa + 1] - ptile[rb][3 * sb + 1],
-                  dz = ptile[ra][3 * sa + 2] - ptile[rb][3 * sb + 2];
-      return sqrtf(dx * dx + dy * dy + dz * dz);
-    };
-    const float e = dist(RAYS - 1, m, 0, m), e1 = dist(1, m, 0, m), sl = dist(0, SAMPLES - 1, 0, 0);
-    along = !(e + 8.f * e1 < 2.f * sl);
-    if (walk) along = (walk == 2);
-    // neighbouring rays more than a third of a step apart at one sample index: jittered depths
-    // (un-jittered views sit a pixel apart there, 0.06 steps: nothing to sort, 4 % to lose)
-    // (three pairs of neighbours: one pair is that close by chance in a fifth of the jittered tiles)
-    const float apart = fmaxf(e1, fmaxf(dist(RAYS / 2 + 1, m, RAYS / 2, m), dist(RAYS - 1, m, RAYS - 2, m)));
-    drifted = apart * (float)(SAMPLES - 1) > 0.35f * sl;
-  }
-  // Across, third variant (walk 3, and the default when a tile that walks across has drifted): the tile's
-  // 64 x SAMPLES (ray, sample) pairs in DEPTH order.  TRAIN jitter lets the rays of a tile drift
-  // +-2.5 steps apart in depth by mid-ray, so "all rays at one sample index" is a cloud 5 steps deep
-  // and the mid levels (cells of 0.3-1 step) stop sharing lines; 64 pairs taken from a counting sort
-  // by depth along the middle ray (64 bins of half a step) form a slab one step thick instead.  The
-  // order of the pairs means nothing to the result.
   __shared__ uint16_t order[RAYS * SAMPLES];
   __shared__ uint32_t bin_at[64];
-  const bool sorted = !along && (walk == 3 || (walk == 0 && drifted));
-  if (sorted) {
-    constexpr int kPairs = RAYS * SAMPLES / 256;  // per thread
-    constexpr int mr = RAYS / 2;
-    const float ax = ptile[mr][3 * (SAMPLES - 1)] - ptile[mr][0],
-                ay = ptile[mr][3 * (SAMPLES - 1) + 1] - ptile[mr][1],
-                az = ptile[mr][3 * (SAMPLES - 1) + 2] - ptile[mr][2];
-    const float inv = 64.f / fmaxf(ax * ax + ay * ay + az * az, 1e-30f);
-    const float ox = ptile[mr][0], oy = ptile[mr][1], oz = ptile[mr][2];
-    if (threadIdx.x < 64) bin_at[threadIdx.x] = 0u;
-    __syncthreads();
-    int my_bin[kPairs];
-#pragma unroll
-    for (int i = 0; i < kPairs; i++) {
-      const int pair = threadIdx.x + 256 * i, ray = pair / SAMPLES, ks = pair % SAMPLES;
-      const float d = (ptile[ray][3 * ks] - ox) * ax + (ptile[ray][3 * ks + 1] - oy) * ay +
-                      (ptile[ray][3 * ks + 2] - oz) * az;
-      my_bin[i] = min(max((int)(d * inv), 0), 63);  // (a NaN point lands in bin 0)
-      atomicAdd(&bin_at[my_bin[i]], 1u);
-    }
-    __syncthreads();
-    if (wave == 0) {
-      const int c = (int)bin_at[lane];
-      bin_at[lane] = (uint32_t)(wave_incl_scan_i32(c) - c);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < kPairs; i++)
-      order[atomicAdd(&bin_at[my_bin[i]], 1u)] = (uint16_t)(threadIdx.x + 256 * i);
-    __syncthreads();
-  }
+  bool along, sorted;
+  raytile_walk_choice<SAMPLES>(&ptile[0][0], walk, along, sorted);
+  if (sorted) raytile_depth_order<SAMPLES>(&ptile[0][0], order, bin_at);
   constexpr int kRaysPerIter = 64 / SAMPLES;  // along: rays one wave instruction covers
   // The 8 corner loads of a sample, in vertex-parity order (corner_order 0: lanes in neighbouring
   // cells ask for the vertices they share in the same load, see gather_blend_paired) or in corner
@@ -230,6 +251,135 @@ __global__ __launch_bounds__(F2N_BLOCK) void hash_fwd_raytile_kernel(
       }
     }
   }
+}
+
+// The same tile taken through a GROUP of consecutive levels by one workgroup: grid = (tiles,
+// groups), group g = the levels from the g-th set bit of group_starts (bit l set: level l opens a
+// group; bit 0 is implied) up to the next set bit or L.  In hash_fwd_raytile_kernel every level's
+// workgroup loads the tile's points, waits for them, takes the walk decision and sorts the pairs
+// by depth anew, and none of that depends on the level: a one-level launch costs 0.09 ms of a
+// headline chunk before its gathers cost anything (NOTES 25), sixteen times per chunk.  Here all
+// of it happens once per group; the lane's SAMPLES / 4 (ray, sample) pairs and their coordinates
+// then sit in registers, and the level loop holds only rows, gathers, blend and the results' way
+// out.  The level is the loop's counter, so its parameters stay scalar loads.  Per sample and
+// level the calls are hash_fwd_raytile_kernel's own: the same bits.
+//
+// LDS: result tile 0, then a second region that holds the points, the depth order and the bins
+// during the prologue and result tile 1 afterwards.  Level i of a group writes tile i & 1, so the
+// float4 stores of one level leave while the next level gathers, with one barrier per level: a
+// tile is written again two levels later, and every thread has passed the barrier in between only
+// after its own reads of that tile.  (The prologue's region is first overwritten by the group's
+// second level, behind the first level's barrier.) The second tile costs no instantiation a
+// workgroup per CU.
+//
+// Tiles are the fast grid dimension as before: the chip works through one group at a time, and
+// what is live of the table is the group's levels.  Which levels share is the caller's mask, or
+// raytile_default_groups' (all sixteen levels in one group are no faster than one level each).
+template <int F, bool POW2, int SAMPLES>
+__global__ __launch_bounds__(F2N_BLOCK) void hash_fwd_raytile_kernel_groups(
+  const float * __restrict__ pts, const uint16_t * __restrict__ table,
+  const int32_t * __restrict__ primes, const float * __restrict__ bias,
+  const float * __restrict__ mul, float * __restrict__ out, int n_rays, int S, int L, uint32_t T,
+  int64_t level_stride, int walk, int corner_order, uint32_t group_starts)
+{
+  static_assert(F2N_BLOCK == 256 && SAMPLES % 16 == 0, "4 waves, float4 runs");
+  constexpr int RAYS = 64, kPitch = SAMPLES + 4, kPPitch = 3 * SAMPLES + 1;
+  constexpr int kPairs = SAMPLES / 4;  // (ray, sample) pairs per thread
+  // in 4-byte words: one result tile; points, order (uint16) and bins of the prologue
+  constexpr int kTile = F * RAYS * kPitch, kChan = RAYS * kPitch;
+  constexpr int kPts = RAYS * kPPitch, kOrder = RAYS * SAMPLES / 2, kBins = 64;
+  constexpr int kSecond = (kTile > kPts + kOrder + kBins) ? kTile : (kPts + kOrder + kBins);
+  __shared__ __attribute__((aligned(16))) float lds[kTile + kSecond];
+  float * const ptile = lds + kTile;  // [RAYS][kPPitch]
+  uint16_t * const order = reinterpret_cast<uint16_t *>(ptile + kPts);
+  uint32_t * const bin_at = reinterpret_cast<uint32_t *>(ptile + kPts + kOrder);
+
+  // the group's levels [l0, l1): drop blockIdx.y set bits, the lowest left opens this group
+  uint32_t starts = group_starts | 1u;
+  for (int g = blockIdx.y; g > 0; g--) starts &= starts - 1u;
+  const int l0 = __builtin_ctz(starts);
+  starts &= starts - 1u;
+  const int l1 = starts ? __builtin_ctz(starts) : L;
+
+  const int tiles_s = S / SAMPLES;
+  const int r0 = (int)(blockIdx.x / tiles_s) * RAYS, k0 = (int)(blockIdx.x % tiles_s) * SAMPLES;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t n = (int64_t)n_rays * S;
+#pragma unroll
+  for (int i = 0; i < RAYS * 3 * SAMPLES / 256; i++) {
+    const int idx = threadIdx.x + 256 * i;
+    const int ray = idx / (3 * SAMPLES), off = idx % (3 * SAMPLES);
+    const int r = min(r0 + ray, n_rays - 1);  // clamped: tail rays redo the last ray, never stored
+    ptile[ray * kPPitch + off] = pts[((int64_t)r * S + k0) * 3 + off];
+  }
+  __syncthreads();
+  bool along, sorted;
+  raytile_walk_choice<SAMPLES>(ptile, walk, along, sorted);
+  if (sorted) raytile_depth_order<SAMPLES>(ptile, order, bin_at);
+  // This lane's pairs, fixed for every level of the group: coordinates and place in a result tile.
+  constexpr int kRaysPerIter = 64 / SAMPLES;  // along: rays one wave instruction covers
+  float px[kPairs], py[kPairs], pz[kPairs];
+  int at[kPairs];
+#pragma unroll
+  for (int j = 0; j < kPairs; j++) {
+    int ks = along ? (lane % SAMPLES) : (j * 4 + wave);
+    int ray = along ? ((j * 4 + wave) * kRaysPerIter + lane / SAMPLES) : lane;
+    if (sorted) {
+      const int pair = order[(j * 4 + wave) * 64 + lane];
+      ray = pair / SAMPLES;
+      ks = pair % SAMPLES;
+    }
+    const float * p = ptile + ray * kPPitch + 3 * ks;
+    px[j] = p[0];
+    py[j] = p[1];
+    pz[j] = p[2];
+    at[j] = ray * kPitch + ks;
+  }
+  // One level loop per corner order (F2N_OPT_GATHER_PAIRED), so that neither carries the other's
+  // registers.
+  auto run_levels = [&](auto paired) {
+    float * tl = lds;
+#pragma unroll 1
+    for (int l = l0; l < l1; l++) {
+      const LevelParams lp = load_level(primes, bias, mul, l);
+      const uint16_t * level_base = table + level_stride * l;
+#pragma unroll
+      for (int j = 0; j < kPairs; j++) {
+        uint32_t row[8];
+        float w[8], acc[F];
+        if constexpr (decltype(paired)::value) {
+          const uint32_t m = slot_rows_and_weights<POW2>(px[j], py[j], pz[j], lp, T, row, w);
+          gather_blend_paired<F>(level_base, row, m, w, acc);
+        } else {
+          corner_rows_and_weights<POW2>(px[j], py[j], pz[j], lp, T, row, w);
+          gather_blend<F>(level_base, row, w, acc);
+        }
+#pragma unroll
+        for (int k = 0; k < F; k++) tl[k * kChan + at[j]] = round_f16(acc[k]);
+      }
+      __syncthreads();
+      // RAYS x (SAMPLES / 4) float4 per channel, SAMPLES / 16 per thread
+#pragma unroll
+      for (int i = 0; i < SAMPLES / 16; i++) {
+        const int idx = threadIdx.x + 256 * i;
+        const int ray = idx / (SAMPLES / 4), quad = idx % (SAMPLES / 4);
+        if (r0 + ray < n_rays) {
+#pragma unroll
+          for (int k = 0; k < F; k++) {
+            const float4 v =
+              *reinterpret_cast<const float4 *>(&tl[k * kChan + ray * kPitch + 4 * quad]);
+            *reinterpret_cast<float4 *>(
+              out + (int64_t)(l * F + k) * n + (int64_t)(r0 + ray) * S + k0 + 4 * quad) = v;
+          }
+        }
+      }
+      tl = (tl == lds) ? lds + kTile : lds;
+    }
+  };
+  if (corner_order == 0)
+    run_levels(std::true_type{});
+  else
+    run_levels(std::false_type{});
 }
 
 // ---------------------------------------------------------------------------- backward ---------
@@ -480,32 +630,82 @@ extern "C" int f2n_hash_fwd(
   return f2n_launch_status();
 }
 
-extern "C" int f2n_hash_fwd_raytile(
+// Which levels open a group when the caller names none, from a level's position l / (L - 1) (mul
+// lives on the device) and the number of tiles.  tools/microbench_hash.py --level-groups, L = 16,
+// NOTES 26:
+//   kFewTiles tiles and more   the levels below position 2/3 in one group, the finer ones two to a
+//       group: {0-9} {10, 11} {12, 13} {14, 15}.  Two fine levels of the reference's overlapping
+//       windows are 3 MiB of table, which an XCD's 4 MiB L2 still holds; three together are slower
+//       than each alone.  On a headline chunk (4096 tiles) three schedules of this kind lie within
+//       0.5 % of each other and ahead of the rest; this is one of them.
+//   fewer   the levels below 2/5 in one group, those below 2/3 in a second, every finer one alone:
+//       {0-5} {6-9} 10 11 12 13 14 15.  A grid of few tiles needs the workgroups: at 128 and 256
+//       tiles this is 15-30 % ahead of the schedule above, at 512 level with it, from 1024 on
+//       2 % behind.  (Every schedule timed is ahead of one level per workgroup at every tile
+//       count.)
+// Positions are compared as fractions, in integers.
+constexpr int64_t kFewTiles = 1024;
+
+static uint32_t raytile_default_groups(int L, int64_t tiles)
+{
+  const bool few = tiles < kFewTiles;
+  uint32_t starts = 1u;
+  int first_fine = -1;
+  bool middle_open = false;
+  for (int l = 1; l < L; l++) {
+    if (3 * l >= 2 * (L - 1)) {  // position >= 2/3
+      if (first_fine < 0) first_fine = l;
+      if (few || (l - first_fine) % 2 == 0) starts |= 1u << l;
+    } else if (few && 5 * l >= 2 * (L - 1) && !middle_open) {  // the first at position >= 2/5
+      starts |= 1u << l;
+      middle_open = true;
+    }
+  }
+  return starts;
+}
+
+// What both ray-tile entries check, in f2n_hash_fwd_raytile's order.
+static int raytile_args_status(
   const float * pts, const uint16_t * table_f16, const int32_t * primes, const float * bias,
   const float * mul, float * out_cm, int n_rays, int S, int L, int F, uint32_t T,
-  int64_t level_stride, void * stream)
+  int64_t level_stride)
 {
   if (!pts || !table_f16 || !primes || !bias || !mul || !out_cm) return F2N_E_INVALID_ARG;
   if (F != 1 && F != 2 && F != 4 && F != 8) return F2N_E_UNSUPPORTED;
   if (n_rays < 0 || S <= 0) return F2N_E_INVALID_ARG;
   if (S % 16) return F2N_E_UNSUPPORTED;  // callers fall back to f2n_hash_fwd
-  const int64_t n = (int64_t)n_rays * S;
-  if (!f2n_hash_args_ok(n, L, F, T, level_stride)) return F2N_E_INVALID_ARG;
+  if (!f2n_hash_args_ok((int64_t)n_rays * S, L, F, T, level_stride)) return F2N_E_INVALID_ARG;
   if (reinterpret_cast<uintptr_t>(table_f16) % (2u * F)) return F2N_E_INVALID_ARG;
   if (reinterpret_cast<uintptr_t>(out_cm) & 15u) return F2N_E_INVALID_ARG;
-  if (n == 0) return F2N_OK;
+  return F2N_OK;
+}
+
+// Arguments checked.  ts: samples per tile; group_starts 0: hash_fwd_raytile_kernel on a (tiles, L)
+// grid, else hash_fwd_raytile_kernel_groups on (tiles, groups).
+static int raytile_launch(
+  const float * pts, const uint16_t * table_f16, const int32_t * primes, const float * bias,
+  const float * mul, float * out_cm, int n_rays, int S, int L, int F, uint32_t T,
+  int64_t level_stride, int ts, uint32_t group_starts, void * stream)
+{
   const int walk = f2n_get_option(F2N_OPT_RAYTILE_WALK);
   const int corner_order = f2n_get_option(F2N_OPT_GATHER_PAIRED);
-  const int want = f2n_get_option(F2N_OPT_RAYTILE);  // samples per tile: 16 | 32 (measurements)
-  const int ts = (want == 16) ? 16 : (S % 32 == 0 ? 32 : 16);
   const int64_t tiles = (int64_t)f2n_div_up(n_rays, 64) * (S / ts);
   if (tiles > 0x7fffffff) return F2N_E_INVALID_ARG;
-  const dim3 grid((unsigned)tiles, (unsigned)L), block(F2N_BLOCK);
+  const unsigned rows = group_starts ? (unsigned)__builtin_popcount(group_starts) : (unsigned)L;
+  const dim3 grid((unsigned)tiles, rows), block(F2N_BLOCK);
   hipStream_t s = (hipStream_t)stream;
   f2n_dispatch_field(F, T, [&](auto ff, auto p2) {
     constexpr int FF = decltype(ff)::value;
     constexpr bool P2 = decltype(p2)::value;
-    if (ts == 16)
+    if (group_starts && ts == 16)
+      hipLaunchKernelGGL(
+        (hash_fwd_raytile_kernel_groups<FF, P2, 16>), grid, block, 0, s, pts, table_f16, primes,
+        bias, mul, out_cm, n_rays, S, L, T, level_stride, walk, corner_order, group_starts);
+    else if (group_starts)
+      hipLaunchKernelGGL(
+        (hash_fwd_raytile_kernel_groups<FF, P2, 32>), grid, block, 0, s, pts, table_f16, primes,
+        bias, mul, out_cm, n_rays, S, L, T, level_stride, walk, corner_order, group_starts);
+    else if (ts == 16)
       hipLaunchKernelGGL(
         (hash_fwd_raytile_kernel<FF, P2, 16>), grid, block, 0, s, pts, table_f16, primes, bias, mul,
         out_cm, n_rays, S, T, level_stride, walk, corner_order);
@@ -515,6 +715,49 @@ extern "C" int f2n_hash_fwd_raytile(
         out_cm, n_rays, S, T, level_stride, walk, corner_order);
   });
   return f2n_launch_status();
+}
+
+extern "C" int64_t f2n_hash_raytile_default_groups(int L, int64_t tiles)
+{
+  if (L < 1 || tiles < 0) return F2N_E_INVALID_ARG;
+  if (L > 32) return F2N_E_UNSUPPORTED;
+  return (int64_t)raytile_default_groups(L, tiles);
+}
+
+extern "C" int f2n_hash_fwd_raytile(
+  const float * pts, const uint16_t * table_f16, const int32_t * primes, const float * bias,
+  const float * mul, float * out_cm, int n_rays, int S, int L, int F, uint32_t T,
+  int64_t level_stride, void * stream)
+{
+  const int st = raytile_args_status(
+    pts, table_f16, primes, bias, mul, out_cm, n_rays, S, L, F, T, level_stride);
+  if (st != F2N_OK) return st;
+  if (n_rays == 0) return F2N_OK;
+  // F2N_OPT_RAYTILE 0: the level groups, tiles of 32 samples where S allows; 16 | 32: one level per
+  // workgroup with tiles of that many samples (the A/B arm)
+  const int want = f2n_get_option(F2N_OPT_RAYTILE);
+  const int ts = (want == 16) ? 16 : (S % 32 == 0 ? 32 : 16);
+  return raytile_launch(
+    pts, table_f16, primes, bias, mul, out_cm, n_rays, S, L, F, T, level_stride, ts,
+    want ? 0u : raytile_default_groups(L, (int64_t)f2n_div_up(n_rays, 64) * (S / ts)), stream);
+}
+
+extern "C" int f2n_hash_fwd_raytile_groups(
+  const float * pts, const uint16_t * table_f16, const int32_t * primes, const float * bias,
+  const float * mul, float * out_cm, int n_rays, int S, int L, int F, uint32_t T,
+  int64_t level_stride, uint32_t group_starts, void * stream)
+{
+  if (!pts || !table_f16 || !primes || !bias || !mul || !out_cm) return F2N_E_INVALID_ARG;
+  if (L > 32) return F2N_E_UNSUPPORTED;
+  const int st = raytile_args_status(
+    pts, table_f16, primes, bias, mul, out_cm, n_rays, S, L, F, T, level_stride);
+  if (st != F2N_OK) return st;
+  // a group that opens past the last level
+  if (L < 32 && (group_starts >> L)) return F2N_E_INVALID_ARG;
+  if (n_rays == 0) return F2N_OK;
+  return raytile_launch(
+    pts, table_f16, primes, bias, mul, out_cm, n_rays, S, L, F, T, level_stride,
+    S % 32 == 0 ? 32 : 16, group_starts | 1u, stream);
 }
 
 extern "C" int f2n_hash_bwd(

@@ -52,7 +52,10 @@ const char * f2n_status_string(int status);
 #define F2N_OPT_SHADE_VARIANT 2 /* matrix-core backward at one wave per SIMD: 0 phases may overlap, 1
                                   phase-fenced (the two-wave form: F2N_OPT_SHADE_BWD_WAVES); the
                                   matrix-core FORWARD: 0 four waves per SIMD, 3 three, 2 two          */
-#define F2N_OPT_RAYTILE 3       /* samples per ray tile of f2n_hash_fwd_raytile: 0 auto, 16, 32     */
+#define F2N_OPT_RAYTILE 3       /* f2n_hash_fwd_raytile: 0 a workgroup takes its ray tile (32 samples,
+                                  16 unless S % 32 == 0) through a group of levels
+                                  (f2n_hash_raytile_default_groups); 16, 32: one level per
+                                  workgroup, tiles of that many samples; same bits                */
 #define F2N_OPT_HASH_BWD 4      /* f2n_hash_bwd route: 0 auto, 1 global atomics, 2 LDS-sliced       */
 #define F2N_OPT_BWD_COMBINE 5   /* binned backward: 0 combine coarse levels per tile, 1 never       */
 #define F2N_OPT_RAYTILE_WALK 6  /* lanes of f2n_hash_fwd_raytile: 0 chosen per tile, 1 across rays at one
@@ -134,6 +137,32 @@ int f2n_hash_fwd_raytile(
   const float * pts, const uint16_t * table_f16, const int32_t * primes, const float * bias,
   const float * mul, float * out_cm, int n_rays, int S, int L, int F, uint32_t T,
   int64_t level_stride, void * stream);
+
+/* f2n_hash_fwd_raytile with the schedule of its levels spelled out (Hash3DAnchoredForwardKernel,
+ * src/hash_3d_anchored.cu:60-93, evaluates one level per block; so does F2N_OPT_RAYTILE = 16 | 32).
+ * One workgroup takes a tile of 64 rays x 32 samples (16 unless S is a multiple of 32) through a
+ * GROUP of consecutive levels: the tile's points, its walk and its depth order are set up once per
+ * group.
+ * Bit l of group_starts set: level l opens a group; bit 0 is implied.  Same arguments, same results
+ * bit for bit under every mask.  A bit at or above L: F2N_E_INVALID_ARG; L > 32: F2N_E_UNSUPPORTED;
+ * both, and every check of f2n_hash_fwd_raytile, before any HIP work. */
+int f2n_hash_fwd_raytile_groups(
+  const float * pts, const uint16_t * table_f16, const int32_t * primes, const float * bias,
+  const float * mul, float * out_cm, int n_rays, int S, int L, int F, uint32_t T,
+  int64_t level_stride, uint32_t group_starts, void * stream);
+
+/* The group_starts that f2n_hash_fwd_raytile uses under F2N_OPT_RAYTILE = 0 for L levels and a grid
+ * of `tiles` tiles (ceil(n_rays / 64) * S / 32, or S / 16 unless S is a multiple of 32).  No
+ * counterpart in the reference, whose Hash3DAnchoredForwardKernel (src/hash_3d_anchored.cu:60-93)
+ * has one level per block and nothing to schedule; exported so that a caller, a measurement or a
+ * test can name the default without a GPU.  From a level's position l / (L - 1):
+ *   tiles >= 1024  the levels below 2/3 form one group, the levels from 2/3 on go two to a group,
+ *                  counted from the first of them (L = 16: 0-9, 10-11, 12-13, 14-15 = 0x5401);
+ *   tiles < 1024   the levels below 2/5 form one group, those from 2/5 to below 2/3 a second, every
+ *                  level from 2/3 on its own (L = 16: 0-5, 6-9, 10, 11, ... 15 = 0xfc41).
+ * L = 1: 1; L = 2: 3.  Host arithmetic, no HIP work.  Returns the mask, a value in [1, 2^32), or a
+ * negative status: F2N_E_INVALID_ARG for L < 1 or tiles < 0, F2N_E_UNSUPPORTED for L > 32. */
+int64_t f2n_hash_raytile_default_groups(int L, int64_t tiles);
 
 /* Hash3DAnchoredBackwardKernel<__half> + the /grad_scale epilogue
  * -- src/hash_3d_anchored.cu:95-145,190-215.

@@ -11,6 +11,12 @@ at a time (L = 1 with that level's mul), with the corner loads in corner order (
 in vertex-parity order (= 0), the two arms alternating call by call; one JSON line per level, to be
 set beside the line counts of tools/gather_lines_model.py.
 
+--level-groups: f2n_hash_fwd_raytile_groups on the same chunk with all 16 levels (the reference's
+overlapping stride), under each schedule of --groups and on the one-level-per-workgroup route
+(RAYTILE = 32), the arms alternating call by call, nine calls each; one JSON line per arm.
+--rays N takes the chunk's first N rays (fewer tiles), --random-rays the reference's own batch of 512
+random rays x 1024 samples.
+
 Reports ms and algorithmic GB/s (SURVEY.md 8d bytes) per variant; used to choose layouts/kernels.
 """
 import argparse
@@ -22,6 +28,16 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+ALONE = ",".join(str(l) for l in range(16))
+# every level alone | one group | the default | fine levels alone, boundary moved | fine levels in
+# pairs, boundaries moved | fine levels in threes | all fine levels together
+DEFAULT_GROUPS = ";".join([
+    ALONE, "0", "default", "0-5,6-9,10,11,12,13,14,15", "0-9,10,11,12,13,14,15", "0-11,12,13,14,15",
+    "0-9,10-11,12-13,14,15", "0-10,11-12,13-14,15", "0-11,12-13,14-15", "0-7,8-9,10-11,12-13,14-15",
+    "0-5,6-9,10-11,12-13,14-15", "0-9,10-12,13-15", "0-9,10-15",
+])
 
 
 def timeit(fn, reps):
@@ -53,16 +69,13 @@ def alternating(fns, reps, warmup=2):
     return ms
 
 
-def corner_order_arm(args, capi, dev):
-    import json
-
+def headline_chunk_points(capi, dev, g, n_rays, S):
+    """the contracted points of one chunk of the benchmark's headline: n_rays rays of an 800 x 800 view
+    in the Renderer's pixel-compact bundles, S jittered samples"""
     sys.path.insert(0, ROOT)
     from bench import fox_like_poses
 
     H = importlib.import_module("f2-nerf_amd").load_host()
-    n_rays, S, F, log2_T, Lfull = 65536, 128, 2, 19, 16
-    T = 1 << log2_T
-    g = torch.Generator(device=dev).manual_seed(0)
     intr = torch.tensor([[1111.1, 0, 400.0], [0, 1111.1, 400.0], [0, 0, 1.0]], device=dev)
     o, d = H.get_view_rays(fox_like_poses(50)[7].to(dev), intr, 800, 800)
     lo = 4 * n_rays                                           # the view's fifth chunk: image rows 327-409
@@ -75,6 +88,84 @@ def corner_order_arm(args, capi, dev):
     bounds = torch.empty(n_rays, 2, device=dev, dtype=torch.int32)
     dirs = torch.empty(n_rays, 3, device=dev)
     capi.call("sample_dense", o, d, u, None, 1, pts, dt, t, bounds, dirs, n_rays, S, 4.0 / S)
+    return pts
+
+
+def parse_groups(text):
+    """'0-5,6-9,10,11' -> mask with bits 0, 6, 10, 11; 'default' / a number pass through"""
+    if text == "default":
+        return None
+    if text.startswith("0x"):
+        return int(text, 16)
+    mask = 0
+    for part in text.split(","):
+        mask |= 1 << int(part.split("-")[0])
+    return mask
+
+
+def level_groups_arm(args, capi, dev):
+    """f2n_hash_fwd_raytile_groups on one headline chunk at L = 16 under each schedule of --groups
+    (separated by ';'), and the one-level-per-workgroup route (RAYTILE = 32), alternating call by call"""
+    import json
+
+    n_rays, S, F, log2_T, L = 65536, 128, 2, 19, 16
+    T = 1 << log2_T
+    g = torch.Generator(device=dev).manual_seed(0)
+    if args.random_rays:                                      # BASELINE config C4's batch: tiles walk along
+        n_rays, S = args.rays or 512, 1024
+        o = torch.randn(n_rays, 1, 3, device=dev, generator=g) * 0.3
+        d = torch.randn(n_rays, 1, 3, device=dev, generator=g)
+        t = (torch.arange(1, S + 1, device=dev).float() * (4.0 / S)).reshape(1, S, 1)
+        p = (o + d / d.norm(dim=-1, keepdim=True) * t).reshape(-1, 3)
+        nrm = p.norm(dim=1, keepdim=True)
+        pts = torch.where(nrm <= 1, p, (2 - 1 / nrm) * p / nrm).contiguous()
+    else:
+        pts = headline_chunk_points(capi, dev, g, n_rays, S)
+        if args.rays:                                         # the chunk's first rays: fewer tiles
+            n_rays = args.rays
+            pts = pts[:n_rays * S].contiguous()
+    n = n_rays * S
+    numel = T * (L - 1) + T * F                               # the reference's stride: T elements
+    table = torch.randn(numel, device=dev, generator=g) * 0.1
+    table16 = torch.empty(numel, dtype=torch.int16, device=dev)
+    capi.call("table_to_f16", table, table16, numel)
+    primes = (torch.randint(1 << 28, 1 << 30, (L, 3), device=dev, generator=g).to(torch.int32) | 1)
+    bias = torch.rand(L, 3, device=dev, generator=g) * 1000 + 100
+    mul = torch.tensor([2.0 ** (7.0 * l / (L - 1) + 3.0) for l in range(L)], device=dev)
+    out = torch.empty(L * F, n, device=dev)
+    default = int(capi.lib().cdll.f2n_hash_raytile_default_groups(L, (n_rays + 63) // 64 * (S // 32)))
+
+    def one_level_route():
+        with capi.option("RAYTILE", 32):
+            capi.call("hash_fwd_raytile", pts, table16, primes, bias, mul, out, n_rays, S, L, F, T, T)
+
+    def groups_route(mask):
+        return lambda: capi.call("hash_fwd_raytile_groups", pts, table16, primes, bias, mul, out, n_rays, S,
+                                 L, F, T, T, mask)
+
+    fns = {"one level per workgroup (RAYTILE=32)": one_level_route}
+    masks = {}
+    for text in args.groups.split(";"):
+        mask = parse_groups(text.strip())
+        name = "groups " + text.strip()
+        masks[name] = default if mask is None else (mask | 1)
+        fns[name] = groups_route(masks[name])
+    ms = alternating(fns, args.reps)
+    for name, v in ms.items():
+        print(json.dumps(dict(
+            what="hash_fwd_raytile, 16 levels", arm=name, group_starts=hex(masks[name]) if name in masks else None,
+            rays=n_rays, samples=S, ms_median=round(sorted(v)[len(v) // 2], 4), ms_min=round(min(v), 4),
+            ms_all=[round(x, 4) for x in v])), flush=True)
+
+
+def corner_order_arm(args, capi, dev):
+    import json
+
+    n_rays, S, F, log2_T, Lfull = 65536, 128, 2, 19, 16
+    T = 1 << log2_T
+    g = torch.Generator(device=dev).manual_seed(0)
+    pts = headline_chunk_points(capi, dev, g, n_rays, S)
+    n = n_rays * S
     table = torch.randn(T * F, device=dev, generator=g) * 0.1
     table16 = torch.empty(T * F, dtype=torch.int16, device=dev)
     capi.call("table_to_f16", table, table16, T * F)
@@ -106,7 +197,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c2")
     ap.add_argument("--n", type=int, default=0)
-    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=None, help="timed calls per arm (5; --level-groups: 9)")
     ap.add_argument("--points", default="rays", choices=["rays", "ball", "view", "view_sm", "view_jit"],
                     help="rays: random rays, samples of a ray consecutive; view: 65536 consecutive pixels of "
                          "an 800-wide pinhole view (focal 1111, camera at distance 1), ray-major as the "
@@ -115,9 +206,21 @@ def main():
     ap.add_argument("--corner-order", action="store_true",
                     help="only the per-level arm of the two corner orders on one headline chunk")
     ap.add_argument("--levels", default="0,4,8,10,12,14,15")
+    ap.add_argument("--level-groups", action="store_true",
+                    help="only the level schedules of f2n_hash_fwd_raytile_groups on one headline chunk")
+    ap.add_argument("--groups", default=DEFAULT_GROUPS,
+                    help="schedules separated by ';': the first level of each group, e.g. '0-5,6-9,10,11,12,13,14,15'")
+    ap.add_argument("--rays", type=int, default=0,
+                    help="--level-groups: only the first RAYS rays of the chunk (64 rays x 32 samples to a tile)")
+    ap.add_argument("--random-rays", action="store_true",
+                    help="--level-groups: --rays (512) random rays x 1024 samples of 1/256 instead of the chunk")
     args = ap.parse_args()
     capi = importlib.import_module("f2-nerf_amd").capi
     dev = torch.device("cuda:0")
+    if args.level_groups:
+        args.reps = args.reps or 9
+        return level_groups_arm(args, capi, dev)
+    args.reps = args.reps or 5
     if args.corner_order:
         return corner_order_arm(args, capi, dev)
     cfg = {"c2": (16, 2, 19, None, 65536 * 128), "c1": (4, 2, 19, None, 65536 * 64),
