@@ -571,6 +571,14 @@ def density_scan_ref(case, thresh=SCAN_THRESH):
     x = logit - DENSITY_SHIFT
     sec = (np.exp(x) * case["dt"].double().numpy()).reshape(R, S)
     e_rel = ((C + 1) * A + np.abs(x) + 4.0).reshape(R, S)
+    return keep_rule(sec, e_rel, thresh)
+
+
+def keep_rule(sec, e_rel, thresh=SCAN_THRESH):
+    """The keep decision of density_scan_ref on sec [R, S] (float64; 0 where a sample contributes
+    nothing) with the relative error e_rel [R, S] of each sec, in units of u -> kept [R], in_band [R].
+    tests/render_model.py applies it to the one-pass render's chain."""
+    S = sec.shape[1]
     depth = np.cumsum(sec, 1) - sec
     limit = -math.log(float(np.float32(thresh)))
     keep = np.exp(-depth) > float(np.float32(thresh))

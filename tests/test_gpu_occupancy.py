@@ -12,6 +12,7 @@ import torch
 from oracle import kernels as K
 from oracle import ref_render as R
 from tests.test_gpu_render import _close, _copy_params, _oracle_grads, _setup
+from tests.util import _cells, _pack, _raw_field  # noqa: F401 (other test modules import them from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -22,20 +23,6 @@ def host():
 
 
 # ---- helpers -------------------------------------------------------------------------------------
-
-def _pack(bits_bool):
-    """bool [G^3] (index i = (cz*G + cy)*G + cx) -> int32 words, bit (i & 31) of word (i >> 5)."""
-    b = np.ascontiguousarray(bits_bool.reshape(-1).cpu().numpy().astype(np.uint8))
-    return torch.from_numpy(np.packbits(b, bitorder="little").view(np.int32).copy())
-
-
-def _cells(x, G):
-    """The header's cell expression in numpy f32: x [n,3] contracted -> linear bit index [n]."""
-    x = x.astype(np.float32)
-    c = np.floor((x + np.float32(2.0)) * (np.float32(0.25) * np.float32(G)))
-    c = np.clip(c, 0, G - 1).astype(np.int64)
-    return (c[:, 2] * G + c[:, 1]) * G + c[:, 0]
-
 
 def _expected_mask(x, bits_bool, G):
     """x: contracted points (numpy [n,3]); non-finite coordinates read as occupied."""
@@ -54,26 +41,6 @@ def _lookup(capi, pts, words, G):
     out = torch.empty(pts.shape[0], dtype=torch.uint8, device=pts.device)
     capi.call("occ_lookup", pts, pts.shape[0], words, G, out)
     return out
-
-
-def _raw_field(L, F, T, bias0, seed, dev):
-    """A hash grid + density head as device tensors for the C ABI ("trained-like" table)."""
-    g = torch.Generator().manual_seed(seed)
-    numel = T * L * F
-    table = torch.randn(numel, generator=g) * 0.1
-    primes = []
-    while len(primes) < 3 * L:
-        v = int(torch.randint(1 << 28, 1 << 30, (1,), generator=g))
-        if R._is_prime(v):
-            primes.append(v)
-    C = L * F
-    w0 = (torch.rand(C, generator=g) * 2 - 1) / math.sqrt(C)
-    return dict(L=L, F=F, T=T, stride=T,
-                table16=K.cast_f16(table).to(dev),
-                primes=torch.tensor(primes, dtype=torch.int32).reshape(L, 3).to(dev),
-                bias=(torch.rand(L, 3, generator=g) * 1000.0 + 100.0).to(dev),
-                mul=K.level_mul(L).to(dev), w0=w0.to(dev),
-                b0=torch.tensor([bias0], dtype=torch.float32).to(dev))
 
 
 def _rays(n_rays, S, seed, dev, train):

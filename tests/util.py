@@ -1,4 +1,7 @@
 """Shared input builders for the parity tests (seeded; same tensors go to the oracle and the GPU)."""
+import math
+
+import numpy as np
 import torch
 
 from oracle import kernels as K
@@ -184,3 +187,40 @@ def old_table_grad_criterion(got, ref, max_tol=2e-5, norm_tol=1e-5):
     scale = ref.abs().max().item()
     assert (got - ref).abs().max().item() <= max_tol * scale
     assert ((got - ref).norm() / ref.norm()).item() < norm_tol
+
+
+# ---- the occupancy grid and the raw field of the C-ABI tests (tests/test_gpu_occupancy.py, the render
+# tests and tests/render_model.py share them)
+
+def _pack(bits_bool):
+    """bool [G^3] (index i = (cz*G + cy)*G + cx) -> int32 words, bit (i & 31) of word (i >> 5)."""
+    b = np.ascontiguousarray(bits_bool.reshape(-1).cpu().numpy().astype(np.uint8))
+    return torch.from_numpy(np.packbits(b, bitorder="little").view(np.int32).copy())
+
+
+def _cells(x, G):
+    """The header's cell expression in numpy f32: x [n,3] contracted -> linear bit index [n]."""
+    x = x.astype(np.float32)
+    c = np.floor((x + np.float32(2.0)) * (np.float32(0.25) * np.float32(G)))
+    c = np.clip(c, 0, G - 1).astype(np.int64)
+    return (c[:, 2] * G + c[:, 1]) * G + c[:, 0]
+
+
+def _raw_field(L, F, T, bias0, seed, dev):
+    """A hash grid + density head as device tensors for the C ABI ("trained-like" table)."""
+    g = torch.Generator().manual_seed(seed)
+    numel = T * L * F
+    table = torch.randn(numel, generator=g) * 0.1
+    primes = []
+    while len(primes) < 3 * L:
+        v = int(torch.randint(1 << 28, 1 << 30, (1,), generator=g))
+        if is_prime(v):
+            primes.append(v)
+    C = L * F
+    w0 = (torch.rand(C, generator=g) * 2 - 1) / math.sqrt(C)
+    return dict(L=L, F=F, T=T, stride=T,
+                table16=K.cast_f16(table).to(dev),
+                primes=torch.tensor(primes, dtype=torch.int32).reshape(L, 3).to(dev),
+                bias=(torch.rand(L, 3, generator=g) * 1000.0 + 100.0).to(dev),
+                mul=K.level_mul(L).to(dev), w0=w0.to(dev),
+                b0=torch.tensor([bias0], dtype=torch.float32).to(dev))
