@@ -193,6 +193,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
       py::arg("level_stride") = 0, py::arg("device") = "")
     .def("query", &Hash3DAnchored::query)
     .def("table_f16", &Hash3DAnchored::table_f16)
+    .def("density_grad", &Hash3DAnchored::density_grad, py::call_guard<py::gil_scoped_release>(),
+         py::arg("points"),
+         "d(density logit)/d(position) [n,3] at raw points: the interpolant's true gradient, detached")
+    .def("density_head", &Hash3DAnchored::density_head, "(row 0 of the field head [L*F], its bias [1])")
     .def("named_parameters", [](Hash3DAnchored & s) { return named_params(s); })
     .def(
       "encode",
@@ -277,6 +281,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
       "DEFAULT_DECAY", [](py::object) { return OccupancyGrid::kDefaultDecay; });
 
   // ---- Renderer ----------------------------------------------------------------------------------
+  py::class_<RenderResult>(m, "RenderResult")
+    .def_readonly("colors", &RenderResult::colors)
+    .def_readonly("depths", &RenderResult::depths)
+    .def_property_readonly("weights", [](const RenderResult & r) { return tensor_or_none(r.weights); })
+    .def_readonly("idx_start_end", &RenderResult::idx_start_end)
+    .def_property_readonly(
+      "normals", [](const RenderResult & r) { return tensor_or_none(r.normals); },
+      "[n_rays, 3] sum of w n^ over the kept samples, or None when RendererOptions::normals is off");
   py::class_<Renderer, std::shared_ptr<Renderer>>(m, "Renderer")
     .def(
       py::init([](int n_images, int64_t L, int64_t F, int64_t log2_T, int64_t stride,
@@ -339,7 +351,36 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
       py::arg("rays_o"), py::arg("rays_d"), py::arg("emb_idx") = py::none(),
       py::arg("mode") = "validate", py::arg("noise") = py::none(), py::arg("bg_color") = py::none(),
       "the no-grad render as one kernel: (colors, depths, last_trans, kept); see Renderer::render_rays")
+    .def(
+      "render_result",
+      [](Renderer & r, const Tensor & o, const Tensor & d, const c10::optional<Tensor> & emb_idx,
+         const std::string & mode, const c10::optional<Tensor> & noise,
+         const c10::optional<Tensor> & bg) {
+        py::gil_scoped_release no_gil;
+        return r.render(o, d, opt_tensor(emb_idx), parse_mode(mode), opt_tensor(noise), opt_tensor(bg));
+      },
+      py::arg("rays_o"), py::arg("rays_d"), py::arg("emb_idx") = py::none(),
+      py::arg("mode") = "validate", py::arg("noise") = py::none(), py::arg("bg_color") = py::none(),
+      "render() handing back the RenderResult itself: colors, depths, weights, idx_start_end and, "
+      "after set_normals(True), normals (None otherwise)")
+    .def("set_normals", &Renderer::set_normals,
+         "RendererOptions::normals: render() also composites the kept samples' surface normals")
+    .def_property_readonly(
+      "normals", [](const Renderer & r) { return r.options_.normals; },
+      "RendererOptions::normals as set_normals left it")
     .def("render_all_rays", &Renderer::render_all_rays, py::call_guard<py::gil_scoped_release>())
+    .def("render_all_rays_with_normals", &Renderer::render_all_rays_with_normals,
+         py::call_guard<py::gil_scoped_release>(), py::arg("rays_o"), py::arg("rays_d"),
+         py::arg("batch_size"), "(colors [n,3], depths [n,1], normals [n,3])")
+    .def(
+      "render_image_with_normals",
+      [](Renderer & r, const Tensor & pose, const Tensor & intr, int h, int w, int batch_size,
+         const c10::optional<Tensor> & dist) {
+        py::gil_scoped_release no_gil;
+        return r.render_image_with_normals(pose, intr, h, w, batch_size, opt_tensor(dist));
+      },
+      py::arg("pose"), py::arg("intrinsic"), py::arg("h"), py::arg("w"), py::arg("batch_size"),
+      py::arg("dist") = py::none(), "(colors [h,w,3], depths [h,w,3], normals [h,w,3])")
     .def(
       "render_image",
       [](Renderer & r, const Tensor & pose, const Tensor & intr, int h, int w, int batch_size,

@@ -179,6 +179,26 @@ std::pair<Tensor, Tensor> Hash3DAnchored::density_head() const
           mlp_->bias.detach().slice(0, 0, 1).contiguous()};
 }
 
+Tensor Hash3DAnchored::density_grad(const Tensor & points_in)
+{
+  torch::NoGradGuard no_grad;
+  const Tensor points = f2n::dev_f32(points_in.detach(), "points");
+  TORCH_CHECK(points.dim() == 2 && points.size(1) == 3, "points must be [n, 3]");
+  const int64_t n = points.size(0);
+  const Tensor table16 = table_f16();
+  const f2n::FieldArgs g = kernel_args(table16);
+  const Tensor w0 = density_head().first;
+  Tensor grad = torch::empty({n, 3}, points.options());
+  void * stream = f2n::current_stream(points);
+  f2n::ScopedKernelTimer timer("density_grad", stream, (double)n);
+  f2n::check(
+    f2n_density_grad(
+      points.data_ptr<float>(), g.table, g.primes, g.bias, g.mul, w0.data_ptr<float>(),
+      grad.data_ptr<float>(), n, g.L, g.F, g.T, g.level_stride, stream),
+    "f2n_density_grad");
+  return grad;
+}
+
 Tensor Hash3DAnchored::encode(const Tensor & points, int64_t samples_per_ray, Tensor * contracted_out)
 {
   auto info = torch::make_intrusive<Hash3DAnchoredInfo>();

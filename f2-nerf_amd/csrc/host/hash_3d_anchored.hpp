@@ -85,6 +85,12 @@ public:
   // ray march evaluates in-kernel.
   std::pair<Tensor, Tensor> density_head() const;
 
+  // d(density logit)/d(position) at the raw points [n, 3] -> [n, 3]: the spatial gradient of the
+  // trilinear interpolant query() evaluates, followed by row 0 of mlp_ and taken through the
+  // contraction (f2n_density_grad).  Not the point gradient autograd returns for query(), which is
+  // the reference's (quirk Q5: no interpolation weights of the other two axes).  No-grad, detached.
+  Tensor density_grad(const Tensor & points);
+
   // f16 working copy of feat_pool_, refreshed if feat_pool_ was modified since the last call.
   Tensor table_f16();
   // f16 copy of an arbitrary table tensor (the shadow when it is feat_pool_ itself).

@@ -293,6 +293,7 @@ RenderResult Renderer::render_routed(
     RenderResult none{
       bg_color, torch::zeros({n_rays}, fopt), torch::full({n_rays}, 512.f, fopt), Tensor()};
     if (want_dist) none.weight_dist = torch::zeros({n_rays}, fopt);
+    if (options_.normals) none.normals = torch::zeros({n_rays, 3}, fopt);
     return none;
   }
   Route route = choose_route(rays_o, rays_d, bg_color);
@@ -345,6 +346,8 @@ Renderer::Route Renderer::choose_route(
   route.lean = route.first_pass == Route::Dense && f2n_get_option(F2N_OPT_DENSE_LEAN) == 0 &&
                !rays_need_grad && !(torch::GradMode::is_enabled() && bg_color.requires_grad()) &&
                f2n::shade_rays_applies(n_rays * S, n_rays, S);
+  // normals need the kept samples' world positions, which neither of the two carries
+  if (options_.normals) route.bucketed = route.lean = false;
   return route;
 }
 
@@ -409,6 +412,7 @@ RenderResult Renderer::render_op_by_op(
   Tensor depths = FlexOps::Sum(weights * sampled_t, idx) / (1.f - last_trans + 1e-4f);
   RenderResult res{colors, depths, weights, idx};
   if (route.want_dist) res.weight_dist = CustomOps::WeightDist(weights, kept.t, kept.dt, idx);
+  if (options_.normals) res.normals = ray_normals(kept, weights);
   return res;
 }
 
@@ -597,6 +601,7 @@ RenderResult Renderer::render_dense(
     if (auto guess = shade_all_unless_near_threshold(
           all, emb_idx, mode, bg_color, route, enc_all_cm, contracted_all)) {
       record_kept(n_all, n_all);
+      if (options_.normals) guess->normals = ray_normals(all, guess->weights);
       return *guess;
     }
   }
@@ -607,10 +612,14 @@ RenderResult Renderer::render_dense(
   RenderResult guess;
   const bool guessed = may_guess && !large;
   if (guessed)  // enqueued BEFORE the host waits for the count: the GPU does not idle across the read
-    guess = shade_and_composite(all, emb_idx, mode, bg_color, route, enc_all_cm, contracted_all);
+    guess = shade_and_composite(
+      all, emb_idx, mode, bg_color, route, enc_all_cm, contracted_all, /*final=*/false);
   const int64_t n_kept = survivors_.wait();
   record_kept(n_kept, n_all);
-  if (guessed && n_kept == n_all) return guess;
+  if (guessed && n_kept == n_all) {
+    if (options_.normals) guess.normals = ray_normals(all, guess.weights);
+    return guess;
+  }
   guess = RenderResult();  // a wrong guess is released before the compaction allocates
   if (n_kept == n_all) {
     // nothing terminated: the uncompacted arrays ARE the compacted ones, and so are their
@@ -725,7 +734,7 @@ std::optional<RenderResult> Renderer::shade_all_unless_near_threshold(
       near_threshold.data_ptr<int32_t>(), (int)(all.dt.size(0) / S), S, 3.f, limit, stream),
     "f2n_density_margin");
   survivors_.request(near_threshold, stream);
-  RenderResult guess = composite(all, shaded, bg_color, route);
+  RenderResult guess = composite(all, shaded, bg_color, route, /*final=*/false);
   if (survivors_.wait() != 0) return std::nullopt;
   return guess;
 }
@@ -733,9 +742,10 @@ std::optional<RenderResult> Renderer::shade_all_unless_near_threshold(
 // Second pass on the survivors (renderer.cpp:92-118).
 RenderResult Renderer::shade_and_composite(
   const SampleResultFlex & kept, const Tensor & emb_idx, RunningMode mode, const Tensor & bg_color,
-  const Route & route, const Tensor & enc_cm, const Tensor & contracted)
+  const Route & route, const Tensor & enc_cm, const Tensor & contracted, bool final)
 {
-  return composite(kept, shade(kept, emb_idx, mode, route, enc_cm, contracted), bg_color, route);
+  return composite(
+    kept, shade(kept, emb_idx, mode, route, enc_cm, contracted), bg_color, route, final);
 }
 
 Renderer::Shaded Renderer::shade(
@@ -800,7 +810,8 @@ Tensor Renderer::shade_aten(
 }
 
 RenderResult Renderer::composite(
-  const SampleResultFlex & kept, const Shaded & shaded, const Tensor & bg_color, const Route & route)
+  const SampleResultFlex & kept, const Shaded & shaded, const Tensor & bg_color, const Route & route,
+  bool final)
 {
   // (the fused routes' kept.pts_idx_bounds comes from f2n_bounds_from_counts / the sampler: the
   // ranges tile [0, n))
@@ -811,7 +822,35 @@ RenderResult Renderer::composite(
   // occupancy grid or not; t and dt get no gradient)
   if (route.want_dist)
     res.weight_dist = CustomOps::WeightDist(out.weights, kept.t, kept.dt, kept.pts_idx_bounds);
+  if (options_.normals && final) res.normals = ray_normals(kept, out.weights);
   return res;
+}
+
+Tensor Renderer::ray_normals(const SampleResultFlex & kept, const Tensor & weights_in)
+{
+  torch::NoGradGuard no_grad;
+  TORCH_CHECK(kept.pts.defined(), "normals need the kept samples' world positions");
+  const Tensor pts = f2n::dev_f32(kept.pts.detach(), "kept pts");
+  const Tensor weights = f2n::dev_f32(weights_in.detach(), "weights");
+  const Tensor bounds = f2n::dev_i32(kept.pts_idx_bounds, "kept bounds");
+  const int64_t n_rays = bounds.size(0);
+  TORCH_CHECK(weights.numel() == pts.size(0), "weights / kept samples mismatch");
+  // nothing kept (an empty occupancy grid): every segment is empty, and an empty tensor has no pointer
+  if (pts.size(0) == 0) return torch::zeros({n_rays, 3}, pts.options());
+  Hash3DAnchored & field = *scene_field_;
+  const Tensor table16 = field.table_f16();
+  const f2n::FieldArgs g = field.kernel_args(table16);
+  const Tensor w0 = field.density_head().first;
+  Tensor normals = torch::empty({n_rays, 3}, pts.options());
+  void * stream = f2n::current_stream(pts);
+  f2n::ScopedKernelTimer timer("ray_normals", stream, (double)pts.size(0));
+  f2n::check(
+    f2n_ray_normals(
+      pts.data_ptr<float>(), bounds.data_ptr<int32_t>(), weights.data_ptr<float>(), g.table,
+      g.primes, g.bias, g.mul, w0.data_ptr<float>(), normals.data_ptr<float>(), (int)n_rays, g.L,
+      g.F, g.T, g.level_stride, stream),
+    "f2n_ray_normals");
+  return normals;
 }
 
 // ---- one-pass inference render ---------------------------------------------------------------------
@@ -966,6 +1005,20 @@ std::tuple<Tensor, Tensor> Renderer::render_all_rays(
   return {torch::cat(colors, 0), torch::cat(depths, 0)};
 }
 
+namespace
+{
+// The view's pixels in B x B tiles (row-major tiles, row-major inside a tile), int64 [h * w]; undefined
+// when the tiles do not divide the view (row-major traversal).
+Tensor pixel_tile_order(int h, int w, int B, const torch::Device & device)
+{
+  if (!(B > 1 && h % B == 0 && w % B == 0)) return Tensor();
+  return torch::arange((int64_t)h * w, torch::TensorOptions().dtype(torch::kInt64).device(device))
+    .view({h / B, B, w / B, B})
+    .permute({0, 2, 1, 3})
+    .reshape({-1});
+}
+}  // namespace
+
 std::tuple<Tensor, Tensor> Renderer::render_image(
   const Tensor & pose, const Tensor & intrinsic, const int h, const int w, const int batch_size,
   const Tensor & dist)
@@ -976,13 +1029,8 @@ std::tuple<Tensor, Tensor> Renderer::render_image(
   // ways instead of a strip 64 pixels long -- a third fewer distinct table lines per gather at the
   // middle levels (src/renderer.cpp:153-172 walks the image in row-major batches; the image that
   // comes out is the same).
-  const int B = options_.pixel_tiles;
-  Tensor order;
-  if (B > 1 && h % B == 0 && w % B == 0) {
-    order = torch::arange((int64_t)h * w, torch::TensorOptions().dtype(torch::kInt64).device(pose.device()))
-              .view({h / B, B, w / B, B})
-              .permute({0, 2, 1, 3})
-              .reshape({-1});
+  const Tensor order = pixel_tile_order(h, w, options_.pixel_tiles, pose.device());
+  if (order.defined()) {
     rays.origins = rays.origins.index_select(0, order);
     rays.dirs = rays.dirs.index_select(0, order);
   }
@@ -994,6 +1042,58 @@ std::tuple<Tensor, Tensor> Renderer::render_image(
   colors = colors.reshape({h, w, 3}).clip(0.f, 1.f);
   depths = depths.reshape({h, w, 1}).repeat({1, 1, 3});
   return {colors, depths};
+}
+
+std::tuple<Tensor, Tensor, Tensor> Renderer::render_all_rays_with_normals(
+  const Tensor & rays_o, const Tensor & rays_d, const int batch_size)
+{
+  TORCH_CHECK(batch_size > 0, "batch_size must be positive");
+  const int64_t n_rays = rays_d.size(0);
+  // the option is on for the duration of this call only, an exception included
+  struct Restore
+  {
+    bool & flag;
+    bool was;
+    ~Restore() { flag = was; }
+  } restore{options_.normals, options_.normals};
+  options_.normals = true;
+  std::vector<Tensor> colors, depths, normals;
+  for (int64_t lo = 0; lo < n_rays; lo += batch_size) {
+    const int64_t hi = std::min<int64_t>(lo + batch_size, n_rays);
+    RenderResult r = render(
+      rays_o.index({Slc(lo, hi)}).contiguous(), rays_d.index({Slc(lo, hi)}).contiguous(), Tensor(),
+      RunningMode::VALIDATE);
+    colors.push_back(r.colors);
+    depths.push_back(r.depths.reshape({-1, 1}));
+    normals.push_back(r.normals);
+  }
+  if (colors.empty()) {
+    const auto fopt = f2n::float_on(rays_d.device());
+    return {torch::empty({0, 3}, fopt), torch::empty({0, 1}, fopt), torch::empty({0, 3}, fopt)};
+  }
+  return {torch::cat(colors, 0), torch::cat(depths, 0), torch::cat(normals, 0)};
+}
+
+std::tuple<Tensor, Tensor, Tensor> Renderer::render_image_with_normals(
+  const Tensor & pose, const Tensor & intrinsic, const int h, const int w, const int batch_size,
+  const Tensor & dist)
+{
+  Rays rays = get_view_rays(pose, intrinsic, h, w, dist);
+  const Tensor order = pixel_tile_order(h, w, options_.pixel_tiles, pose.device());  // as render_image
+  if (order.defined()) {
+    rays.origins = rays.origins.index_select(0, order);
+    rays.dirs = rays.dirs.index_select(0, order);
+  }
+  auto [colors, depths, normals] = render_all_rays_with_normals(rays.origins, rays.dirs, batch_size);
+  if (order.defined()) {
+    colors = torch::empty_like(colors).index_copy_(0, order, colors);
+    depths = torch::empty_like(depths).index_copy_(0, order, depths);
+    normals = torch::empty_like(normals).index_copy_(0, order, normals);
+  }
+  colors = colors.reshape({h, w, 3}).clip(0.f, 1.f);
+  depths = depths.reshape({h, w, 1}).repeat({1, 1, 3});
+  normals = normals.reshape({h, w, 3});
+  return {colors, depths, normals};
 }
 
 std::vector<torch::optim::OptimizerParamGroup> Renderer::optim_param_groups(float lr)

@@ -73,6 +73,9 @@ struct RenderResult
   // Renderer::render_for_loss with want_dist only: CustomOps::WeightDist of the kept samples'
   // weights, t and dt, [n_rays] in the caller's order, on every route; undefined otherwise
   Tensor weight_dist;
+  // RendererOptions::normals only: N_r = sum_k w_k n^_k over the kept samples (f2n_ray_normals),
+  // [n_rays, 3] in the caller's order, detached, not renormalised; undefined when the option is off
+  Tensor normals;
 };
 
 struct RendererOptions
@@ -131,6 +134,15 @@ struct RendererOptions
   // For scenes whose rays stop after a few samples.  Still no host read, O(n_rays)
   // memory (64 bytes of state per ray of a chunk, cached) and capturable in a hipGraph.
   int one_pass_head = 0;
+  // Surface normals next to colours and depths: render() fills RenderResult::normals with the
+  // weighted sum of the kept samples' unit normals -g/|g|, g the density logit's true spatial
+  // gradient (f2n_ray_normals: one launch after compositing, on the kept samples and the weights the
+  // route holds anyway).  No gradient flows through them.  While it is on, neither the bucketed nor
+  // the lean dense route is taken (they carry no world positions -- the concession fused_ray_grad
+  // makes); every other launch is the one made without it and colours, depths and weights keep their
+  // bits on the route taken.  Ignored by render_rays and the one-pass path, which have no per-sample
+  // weights: use render_all_rays_with_normals / render_image_with_normals.
+  bool normals = false;
 };
 
 class Renderer : public torch::nn::Module
@@ -190,6 +202,16 @@ public:
   // dist: optional (k1, k2, p1, p2) of the view's camera, [4] or [1,4] (get_view_rays); undefined =
   // pinhole, as in the reference
   std::tuple<Tensor, Tensor> render_image(
+    const torch::Tensor & pose, const torch::Tensor & intrinsic, const int h, const int w,
+    const int batch_size, const torch::Tensor & dist = torch::Tensor());
+
+  // render_all_rays / render_image with the per-ray normals as a third output ([n, 3] and [h, w, 3],
+  // not clipped, not renormalised): the same chunk loop and pixel-tile traversal, every chunk through
+  // render() with RendererOptions::normals on -- the default routes, whatever one_pass says.
+  void set_normals(bool on) { options_.normals = on; }
+  std::tuple<Tensor, Tensor, Tensor> render_all_rays_with_normals(
+    const Tensor & rays_o, const Tensor & rays_d, const int batch_size);
+  std::tuple<Tensor, Tensor, Tensor> render_image_with_normals(
     const torch::Tensor & pose, const torch::Tensor & intrinsic, const int h, const int w,
     const int batch_size, const torch::Tensor & dist = torch::Tensor());
 
@@ -294,13 +316,18 @@ private:
   Tensor shade_aten(
     const Tensor & scene_feat, const SampleResultFlex & kept, const Tensor & emb_idx,
     RunningMode mode);
+  // final = false: a guess of render_dense that may be thrown away -- RenderResult::normals is left
+  // to the caller, who launches ray_normals once the guess is accepted
   RenderResult composite(
     const SampleResultFlex & kept, const Shaded & shaded, const Tensor & bg_color,
-    const Route & route);
+    const Route & route, bool final = true);
   RenderResult shade_and_composite(
     const SampleResultFlex & kept, const Tensor & emb_idx, RunningMode mode,
     const Tensor & bg_color, const Route & route, const Tensor & enc_cm = Tensor(),
-    const Tensor & contracted = Tensor());
+    const Tensor & contracted = Tensor(), bool final = true);
+  // RenderResult::normals of the kept samples (raw positions) and their weights: one launch of
+  // f2n_ray_normals, nothing recorded by autograd
+  Tensor ray_normals(const SampleResultFlex & kept, const Tensor & weights);
   // n_all < 0: the kept fraction (what the adaptive first-pass choice reads) keeps its value
   void record_kept(int64_t n_kept, int64_t n_all = -1);
 

@@ -236,6 +236,41 @@ int f2n_hash_rays_grad(
   float * d_rays_d, int n_rays, int L, int F, uint32_t T, int64_t level_stride, float grad_scale,
   void * stream);
 
+/* The density logit's spatial gradient: d(logit)/d(p) of the trilinear interpolant the forward
+ * computes (src/hash_3d_anchored.cu:25-93 behind the contraction of src/hash_3d_anchored.cpp:79-82)
+ * followed by row 0 of the field head,
+ *   logit(p) = b0 + sum_l sum_k w0[l F + k] sum_d w_d(frac_l) f_{l,d,k},
+ * the march's density chain without the per-channel f16 rounding of the blend, differentiated in f32
+ * per level with all three axes' interpolation weights and taken through the contraction's Jacobian
+ * to the raw point.  It is NOT what src/hash_3d_anchored.cu:138-143 computes (quirk Q5: the corner
+ * features signed by the corner bit, without the other two axes' weights), which f2n_hash_bwd's
+ * pts_grad and f2n_hash_rays_grad reproduce.
+ *   pts        [n,3] f32 RAW (uncontracted) positions; |p| == 0 yields NaN for that point only
+ *   table_f16 .. level_stride: as f2n_hash_fwd; L <= F2N_MAX_LEVELS (F2N_E_UNSUPPORTED above)
+ *   w0         [L*F] f32, row 0 of the field head; its bias does not enter
+ *   grad       [n,3] f32, overwritten
+ * One lane per point, no atomics; n == 0 is F2N_OK without a launch. */
+int f2n_density_grad(
+  const float * pts, const uint16_t * table_f16, const int32_t * primes, const float * bias,
+  const float * mul, const float * w0, float * grad, int64_t n, int L, int F, uint32_t T,
+  int64_t level_stride, void * stream);
+
+/* Per-ray normals N_r = sum_k w_k n^_k over the ray's kept samples, n^ = -g/|g| with g the
+ * gradient f2n_density_grad forms (same device function: the interpolant of
+ * src/hash_3d_anchored.cu:25-93 behind src/hash_3d_anchored.cpp:79-82, NOT the Q5 vector of
+ * src/hash_3d_anchored.cu:138-143); n^ = 0 where g is zero in all three components.  Not
+ * renormalised: |N_r| is at most the ray's opacity and the background contributes nothing.
+ *   pts        [n,3] f32 RAW positions of the kept samples, weights [n] their compositing weights
+ *   bounds     [n_rays, 2] segment of each ray in pts / weights
+ *   table_f16 .. level_stride, w0: as f2n_density_grad
+ *   normals    [n_rays, 3] f32, every element written; a ray with an empty segment gets zeros, a
+ *              non-finite sample poisons its own ray only.
+ * One wavefront per ray, one launch, no atomics, the same bits on every run. */
+int f2n_ray_normals(
+  const float * pts, const int32_t * bounds, const float * weights, const uint16_t * table_f16,
+  const int32_t * primes, const float * bias, const float * mul, const float * w0,
+  float * normals, int n_rays, int L, int F, uint32_t T, int64_t level_stride, void * stream);
+
 /* ------------------------------------------------------------------ SH encode (row A6) -------- */
 
 /* SHKernel<<<ceil(n/512), 512>>> -- src/sh_shader.cu:11-115.  dirs [n,3] -> out [n, degree^2],
