@@ -7,6 +7,7 @@
 #include "hash_3d_anchored.hpp"
 #include "kernel_timer.hpp"
 #include "localizer.hpp"
+#include "mesh.hpp"
 #include "occupancy_grid.hpp"
 #include "points_sampler.hpp"
 #include "pose_refiner.hpp"
@@ -474,6 +475,53 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
         return h;
       },
       "FusedAdam over the same groups: one kernel per parameter, emits the table's f16 shadow");
+
+  // ---- mesh extraction ---------------------------------------------------------------------------
+  m.attr("DENSITY_SHIFT") = f2n::kDensityShift;
+  m.def(
+    "density_lattice",
+    [](Hash3DAnchored & field, const std::array<float, 3> & lo, const std::array<float, 3> & step,
+       const std::array<int64_t, 3> & dims) {
+      py::gil_scoped_release no_gil;
+      return f2n::density_lattice(field, lo, step, dims);
+    },
+    py::arg("field"), py::arg("lo"), py::arg("step"), py::arg("dims"),
+    "f2n_density_lattice: the density logit [nz,ny,nx] at lo + i * step, dims = (nx, ny, nz)");
+  m.def(
+    "marching_tets",
+    [](const Tensor & values, float level, const std::array<float, 3> & lo,
+       const std::array<float, 3> & step) {
+      f2n::Mesh mesh;
+      {
+        py::gil_scoped_release no_gil;
+        mesh = f2n::marching_tets(values, level, lo, step);
+      }
+      return py::make_tuple(mesh.vertices, mesh.triangles);
+    },
+    py::arg("values"), py::arg("level"), py::arg("lo"), py::arg("step"),
+    "marching tetrahedra on values [nz,ny,nx] -> (vertices [V,3] f32, triangles [T,3] i32)");
+  m.def(
+    "extract_mesh",
+    [](Renderer & r, const std::array<float, 3> & lo, const std::array<float, 3> & hi,
+       const std::array<int64_t, 3> & dims, float sigma_level, bool with_normals) {
+      f2n::Mesh mesh;
+      {
+        py::gil_scoped_release no_gil;
+        mesh = f2n::extract_mesh(r, lo, hi, dims, sigma_level, with_normals);
+      }
+      return py::make_tuple(mesh.vertices, mesh.triangles, tensor_or_none(mesh.normals));
+    },
+    py::arg("renderer"), py::arg("lo"), py::arg("hi"), py::arg("dims"), py::arg("sigma_level"),
+    py::arg("with_normals") = false,
+    "the surface density == sigma_level inside [lo, hi] -> (vertices, triangles, normals | None)");
+  m.def(
+    "save_ply",
+    [](const std::string & path, const Tensor & vertices, const Tensor & triangles,
+       const c10::optional<Tensor> & normals) {
+      f2n::save_ply(path, vertices, triangles, opt_tensor(normals));
+    },
+    py::arg("path"), py::arg("vertices"), py::arg("triangles"), py::arg("normals") = py::none(),
+    "binary little-endian PLY 1.0: x y z [nx ny nz], faces as uchar 3 + three int32");
 
   // ---- scene files: cams_meta.tsv, scene normalisation, inference_params.yaml
   m.def("read_cams_meta", [](const std::string & path) {

@@ -271,6 +271,65 @@ int f2n_ray_normals(
   const int32_t * primes, const float * bias, const float * mul, const float * w0,
   float * normals, int n_rays, int L, int F, uint32_t T, int64_t level_stride, void * stream);
 
+/* The density logit on the vertices of an axis-aligned lattice in RAW world space, no point array in
+ * and no encoding out: the evaluation the early-stop pass applies to its samples
+ * (src/renderer.cpp:61-62 through the contraction of src/hash_3d_anchored.cpp:79-82), which the
+ * reference itself never runs off a ray.  Vertex (ix, iy, iz) sits at p = fmaf((float)i, step, lo) per
+ * axis; its value is f2n_density_march's logit bit for bit: the contraction of f2n_contract_fwd, the
+ * gather and per-channel f16 rounding of f2n_hash_fwd, logit = fmaf(enc_c, w0[c], logit) in level
+ * order from b0.  density_shift is NOT subtracted (a caller folds it into its level).
+ *   table_f16 .. level_stride: as f2n_hash_fwd; L <= F2N_MAX_LEVELS (F2N_E_UNSUPPORTED above)
+ *   w0 [L*F], b0 [1]: as f2n_density_march
+ *   lo, step   f32 per axis, every step > 0
+ *   nx, ny, nz each >= 2, nx*ny*nz < 2^31
+ *   logit      [nz, ny, nx] f32, x fastest, every element written; a vertex at |p| == 0 yields NaN
+ *              (quirk Q6) for itself only.
+ * One lane per vertex, a wavefront is a 4x4x4 brick of vertices; one launch per group of consecutive
+ * levels whose part of the table fits half an L2 (one launch for a small table), each continuing the
+ * chain from the logit the one before it stored: the same chain and the same bits however the levels
+ * are grouped.  No atomics. */
+int f2n_density_lattice(
+  const uint16_t * table_f16, const int32_t * primes, const float * bias, const float * mul,
+  const float * w0, const float * b0, float * logit, float lo_x, float lo_y, float lo_z,
+  float step_x, float step_y, float step_z, int nx, int ny, int nz, int L, int F, uint32_t T,
+  int64_t level_stride, void * stream);
+
+/* ------------------------------------------------------------------ mesh extraction ----------- */
+
+/* Marching tetrahedra on a scalar lattice.  The reference has no mesher: its geometry is per ray
+ * (src/renderer.cpp:58-90); these two entries are independent of the field and are applied to
+ * f2n_density_lattice's logits of the density of src/hash_3d_anchored.cpp:79-86.
+ *   values     [nz, ny, nx] f32, x fastest; vertex (x, y, z) has lattice index (z ny + y) nx + x and
+ *              is inside iff value > level (NaN is outside); nx, ny, nz >= 2, nx*ny*nz < 2^31
+ * Every cell is six Kuhn tetrahedra around its body diagonal, so every tetrahedron edge runs from a
+ * vertex a to a + d, d = dx + 2 dy + 4 dz in 1..7, and a owns it.  An owned edge whose ends differ
+ * carries one mesh vertex.  The orders (vertices by (owner, d), triangles by (cell, tetrahedron,
+ * triangle)), the tetrahedra, the triangles of each case and their winding -- (b - a) x (c - a)
+ * points from the inside corners to the outside ones -- are stated in mesh.hip's header comment.
+ * f2n_mesh_count writes, per lattice vertex,
+ *   mask   [n] u8  bit d - 1: the owned edge d crosses
+ *   vcount [n] u8  popcount(mask), tcount [n] u8  triangles of the cell at this vertex (at most 12). */
+int f2n_mesh_count(
+  const float * values, uint8_t * mask, uint8_t * vcount, uint8_t * tcount, int nx, int ny, int nz,
+  float level, void * stream);
+
+/* f2n_mesh_emit writes the mesh, given f2n_mesh_count's mask of the same values and level (no
+ * reference counterpart either; the field is that of src/hash_3d_anchored.cpp:79-86):
+ *   voff, toff [n] i64  EXCLUSIVE prefix sums of vcount and tcount
+ *   n_vertices, n_triangles  their totals; at or above 2^31 (3 n_triangles for the latter):
+ *              F2N_E_UNSUPPORTED; both 0: F2N_OK without a launch; one of them 0: F2N_E_INVALID_ARG
+ *   vertices   [n_vertices, 3] f32: on the edge a -> b = a + d, t = (level - s_a) / (s_b - s_a),
+ *              t = 0.5 if !(t >= 0 && t <= 1), p = fmaf(t, p_b - p_a, p_a) per axis with
+ *              p = fmaf((float)i, step, lo)
+ *   triangles  [n_triangles, 3] i32 indices into vertices
+ * Every store is checked against the totals: inputs that do not belong together skip stores and never
+ * write outside the two arrays.  No atomics, the same bits on every run. */
+int f2n_mesh_emit(
+  const float * values, const uint8_t * mask, const int64_t * voff, const int64_t * toff,
+  float * vertices, int32_t * triangles, int64_t n_vertices, int64_t n_triangles, float lo_x,
+  float lo_y, float lo_z, float step_x, float step_y, float step_z, float level, int nx, int ny,
+  int nz, void * stream);
+
 /* ------------------------------------------------------------------ SH encode (row A6) -------- */
 
 /* SHKernel<<<ceil(n/512), 512>>> -- src/sh_shader.cu:11-115.  dirs [n,3] -> out [n, degree^2],
