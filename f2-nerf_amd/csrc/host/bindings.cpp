@@ -3,6 +3,7 @@
 // call the C ABI of libf2nerf_hip.so.
 #include <torch/extension.h>
 
+#include "depth_targets.hpp"
 #include "fused_adam.hpp"
 #include "hash_3d_anchored.hpp"
 #include "kernel_timer.hpp"
@@ -96,6 +97,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
   m.def("flex_accumulate_sum", &FlexOps::AccumulateSum, "FlexOps::AccumulateSum");
   m.def("weight_var", &CustomOps::WeightVar, "CustomOps::WeightVar");
   m.def("weight_dist", &CustomOps::WeightDist, "CustomOps::WeightDist(weights, t, dt, idx_start_end)");
+  m.def(
+    "depth_sight", &CustomOps::DepthSight, py::arg("weights"), py::arg("t"), py::arg("dt"),
+    py::arg("idx_start_end"), py::arg("z"), py::arg("eps"),
+    "CustomOps::DepthSight -> [n_rays, 3] (empty space, near surface, expected depth)");
+  m.def(
+    "splat_depth",
+    [](const Tensor & points, const Tensor & cam_idx, const Tensor & poses, const Tensor & intr,
+       const c10::optional<Tensor> & dist, int h, int w) {
+      return f2n::splat_depth(points, cam_idx, poses, intr, opt_tensor(dist), h, w);
+    },
+    py::arg("points"), py::arg("cam_idx"), py::arg("poses"), py::arg("intrinsics"),
+    py::arg("dist") = py::none(), py::arg("h"), py::arg("w"),
+    "f2n_depth_splat -> depth [E,h,w]: per pixel the smallest ray distance |p - t_cam|, 0 = no return");
+  m.def(
+    "gather_depth", &f2n::gather_depth, py::arg("depth_maps"), py::arg("cam_idx"), py::arg("ij"),
+    "depth_maps[cam_idx, ij[:,0], ij[:,1]] -> [n]: a batch's depth targets");
   m.def("scatter_add", &CustomOps::ScatterAdd, "CustomOps::ScatterAdd(emb, idx, to_add)");
   m.def("scatter_idx", &CustomOps::ScatterIdx, "CustomOps::ScatterIdx(n_all, idx_start_end, emb_idx)");
   m.def("trunc_exp", [](const Tensor & x) { return torch::autograd::TruncExp::apply(x)[0]; });
@@ -288,8 +305,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def_property_readonly("weights", [](const RenderResult & r) { return tensor_or_none(r.weights); })
     .def_readonly("idx_start_end", &RenderResult::idx_start_end)
     .def_property_readonly(
+      "weight_var", [](const RenderResult & r) { return tensor_or_none(r.weight_var); })
+    .def_property_readonly(
+      "weight_dist", [](const RenderResult & r) { return tensor_or_none(r.weight_dist); })
+    .def_property_readonly(
+      "depth_terms", [](const RenderResult & r) { return tensor_or_none(r.depth_terms); },
+      "[n_rays, 3] line-of-sight depth terms, or None unless render_for_loss got a depth_target")
+    .def_property_readonly(
       "normals", [](const RenderResult & r) { return tensor_or_none(r.normals); },
       "[n_rays, 3] sum of w n^ over the kept samples, or None when RendererOptions::normals is off");
+  py::class_<f2n::DepthLossOptions>(m, "DepthLossOptions")
+    .def(
+      py::init([](float empty, float near, float expected, float eps) {
+        return f2n::DepthLossOptions{empty, near, expected, eps};
+      }),
+      py::arg("empty") = 0.f, py::arg("near") = 0.f, py::arg("expected") = 0.f, py::arg("eps") = 0.f,
+      "weights of the three line-of-sight depth terms and the half-width of the surface band")
+    .def_readwrite("empty", &f2n::DepthLossOptions::empty)
+    .def_readwrite("near", &f2n::DepthLossOptions::near)
+    .def_readwrite("expected", &f2n::DepthLossOptions::expected)
+    .def_readwrite("eps", &f2n::DepthLossOptions::eps);
   py::class_<Renderer, std::shared_ptr<Renderer>>(m, "Renderer")
     .def(
       py::init([](int n_images, int64_t L, int64_t F, int64_t log2_T, int64_t stride,
@@ -324,22 +359,60 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
       "render_for_loss",
       [](Renderer & r, const Tensor & o, const Tensor & d, const c10::optional<Tensor> & emb_idx,
          const std::string & mode, const c10::optional<Tensor> & noise,
-         const c10::optional<Tensor> & bg, bool want_dist) {
+         const c10::optional<Tensor> & bg, bool want_dist,
+         const c10::optional<Tensor> & depth_target, float depth_eps) -> py::tuple {
         RenderResult res;
         {
           py::gil_scoped_release no_gil;
-          res = r.render_for_loss(
-            o, d, opt_tensor(emb_idx), parse_mode(mode), opt_tensor(noise), opt_tensor(bg), want_dist);
+          // (no target: the overload that exists without it, not the new one with an undefined tensor)
+          res = depth_target.has_value()
+                  ? r.render_for_loss(
+                      o, d, opt_tensor(emb_idx), parse_mode(mode), opt_tensor(noise), opt_tensor(bg),
+                      want_dist, *depth_target, depth_eps)
+                  : r.render_for_loss(
+                      o, d, opt_tensor(emb_idx), parse_mode(mode), opt_tensor(noise), opt_tensor(bg),
+                      want_dist);
         }
+        if (depth_target.has_value())
+          return py::make_tuple(
+            res.colors, res.depths, tensor_or_none(res.weights), res.idx_start_end,
+            tensor_or_none(res.weight_var), tensor_or_none(res.weight_dist),
+            tensor_or_none(res.depth_terms));
         return py::make_tuple(
           res.colors, res.depths, tensor_or_none(res.weights), res.idx_start_end,
           tensor_or_none(res.weight_var), tensor_or_none(res.weight_dist));
       },
       py::arg("rays_o"), py::arg("rays_d"), py::arg("emb_idx") = py::none(),
       py::arg("mode") = "train", py::arg("noise") = py::none(), py::arg("bg_color") = py::none(),
-      py::arg("want_dist") = false,
+      py::arg("want_dist") = false, py::arg("depth_target") = py::none(),
+      py::arg("depth_eps") = 0.f,
       "(colors, depths, weights | None, idx_start_end, weight_var | None, weight_dist | None): see "
-      "Renderer::render_for_loss")
+      "Renderer::render_for_loss.  NOTE THE ARITY: the tuple has these six elements unless a "
+      "depth_target [n_rays] is passed; then, and only then, it has a SEVENTH, depth_terms "
+      "[n_rays, 3].  Callers written before depth supervision keep unpacking six; a caller that "
+      "passes a target unpacks seven.  render_for_loss_result returns the RenderResult itself, with "
+      "every field by name (None where undefined), whatever was asked for.")
+    .def(
+      "render_for_loss_result",
+      [](Renderer & r, const Tensor & o, const Tensor & d, const c10::optional<Tensor> & emb_idx,
+         const std::string & mode, const c10::optional<Tensor> & noise,
+         const c10::optional<Tensor> & bg, bool want_dist,
+         const c10::optional<Tensor> & depth_target, float depth_eps) {
+        py::gil_scoped_release no_gil;
+        return depth_target.has_value()
+                 ? r.render_for_loss(
+                     o, d, opt_tensor(emb_idx), parse_mode(mode), opt_tensor(noise), opt_tensor(bg),
+                     want_dist, *depth_target, depth_eps)
+                 : r.render_for_loss(
+                     o, d, opt_tensor(emb_idx), parse_mode(mode), opt_tensor(noise), opt_tensor(bg),
+                     want_dist);
+      },
+      py::arg("rays_o"), py::arg("rays_d"), py::arg("emb_idx") = py::none(),
+      py::arg("mode") = "train", py::arg("noise") = py::none(), py::arg("bg_color") = py::none(),
+      py::arg("want_dist") = false, py::arg("depth_target") = py::none(),
+      py::arg("depth_eps") = 0.f,
+      "render_for_loss handing back the RenderResult: colors, depths, weights, idx_start_end, "
+      "weight_var, weight_dist, depth_terms, normals by name (None where undefined)")
     .def(
       "render_rays",
       [](Renderer & r, const Tensor & o, const Tensor & d, const c10::optional<Tensor> & emb_idx,
@@ -395,23 +468,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
       "train_step",
       [](Renderer & r, const Tensor & o, const Tensor & d, const Tensor & emb_idx, const Tensor & gt,
          float var_loss_weight, const c10::optional<Tensor> & noise,
-         const c10::optional<Tensor> & bg, bool backward, float dist_loss_weight) {
+         const c10::optional<Tensor> & bg, bool backward, float dist_loss_weight,
+         const c10::optional<Tensor> & depth_target, const f2n::DepthLossOptions & depth_loss) {
         f2n::TrainStepResult out;
         {
           // loss.backward() runs the autograd engine, which must not be entered holding the GIL
           py::gil_scoped_release no_gil;
           out = f2n::train_step(
             r, o, d, emb_idx, gt, var_loss_weight, dist_loss_weight, opt_tensor(noise),
-            opt_tensor(bg), backward);
+            opt_tensor(bg), backward, opt_tensor(depth_target), depth_loss);
         }
         return py::make_tuple(out.loss, out.sq_err_sum, out.n_values, out.n_samples);
       },
       py::arg("rays_o"), py::arg("rays_d"), py::arg("emb_idx"), py::arg("gt_colors"),
       py::arg("var_loss_weight") = 0.f, py::arg("noise") = py::none(),
       py::arg("bg_color") = py::none(), py::arg("backward") = true,
-      py::arg("dist_loss_weight") = 0.f,
+      py::arg("dist_loss_weight") = 0.f, py::arg("depth_target") = py::none(),
+      py::arg("depth_loss") = f2n::DepthLossOptions(),
       "reference train_manager.cpp:76-107 without the optimiser step; dist_loss_weight > 0 adds the "
-      "distortion loss (its mean: last_dist_loss)")
+      "distortion loss (its mean: last_dist_loss); depth_target [n_rays] with a DepthLossOptions "
+      "that has a non-zero weight adds the line-of-sight depth terms (their means: last_depth_loss)")
     .def("named_parameters", [](Renderer & r) { return named_params(r); })
     .def("zero_grad", [](Renderer & r) { r.zero_grad(); })
     .def(
@@ -451,6 +527,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def_property_readonly(
       "last_dist_loss", [](const Renderer & r) { return tensor_or_none(r.last_dist_loss_); },
       "mean weight_dist of the last train_step with dist_loss_weight != 0 (device scalar) or None")
+    .def_property_readonly(
+      "last_depth_loss", [](const Renderer & r) { return tensor_or_none(r.last_depth_loss_); },
+      "[3] means over the valid rays of the depth terms of the last train_step that had them, or None")
     .def_readonly("last_kept_fraction", &Renderer::last_kept_fraction_)
     .def_readonly("last_n_samples", &Renderer::last_n_samples_)
     .def_property_readonly("scene_field", [](Renderer & r) { return r.scene_field_; })

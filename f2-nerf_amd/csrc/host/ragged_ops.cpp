@@ -180,6 +180,56 @@ public:
   }
 };
 
+// The line-of-sight depth losses per ray (f2n_depth_sight_fwd / _bwd), beside WeightDist and with its
+// conventions: differentiable in the weights only; the backward recomputes from the saved inputs.
+class DepthSightFn : public torch::autograd::Function<DepthSightFn>
+{
+public:
+  static variable_list forward(
+    AutogradContext * ctx, Tensor weights, Tensor t, Tensor dt, Tensor idx, Tensor z, double eps)
+  {
+    weights = f2n::dev_f32(weights, "CustomOps::DepthSight weights");
+    t = f2n::dev_f32(t, "CustomOps::DepthSight t");
+    dt = f2n::dev_f32(dt, "CustomOps::DepthSight dt");
+    idx = f2n::dev_i32(idx, "CustomOps::DepthSight idx_start_end");
+    z = f2n::dev_f32(z.detach(), "CustomOps::DepthSight z");
+    TORCH_CHECK(
+      weights.dim() == 1 && t.numel() == weights.numel() && dt.numel() == weights.numel() &&
+        idx.dim() == 2 && idx.size(1) == 2 && z.numel() == idx.size(0),
+      "CustomOps::DepthSight expects weights, t, dt [n], idx_start_end [n_rays, 2] and z [n_rays]");
+    const int n_rays = (int)idx.size(0);
+    Tensor out = torch::empty({n_rays, 3}, weights.options());
+    f2n::check(
+      f2n_depth_sight_fwd(
+        f2n::fptr(weights), f2n::fptr(t), f2n::fptr(dt), f2n::iptr(idx), f2n::fptr(z), (float)eps,
+        out.data_ptr<float>(), n_rays, f2n::current_stream(weights)),
+      "f2n_depth_sight_fwd");
+    ctx->save_for_backward({weights, t, dt, idx, z});
+    ctx->saved_data["eps"] = eps;
+    ctx->set_materialize_grads(!f2n::lean_grads());
+    return {out};
+  }
+
+  static variable_list backward(AutogradContext * ctx, variable_list grad_output)
+  {
+    variable_list none(6);
+    if (!grad_output[0].defined()) return none;
+    Tensor d_out = f2n::dev_f32(grad_output[0], "CustomOps::DepthSight grad");
+    auto saved = ctx->get_saved_variables();
+    Tensor &weights = saved[0], &t = saved[1], &dt = saved[2], &idx = saved[3], &z = saved[4];
+    Tensor dw = torch::zeros_like(weights);
+    if (weights.numel() > 0)  // (nothing kept: every range is empty and an empty tensor has no pointer)
+      f2n::check(
+        f2n_depth_sight_bwd(
+          f2n::fptr(weights), f2n::fptr(t), f2n::fptr(dt), f2n::iptr(idx), f2n::fptr(z),
+          (float)ctx->saved_data["eps"].toDouble(), f2n::fptr(d_out), dw.data_ptr<float>(),
+          (int)idx.size(0), f2n::current_stream(d_out)),
+        "f2n_depth_sight_bwd");
+    none[0] = dw;
+    return none;
+  }
+};
+
 class ScatterAddFn : public torch::autograd::Function<ScatterAddFn>
 {
 public:
@@ -558,6 +608,14 @@ Tensor FlexOps::AccumulateSum(Tensor val, Tensor idx_start_end, bool include_thi
 Tensor CustomOps::WeightVar(Tensor weights, Tensor idx_start_end)
 {
   return WeightVarFn::apply(weights.contiguous(), idx_start_end.contiguous())[0];
+}
+
+Tensor CustomOps::DepthSight(
+  Tensor weights, Tensor t, Tensor dt, Tensor idx_start_end, Tensor z, double eps)
+{
+  return DepthSightFn::apply(
+    weights.contiguous(), t.detach().contiguous(), dt.detach().contiguous(),
+    idx_start_end.contiguous(), z.detach().contiguous(), eps)[0];
 }
 
 Tensor CustomOps::WeightDist(Tensor weights, Tensor t, Tensor dt, Tensor idx_start_end)

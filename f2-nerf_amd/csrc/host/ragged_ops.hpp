@@ -2,6 +2,7 @@
 //   FlexOps::Sum / FlexOps::AccumulateSum          (reference src/CustomOps/FlexOps.hpp:14-20)
 //   CustomOps::WeightVar                           (src/CustomOps/CustomOps.hpp:23-28)
 //   CustomOps::WeightDist                          (no counterpart: the distortion loss beside it)
+//   CustomOps::DepthSight                          (no counterpart: the line-of-sight depth losses)
 //   CustomOps::ScatterAdd / CustomOps::ScatterIdx  (src/CustomOps/Scatter.hpp:16-21)
 //   torch::autograd::TruncExp                      (src/CustomOps/CustomOps.hpp:13-19)
 // Same names, argument meaning and autograd behaviour; the kernels behind them are the wave-per-ray
@@ -39,6 +40,15 @@ torch::Tensor WeightVar(torch::Tensor weights, torch::Tensor idx_start_end);
 // which are data on every training route, and receive none.
 torch::Tensor WeightDist(
   torch::Tensor weights, torch::Tensor t, torch::Tensor dt, torch::Tensor idx_start_end);
+// Not in the reference either (it reads no range data; same site, src/main_functions/train_manager.cpp:80-93):
+// the three line-of-sight terms of depth supervision per ray (f2n_depth_sight_fwd / _bwd),
+//   (E_r, N_r, X_r) = (sum_front w^2, (1 - sum_band w)^2, (sum w m - z_r)^2)  ->  [n_rays, 3]
+// with m = t - dt / 2, front: m < z - eps, band: z - eps <= m <= z + eps; z [n_rays] is the ray's
+// target distance in the units of t, a ray whose z is not finite and > 0 gives zeros and no gradient.
+// The gradient goes to `weights` only: t, dt and z receive none.
+torch::Tensor DepthSight(
+  torch::Tensor weights, torch::Tensor t, torch::Tensor dt, torch::Tensor idx_start_end,
+  torch::Tensor z, double eps);
 torch::Tensor ScatterAdd(torch::Tensor emb, torch::Tensor idx, torch::Tensor to_add);
 torch::Tensor ScatterIdx(int n_all_pts, torch::Tensor idx_start_end, torch::Tensor emb_idx);
 }  // namespace CustomOps
@@ -93,7 +103,7 @@ ShadeOut shade_rays(
   const Tensor & app_emb, bool dirs_per_ray = false);
 
 // F2N_OPT_DENSE_LEAN = 0: the autograd nodes between the per-ray results and the network
-// (CompositeFn, WeightVarFn, WeightDistFn, the Renderer's RayUnpermuteFn) take an undefined gradient
+// (CompositeFn, WeightVarFn, WeightDistFn, DepthSightFn, the Renderer's RayUnpermuteFn) take an undefined gradient
 // as undefined -- no zero tensor of n samples is made, gathered and read for it.
 bool lean_grads();
 

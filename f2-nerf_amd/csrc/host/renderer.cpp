@@ -9,6 +9,8 @@
 #include <c10/hip/HIPGuard.h>
 #include <hip/hip_runtime_api.h>
 
+#include <limits>
+
 using Tensor = torch::Tensor;
 
 f2n::HostCount::~HostCount()
@@ -159,6 +161,43 @@ private:
   }
 };
 
+// Per-ray rows [n, C] of the bucketed order back into the caller's order (the depth terms): row i of
+// the caller is row inv[i] of the bucketed storage, the backward is the inverse gather (map perm).
+class RayRowsUnpermuteFn : public torch::autograd::Function<RayRowsUnpermuteFn>
+{
+public:
+  static torch::autograd::variable_list forward(
+    torch::autograd::AutogradContext * ctx, Tensor rows, Tensor perm, Tensor inv)
+  {
+    rows = f2n::dev_f32(rows, "per-ray rows");
+    TORCH_CHECK(rows.dim() == 2 && rows.size(0) == perm.size(0), "per-ray rows shape");
+    ctx->save_for_backward({perm});
+    ctx->set_materialize_grads(!f2n::lean_grads());
+    return {gather(rows, inv)};
+  }
+
+  static torch::autograd::variable_list backward(
+    torch::autograd::AutogradContext * ctx, torch::autograd::variable_list g)
+  {
+    if (!g[0].defined()) return {Tensor(), Tensor(), Tensor()};
+    return {gather(f2n::dev_f32(g[0], "grad per-ray rows"), ctx->get_saved_variables()[0]), Tensor(),
+            Tensor()};
+  }
+
+private:
+  static Tensor gather(const Tensor & src, const Tensor & map)
+  {
+    Tensor dst = torch::empty_like(src);
+    if (src.numel() > 0)
+      f2n::check(
+        f2n_gather_rows(
+          f2n::fptr(src), dst.data_ptr<float>(), map.data_ptr<int32_t>(), (int)src.size(0),
+          (int)src.size(1), f2n::current_stream(src)),
+        "f2n_gather_rows");
+    return dst;
+  }
+};
+
 // Identity on the encoding of the kept samples whose backward also forms the rays' gradient from
 // the encoding's (f2n_hash_rays_grad).  The encoding's gradient is handed on untouched, so the table
 // gradient (Hash3DAnchoredFunction) and everything else upstream see exactly what they see without
@@ -275,11 +314,25 @@ RenderResult Renderer::render_for_loss(
   return render_routed(rays_o, rays_d, emb_idx, mode, noise_in, bg_in, true, want_dist);
 }
 
+RenderResult Renderer::render_for_loss(
+  const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
+  const Tensor & noise_in, const Tensor & bg_in, bool want_dist, const Tensor & depth_target,
+  float depth_eps)
+{
+  return render_routed(
+    rays_o, rays_d, emb_idx, mode, noise_in, bg_in, true, want_dist, depth_target, depth_eps);
+}
+
 RenderResult Renderer::render_routed(
   const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-  const Tensor & noise_in, const Tensor & bg_in, bool for_loss, bool want_dist)
+  const Tensor & noise_in, const Tensor & bg_in, bool for_loss, bool want_dist,
+  const Tensor & depth_target, float depth_eps)
 {
   const int64_t n_rays = rays_o.size(0);
+  if (depth_target.defined()) {
+    TORCH_CHECK(depth_target.numel() == n_rays, "depth_target must be [n_rays]");
+    TORCH_CHECK(std::isfinite(depth_eps) && depth_eps >= 0.f, "depth_eps must be finite and >= 0");
+  }
   const auto fopt = f2n::float_on(rays_o.device());
   // the uniform draw first, as ever (the generator stream does not depend on the route); the lean
   // dense route hands it to its sampler raw, every other route gets draw_noise's two passes over it
@@ -293,6 +346,7 @@ RenderResult Renderer::render_routed(
     RenderResult none{
       bg_color, torch::zeros({n_rays}, fopt), torch::full({n_rays}, 512.f, fopt), Tensor()};
     if (want_dist) none.weight_dist = torch::zeros({n_rays}, fopt);
+    if (depth_target.defined()) none.depth_terms = torch::zeros({n_rays, 3}, fopt);
     if (options_.normals) none.normals = torch::zeros({n_rays, 3}, fopt);
     return none;
   }
@@ -300,6 +354,10 @@ RenderResult Renderer::render_routed(
   route.noise_raw = route.lean && raw.defined();
   route.want_var = route.lean && route.bucketed && for_loss;
   route.want_dist = want_dist;
+  if (depth_target.defined()) {
+    route.depth_target = f2n::dev_f32(depth_target.detach(), "depth_target").reshape({n_rays});
+    route.depth_eps = depth_eps;
+  }
   const Tensor noise = noise_in.defined() ? noise_in
                        : route.noise_raw  ? raw
                                           : PtsSampler::cook_noise(raw);
@@ -412,6 +470,9 @@ RenderResult Renderer::render_op_by_op(
   Tensor depths = FlexOps::Sum(weights * sampled_t, idx) / (1.f - last_trans + 1e-4f);
   RenderResult res{colors, depths, weights, idx};
   if (route.want_dist) res.weight_dist = CustomOps::WeightDist(weights, kept.t, kept.dt, idx);
+  if (route.depth_target.defined())
+    res.depth_terms =
+      CustomOps::DepthSight(weights, kept.t, kept.dt, idx, route.depth_target, route.depth_eps);
   if (options_.normals) res.normals = ray_normals(kept, weights);
   return res;
 }
@@ -510,9 +571,19 @@ RenderResult Renderer::render_dense_bucketed(
       emb_idx.defined() ? emb_p.data_ptr<int32_t>() : nullptr, bg_p.data_ptr<float>(),
       f2n::fptr_mut(noise_p), inv.data_ptr<int32_t>(), stream),
     "f2n_ray_permute");
+  // a depth target travels with its ray: bucketed ray j is the caller's ray perm[j]
+  Route route_p = route;
+  if (route.depth_target.defined()) {
+    route_p.depth_target = torch::empty_like(route.depth_target);
+    f2n::check(
+      f2n_gather_rows(
+        route.depth_target.data_ptr<float>(), route_p.depth_target.data_ptr<float>(),
+        perm.data_ptr<int32_t>(), n_rays, 1, stream),
+      "f2n_gather_rows");
+  }
   RenderResult r = route.lean
-                     ? render_dense(o_p, d_p, emb_p, mode, noise, bg_p, route, perm)
-                     : render_dense(o_p, d_p, emb_p, mode, noise_p, bg_p, route);
+                     ? render_dense(o_p, d_p, emb_p, mode, noise, bg_p, route_p, perm)
+                     : render_dense(o_p, d_p, emb_p, mode, noise_p, bg_p, route_p);
 
   // every ray kept all S samples (n_kept = n*S, counts <= S): the bounds {i*S, (i+1)*S} are the same
   // in both orders; otherwise the caller-order counts are scanned as the unbucketed route scans them
@@ -530,17 +601,21 @@ RenderResult Renderer::render_dense_bucketed(
   // the distortion loss was taken in composite(), where the weights, t and dt of the bucketed order
   // lie: one float per ray rides back (nothing, when it was not asked for)
   const Tensor dist = route.want_dist ? r.weight_dist : torch::empty({0}, rays_o.options());
+  // ... and so do the depth terms, three floats per ray, through a node of their own: without a
+  // target nothing here is launched or recorded
+  const Tensor terms =
+    r.depth_terms.defined() ? RayRowsUnpermuteFn::apply(r.depth_terms, perm, inv)[0] : Tensor();
   if (route.want_var) {
     // the variance is a per-ray quantity: taken where the weights lie, its [n_rays] result goes back
     // with colours and depths as rows of one float -- no [n, S] gather forward or backward
     Tensor var = CustomOps::WeightVar(r.weights, r.idx_start_end);
     auto out = RayUnpermuteFn::apply(
       r.colors, r.depths, var, dist, perm, inv, r.idx_start_end, bounds, /*S=*/1, /*rows=*/true);
-    return {out[0], out[1], Tensor(), bounds, out[2], route.want_dist ? out[3] : Tensor()};
+    return {out[0], out[1], Tensor(), bounds, out[2], route.want_dist ? out[3] : Tensor(), terms};
   }
   auto out = RayUnpermuteFn::apply(
     r.colors, r.depths, r.weights, dist, perm, inv, r.idx_start_end, bounds, S, rows);
-  return {out[0], out[1], out[2], bounds, Tensor(), route.want_dist ? out[3] : Tensor()};
+  return {out[0], out[1], out[2], bounds, Tensor(), route.want_dist ? out[3] : Tensor(), terms};
 }
 
 // Dense first pass: every sample is encoded once (level-major kernel), the keep-prefix comes from
@@ -822,6 +897,9 @@ RenderResult Renderer::composite(
   // occupancy grid or not; t and dt get no gradient)
   if (route.want_dist)
     res.weight_dist = CustomOps::WeightDist(out.weights, kept.t, kept.dt, kept.pts_idx_bounds);
+  if (route.depth_target.defined())
+    res.depth_terms = CustomOps::DepthSight(
+      out.weights, kept.t, kept.dt, kept.pts_idx_bounds, route.depth_target, route.depth_eps);
   if (options_.normals && final) res.normals = ray_normals(kept, out.weights);
   return res;
 }
@@ -1124,10 +1202,48 @@ f2n::TrainStepResult f2n::train_step(
   const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
   const Tensor & bg_color, bool run_backward)
 {
+  return train_step(
+    renderer, rays_o, rays_d, emb_idx, gt_colors, var_loss_weight, dist_loss_weight, noise, bg_color,
+    run_backward, Tensor(), DepthLossOptions());
+}
+
+f2n::TrainStepResult f2n::train_step(
+  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
+  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
+  const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
+  const DepthLossOptions & depth_loss)
+{
   // (a zero distortion weight: the term is not computed and the call is the one without it)
   const bool want_dist = dist_loss_weight != 0.f;
-  RenderResult res = renderer.render_for_loss(
-    rays_o, rays_d, emb_idx, RunningMode::TRAIN, noise, bg_color, want_dist);
+  // (the same rule for the depth terms: no target, or three zero weights, and nothing of them exists)
+  const bool want_depth = depth_target.defined() && (depth_loss.empty != 0.f ||
+                                                      depth_loss.near != 0.f ||
+                                                      depth_loss.expected != 0.f);
+  // The per-batch constants of the term -- n_valid, counted on the device, and lambda_i / n_valid --
+  // are enqueued BEFORE the render, where the host runs ahead of the GPU: the dense route reads one
+  // flag back per chunk, and small launches made between that read and the backward are on the
+  // critical path.  One column sum, one dot product and one addition remain after it.
+  Tensor depth_n_valid, depth_coef;
+  if (want_depth) {
+    torch::NoGradGuard no_grad;
+    const Tensor z = f2n::dev_f32(depth_target.detach(), "depth_target").reshape({-1});
+    depth_n_valid = z.gt(0.f)
+                      .logical_and(z.lt(std::numeric_limits<float>::infinity()))
+                      .sum()
+                      .to(torch::kFloat32)
+                      .clamp_min(1.f);
+    Tensor lambda = torch::empty({3}, z.options());  // (filled by launches: nothing is copied over)
+    lambda.select(0, 0).fill_(depth_loss.empty);
+    lambda.select(0, 1).fill_(depth_loss.near);
+    lambda.select(0, 2).fill_(depth_loss.expected);
+    depth_coef = lambda / depth_n_valid;
+  }
+  RenderResult res = want_depth
+                       ? renderer.render_for_loss(
+                           rays_o, rays_d, emb_idx, RunningMode::TRAIN, noise, bg_color, want_dist,
+                           depth_target, depth_loss.eps)
+                       : renderer.render_for_loss(
+                           rays_o, rays_d, emb_idx, RunningMode::TRAIN, noise, bg_color, want_dist);
   // colour loss + variance loss + squared error in two launches (f2n_loss_fwd; the ATen spelling of
   // the reference, train_manager.cpp:78-96, is ~23 launches of a few microseconds each)
   Tensor var = res.weight_var.defined() ? res.weight_var
@@ -1142,6 +1258,13 @@ f2n::TrainStepResult f2n::train_step(
     Tensor dist_loss = res.weight_dist.mean();
     loss = loss + dist_loss_weight * dist_loss;
     renderer.last_dist_loss_ = dist_loss.detach();
+  }
+  renderer.last_depth_loss_ = Tensor();
+  if (want_depth && res.depth_terms.numel() > 0) {
+    // invalid rays hold exact zeros: the sum over all rays is the sum over the valid ones
+    const Tensor sums = res.depth_terms.sum(0);  // [3]
+    loss = loss + torch::dot(sums, depth_coef);
+    renderer.last_depth_loss_ = sums.detach() / depth_n_valid;
   }
   TrainStepResult out;
   out.loss = loss.detach();

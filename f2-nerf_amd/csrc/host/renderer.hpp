@@ -73,6 +73,10 @@ struct RenderResult
   // Renderer::render_for_loss with want_dist only: CustomOps::WeightDist of the kept samples'
   // weights, t and dt, [n_rays] in the caller's order, on every route; undefined otherwise
   Tensor weight_dist;
+  // Renderer::render_for_loss with a depth target only: CustomOps::DepthSight of the kept samples'
+  // weights, t and dt against that target, [n_rays, 3] = (empty space, near surface, expected depth)
+  // in the caller's order, on every route; undefined otherwise
+  Tensor depth_terms;
   // RendererOptions::normals only: N_r = sum_k w_k n^_k over the kept samples (f2n_ray_normals),
   // [n_rays, 3] in the caller's order, detached, not renormalised; undefined when the option is off
   Tensor normals;
@@ -177,6 +181,17 @@ public:
   RenderResult render_for_loss(
     const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
     const Tensor & noise, const Tensor & bg_color, bool want_dist);
+  // ... and, with a depth target, for their line-of-sight depth terms: `depth_target` [n_rays] is each
+  // ray's target distance along the ray, in the units of the rays (0, negative or non-finite: the ray
+  // has no return), `depth_eps` >= 0 the half-width of the surface band.  `depth_terms` [n_rays, 3] is
+  // defined on every route want_dist works on, taken where the kept samples' weights, t and dt lie; on
+  // the bucketed routes the target is permuted with the rays and the result rides back with colours
+  // and depths, nothing per-sample is gathered.  The target receives no gradient.  An undefined target
+  // makes this the call above exactly; colours, depths, weights and bounds keep their bits either way.
+  RenderResult render_for_loss(
+    const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
+    const Tensor & noise, const Tensor & bg_color, bool want_dist, const Tensor & depth_target,
+    float depth_eps);
 
   // The no-grad render as one kernel launch (f2n_render_rays): colours [n, 3], depths [n], last_trans
   // [n] (1 - opacity of the ray: an alpha mask) and kept [n] int32 (samples composited per ray).
@@ -245,6 +260,10 @@ public:
   // mean over the rays of weight_dist in the most recent f2n::train_step with a distortion weight
   // (device scalar, detached, no host read); undefined after a step without one
   Tensor last_dist_loss_;
+  // the three means over the valid rays (empty space, near surface, expected depth) of the most
+  // recent f2n::train_step with a depth target and a non-zero DepthLossOptions weight ([3], device,
+  // detached, no host read); undefined after a step without
+  Tensor last_depth_loss_;
 
 private:
   // Everything the routes branch on, decided once per render() call (choose_route).
@@ -262,6 +281,10 @@ private:
     bool noise_raw = false;  // lean: the noise is the renderer's own uniform draw, cooked in the sampler
     bool want_var = false;   // lean and bucketed, render_for_loss: hand back weight_var, not weights
     bool want_dist = false;  // render_for_loss: hand back weight_dist too
+    // render_for_loss with a depth target: [n_rays] f32 in the order of the rays the route renders
+    // (render_dense_bucketed permutes it with them), else undefined; hand back depth_terms too
+    Tensor depth_target;
+    float depth_eps = 0.f;
   };
   // What the shading pass hands to compositing: the field head's output ([n, 1] density logit of the
   // fused network, [n, 16] otherwise) and the colours [n, 3].
@@ -273,7 +296,8 @@ private:
   Route choose_route(const Tensor & rays_o, const Tensor & rays_d, const Tensor & bg_color) const;
   RenderResult render_routed(
     const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-    const Tensor & noise, const Tensor & bg_color, bool for_loss, bool want_dist);
+    const Tensor & noise, const Tensor & bg_color, bool for_loss, bool want_dist,
+    const Tensor & depth_target = Tensor(), float depth_eps = 0.f);
   bool fused_net_applies() const;
   // f2n_render_rays -- or, by options_.one_pass_head, the head or head + tail -- into preallocated
   // outputs (rows of one chunk)
@@ -366,5 +390,28 @@ TrainStepResult train_step(
   Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
   const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
   const Tensor & bg_color, bool run_backward);
+
+// Weights of the three line-of-sight depth terms (CustomOps::DepthSight) and the half-width of the
+// surface band.  All three weights exactly 0: no depth term.  The schedule (URF shrinks eps while
+// training) stays with the caller.
+struct DepthLossOptions
+{
+  float empty = 0.f;     // lambda of E_r: weight in the free space before the return
+  float near = 0.f;      // lambda of N_r: weight missing from the band around the return
+  float expected = 0.f;  // lambda of X_r: squared error of the expected depth
+  float eps = 0.f;       // half-width of the band, in the units of the rays
+};
+
+// ... with depth supervision: `depth_target` [n_rays] as in Renderer::render_for_loss, and
+//   loss += sum_i lambda_i * (sum over valid rays of term_i) / max(n_valid, 1),
+// n_valid counted on the device (no host read); the three means are left in
+// Renderer::last_depth_loss_.  An undefined target, or all three weights exactly 0, is the call above,
+// launch for launch and bit for bit: the term is neither computed nor differentiated -- the rule for
+// dist_loss_weight == 0.
+TrainStepResult train_step(
+  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
+  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
+  const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
+  const DepthLossOptions & depth_loss);
 
 }  // namespace f2n

@@ -388,6 +388,43 @@ int f2n_weight_dist_bwd(
   const float * weights, const float * t, const float * dt, const int32_t * idx,
   const float * d_out, float * dw, int n_rays, void * stream);
 
+/* The line-of-sight losses of depth supervision per ray (Urban Radiance Fields, Rematas et al., CVPR
+ * 2022, section 4.2: empty space, near surface, expected depth).  The reference has NO such kernel and
+ * reads no range data: these stand beside WeightVarLoss*Kernel (src/CustomOps/CustomOps.cu:13-67) and
+ * f2n_weight_dist_* above, on the same arrays, and are used where those are used
+ * (src/main_functions/train_manager.cpp:80-93).
+ *   weights, t, dt [n] f32 and idx [n_rays, 2] as for f2n_weight_dist_*: t is the interval END, the
+ *   midpoint is m_k = t_k - 0.5f * dt_k in f32 (one rounding).
+ *   z   [n_rays] f32: the ray's target distance, in the units of t (Euclidean distance along the unit
+ *       ray direction).  A ray is VALID iff z is finite and > 0.
+ *   eps f32 >= 0: half-width of the surface band; the caller schedules it.
+ * For a valid ray, lo = z - eps and hi = z + eps in f32 (one rounding each); sample k is FRONT if
+ * m_k < lo, BAND if m_k >= lo and m_k <= hi, BEHIND otherwise -- comparisons of f32 values, which are
+ * the definition.  Then
+ *     E_r = sum_front w_k^2                                (free space before the return)
+ *     W_r = sum_band  w_k,      N_r = (1 - W_r)^2          (the weight belongs in the band)
+ *     d_r = sum_all   w_k m_k,  X_r = (d_r - z_r)^2        (expected depth, not normalised by opacity)
+ *   f2n_depth_sight_fwd: out [n_rays, 3] = (E_r, N_r, X_r).  An invalid ray gives (0, 0, 0); a valid
+ *     ray with an empty range gives (0, 1, z^2).
+ *   f2n_depth_sight_bwd: with (g0, g1, g2) = d_out[r],
+ *         dw_k = g0 2 w_k [front]  -  g1 2 (1 - W_r) [band]  +  g2 2 (d_r - z_r) m_k
+ *     for k in ray r's range; an invalid ray WRITES ZEROS over its own range.  Every element inside
+ *     some range is written, nothing outside (the caller zeroes dw if it needs zeros there).
+ *     Recomputed from the inputs; no state is saved by the forward.
+ * t, dt and z receive no gradient.  A non-finite weight poisons its own ray only.  One wavefront per
+ * ray, no atomics, no LDS, no scratch: the same bits on every run; the evaluation order is fixed in
+ * the header comment of depth_sight.hip (the per-ray convention of the kernels that replace
+ * src/CustomOps/CustomOps.cu:13-67).  Not here: URF's Gaussian near-surface kernel (the band with a
+ * shrinking eps is its limit).
+ * A null idx, z or output, n_rays < 0, or an eps that is negative or not finite: F2N_E_INVALID_ARG
+ * before any HIP work; n_rays == 0: F2N_OK. */
+int f2n_depth_sight_fwd(
+  const float * weights, const float * t, const float * dt, const int32_t * idx, const float * z,
+  float eps, float * out, int n_rays, void * stream);
+int f2n_depth_sight_bwd(
+  const float * weights, const float * t, const float * dt, const int32_t * idx, const float * z,
+  float eps, const float * d_out, float * dw, int n_rays, void * stream);
+
 /* ------------------------------------------------------------------ scatter (row A9) ---------- */
 
 /* ScatterIdxKernal -- src/CustomOps/Scatter.cu:111-132 */
@@ -529,6 +566,31 @@ int f2n_pose_compose_bwd(
 int f2n_project_points(
   const float * points, const float * poses, int pose_ld, const float * intrinsics,
   const float * dist, int64_t n_cams, const int32_t * cam_idx, float * pix, int32_t * valid,
+  int64_t n, void * stream);
+
+/* A point cloud to sparse per-camera depth maps: the targets of f2n_depth_sight_*.  The reference
+ * reads no range data; the camera is the one f2n_project_points models (the projection that
+ * src/rays.cpp:7-28 inverts, with the coefficients of src/dataset.cpp:59-63), and every point is
+ * projected by the device function that entry calls, so its pixel decisions agree bit for bit.
+ *   points  [n, 3] in the frame of the poses;  cam_idx [n] i32: point i is seen by camera cam_idx[i]
+ *           (NULL: addressed as in f2n_project_points); a value outside [0, n_cams) skips the point,
+ *           it is never used as an address
+ *   poses, pose_ld, intrinsics, dist (NULL = pinhole), n_cams: as in f2n_project_points
+ *   depth   [n_cams, h, w] f32, every element written; 0 = no return
+ * A point is skipped unless it lies strictly in front of its camera (c_z < 0) and
+ * (floor(row), floor(col)) falls inside [0, h) x [0, w).  Otherwise d = |p - t_cam|, the distance
+ * ALONG THE RAY (what the samples' t measures), not the z-depth, and each pixel keeps the minimum:
+ * an unsigned 32-bit atomicMin on the float's bit pattern (positive floats order like their bits).
+ * A minimum does not depend on the order of arrival: two launches give the same bits.  The entry
+ * fills the map with +inf, splats, and turns what is still +inf into 0 -- an async memset and two
+ * launches on `stream`; no allocation, no sync, no host read.  No occlusion reasoning beyond that
+ * per-pixel minimum.
+ * Null poses, intrinsics or depth (or points with n > 0), n < 0, n_cams, h or w < 1, a pose_ld other
+ * than 12 or 16: F2N_E_INVALID_ARG; h * w * n_cams >= 2^31: F2N_E_UNSUPPORTED; both before any HIP
+ * work.  n == 0: all zeros and F2N_OK. */
+int f2n_depth_splat(
+  const float * points, const int32_t * cam_idx, const float * poses, int pose_ld,
+  const float * intrinsics, const float * dist, int64_t n_cams, int h, int w, float * depth,
   int64_t n, void * stream);
 
 /* PtsSampler::get_samples (about 20 ATen launches) -- src/points_sampler.cpp:20-64.
