@@ -669,6 +669,27 @@ int f2n_sample_compact(
   const float * rays_o, const float * rays_d, const float * noise, const int32_t * bounds,
   float * pts, float * dirs, float * dt, float * t, int n_rays, int S, float step, void * stream);
 
+/* Diagnostic: the ray walk behind every sampler, march and one-pass render kernel -- the samples of
+ * src/points_sampler.cpp:20-64 and the early stop of src/renderer.cpp:58-90 -- written out sample by
+ * sample at one of its three lane mappings.  The march and the render kernels give a ray 64, 16 or 8
+ * lanes and let only counts and colours leave the device; this entry walks EVERY stride of every ray
+ * (no early break; a lane is live when it holds a sample) at the mapping asked for and writes what
+ * each lane holds.  Nothing in the host library calls it.
+ *   noise    [n_rays, S] f32 step multipliers or NULL (all ones), as f2n_sample_rays
+ *   sec_in   [n_rays, S] f32 optical depth sigma * dt of every sample, or NULL (none)
+ *   width    64, 16 or 8: lanes to a ray
+ *   outputs  pts [n_rays*S, 3], dt, t [n_rays*S]: f2n_sample_rays' values bit for bit at every width;
+ *            with sec_in, depth [n_rays*S] f32 = the exclusive sum of sec_in in front of the sample as
+ *            the early stop forms it, and keep [n_rays*S] u8 = expf(-depth) > t_thresh.  Without
+ *            sec_in, depth and keep may be NULL and are not written.
+ * A width other than the three, a null among rays_o, rays_d, pts, dt, t (or depth, keep with sec_in),
+ * n_rays < 0, S < 1 or n_rays * S > INT32_MAX: F2N_E_INVALID_ARG before any HIP work; n_rays == 0:
+ * F2N_OK. */
+int f2n_ray_walk_probe(
+  const float * rays_o, const float * rays_d, const float * noise, const float * sec_in, int width,
+  float * pts, float * dt, float * t, float * depth, uint8_t * keep, int n_rays, int S, float step,
+  float t_thresh, void * stream);
+
 /* ------------------------------------------------------------------ occupancy bitfield -------- */
 
 /* Empty-space skipping for the early-stop march.  The reference fork stripped upstream's occupancy

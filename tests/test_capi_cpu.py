@@ -113,6 +113,29 @@ def test_density_march_two_faults_answer_with_the_first_check(capi):
         assert fn(*args) == want, faults
 
 
+def test_ray_walk_probe_validates_before_any_hip_work(capi):
+    """f2n_ray_walk_probe: a width other than 64, 16, 8, a null among the required pointers (depth and
+    keep are required with sec_in only), n_rays < 0, S < 1 and n_rays * S > INT32_MAX are
+    F2N_E_INVALID_ARG; n_rays == 0 is F2N_OK.  Every call here has a fault or no rays: nothing is
+    launched."""
+    INVALID, OK = -1, 0
+    fn = capi.lib().cdll.f2n_ray_walk_probe
+    fake = 0x1000
+    # (rays_o, rays_d, noise, sec_in, width, pts, dt, t, depth, keep, n_rays, S, step, t_thresh, stream)
+    good = [fake, fake, None, None, 8, fake, fake, fake, None, None, 4, 128, 1.0 / 32, 1e-4, None]
+    for faults, want in (({4: 0}, INVALID), ({4: 32}, INVALID), ({4: 4}, INVALID), ({4: -8}, INVALID),
+                         ({4: 128}, INVALID), ({0: None}, INVALID), ({1: None}, INVALID),
+                         ({5: None}, INVALID), ({6: None}, INVALID), ({7: None}, INVALID),
+                         ({3: fake}, INVALID), ({3: fake, 8: fake}, INVALID), ({3: fake, 9: fake}, INVALID),
+                         ({10: -1}, INVALID), ({11: 0}, INVALID), ({10: 1 << 21, 11: 1 << 10}, INVALID),
+                         ({10: 0}, OK), ({10: 0, 0: None, 5: None}, OK), ({10: 0, 4: 16}, OK),
+                         ({10: 0, 4: 64}, OK), ({10: 0, 4: 7}, INVALID), ({10: 0, 11: 0}, INVALID)):
+        args = list(good)
+        for i, bad in faults.items():
+            args[i] = bad
+        assert fn(*args) == want, faults
+
+
 def test_host_module_mirrors_reference_layout(pkg):
     H = pkg.load_host()
     H.manual_seed(2022)
