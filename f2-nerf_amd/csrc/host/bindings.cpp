@@ -10,6 +10,7 @@
 #include "localizer.hpp"
 #include "mesh.hpp"
 #include "occupancy_grid.hpp"
+#include "pixel_mask.hpp"
 #include "points_sampler.hpp"
 #include "pose_refiner.hpp"
 #include "ragged_ops.hpp"
@@ -191,6 +192,62 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     "f2n_project_points -> (pix [N,2] (row, col), valid [N] i32)");
   m.def("train_loss", &f2n::train_loss, py::arg("colors"), py::arg("gt_colors"), py::arg("var"),
         py::arg("var_loss_weight"));
+  m.def(
+    "train_loss_sup",
+    [](const Tensor & colors, const Tensor & gt, const Tensor & var,
+       const c10::optional<Tensor> & opacity, const c10::optional<Tensor> & ray_weight,
+       const c10::optional<Tensor> & alpha, const c10::optional<Tensor> & bg, float var_loss_weight,
+       float opacity_weight) {
+      return f2n::train_loss_sup(
+        colors, gt, var, opt_tensor(opacity), opt_tensor(ray_weight), opt_tensor(alpha),
+        opt_tensor(bg), var_loss_weight, opacity_weight);
+    },
+    py::arg("colors"), py::arg("gt_colors"), py::arg("var"), py::arg("opacity") = py::none(),
+    py::arg("ray_weight") = py::none(), py::arg("alpha") = py::none(),
+    py::arg("bg_color") = py::none(), py::arg("var_loss_weight") = 0.f,
+    py::arg("opacity_weight") = 0.f,
+    "f2n_loss_sup_fwd as one autograd node -> [6] = (loss, colour, var, opacity term, weighted "
+    "squared error, sum of the ray weights); see f2n::train_loss_sup");
+  py::class_<f2n::PixelMask>(m, "PixelMask")
+    .def_static("from_mask", &f2n::PixelMask::from_mask, py::arg("mask"),
+                "mask [E,h,w] (or [h,w]) uint8 / bool on the GPU, non-zero = valid (f2n_mask_pack)")
+    .def_readonly("bits", &f2n::PixelMask::bits, "[ceil(E*h*w / 32)] int32 holding the uint32 words")
+    .def_readonly("count", &f2n::PixelMask::count, "[1] int64 on the device: valid pixels")
+    .def_readonly("E", &f2n::PixelMask::E)
+    .def_readonly("h", &f2n::PixelMask::h)
+    .def_readonly("w", &f2n::PixelMask::w);
+  m.def(
+    "draw_pixels_masked",
+    [](const f2n::PixelMask & mask, int64_t n, uint64_t seed, int attempts) {
+      auto [cam, ij, tries] = f2n::draw_pixels_masked(mask, n, seed, attempts);
+      return py::make_tuple(cam, ij, tries);
+    },
+    py::arg("mask"), py::arg("n"), py::arg("seed"), py::arg("attempts") = 32,
+    "f2n_draw_pixels_masked -> (cam [n] i32, ij [n,2] i32, tries [n] i32; 0 = every attempt missed)");
+  m.def(
+    "sample_masked_rays",
+    [](const Tensor & poses, const Tensor & intr, const f2n::PixelMask & mask, int64_t n,
+       uint64_t seed, const c10::optional<Tensor> & images, const c10::optional<Tensor> & dist,
+       int attempts) {
+      f2n::MaskedBatch b = f2n::sample_masked_rays(
+        poses, intr, mask, n, seed, opt_tensor(images), opt_tensor(dist), attempts);
+      py::dict d;
+      d["rays_o"] = b.rays.origins;
+      d["rays_d"] = b.rays.dirs;
+      d["gt"] = tensor_or_none(b.gt);
+      d["alpha"] = tensor_or_none(b.alpha);
+      d["cam"] = b.cam;
+      d["ray_weight"] = b.ray_weight;
+      d["ij"] = b.ij;
+      d["tries"] = b.tries;
+      return d;
+    },
+    py::arg("poses"), py::arg("intrinsics"), py::arg("mask"), py::arg("batch_size"),
+    py::arg("seed"), py::arg("images") = py::none(), py::arg("dist") = py::none(),
+    py::arg("attempts") = 32,
+    "sample_random_rays restricted to the mask's valid pixels: dict of rays_o, rays_d, gt | None, "
+    "alpha | None (images with four channels), cam, ray_weight (0 where every attempt missed), ij, "
+    "tries; see f2n::sample_masked_rays");
   m.def("ray_order", &f2n::ray_order, "caller indices of rays_d sorted into pixel-compact bundles");
   m.def("manual_seed", [](uint64_t s) { torch::manual_seed(s); });
   m.def("kernel_timer_enable", &f2n::kernel_timer_enable);
@@ -313,7 +370,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
       "[n_rays, 3] line-of-sight depth terms, or None unless render_for_loss got a depth_target")
     .def_property_readonly(
       "normals", [](const RenderResult & r) { return tensor_or_none(r.normals); },
-      "[n_rays, 3] sum of w n^ over the kept samples, or None when RendererOptions::normals is off");
+      "[n_rays, 3] sum of w n^ over the kept samples, or None when RendererOptions::normals is off")
+    .def_property_readonly(
+      "opacity", [](const RenderResult & r) { return tensor_or_none(r.opacity); },
+      "[n_rays] sum of the kept samples' weights, or None unless render_for_loss got want_opacity");
+  py::class_<f2n::RaySupervision>(m, "RaySupervision")
+    .def(
+      py::init([](const c10::optional<Tensor> & ray_weight, const c10::optional<Tensor> & alpha,
+                  float opacity_weight) {
+        return f2n::RaySupervision{opt_tensor(ray_weight), opt_tensor(alpha), opacity_weight};
+      }),
+      py::arg("ray_weight") = py::none(), py::arg("alpha") = py::none(),
+      py::arg("opacity_weight") = 0.f,
+      "per-ray weights [n_rays], alpha targets [n_rays] and the weight of the opacity term")
+    .def_property_readonly(
+      "ray_weight", [](const f2n::RaySupervision & s) { return tensor_or_none(s.ray_weight); })
+    .def_property_readonly(
+      "alpha", [](const f2n::RaySupervision & s) { return tensor_or_none(s.alpha); })
+    .def_readwrite("opacity_weight", &f2n::RaySupervision::opacity_weight);
   py::class_<f2n::DepthLossOptions>(m, "DepthLossOptions")
     .def(
       py::init([](float empty, float near, float expected, float eps) {
@@ -397,8 +471,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
       [](Renderer & r, const Tensor & o, const Tensor & d, const c10::optional<Tensor> & emb_idx,
          const std::string & mode, const c10::optional<Tensor> & noise,
          const c10::optional<Tensor> & bg, bool want_dist,
-         const c10::optional<Tensor> & depth_target, float depth_eps) {
+         const c10::optional<Tensor> & depth_target, float depth_eps, bool want_opacity) {
         py::gil_scoped_release no_gil;
+        if (want_opacity)
+          return r.render_for_loss(
+            o, d, opt_tensor(emb_idx), parse_mode(mode), opt_tensor(noise), opt_tensor(bg), want_dist,
+            opt_tensor(depth_target), depth_eps, true);
         return depth_target.has_value()
                  ? r.render_for_loss(
                      o, d, opt_tensor(emb_idx), parse_mode(mode), opt_tensor(noise), opt_tensor(bg),
@@ -410,9 +488,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
       py::arg("rays_o"), py::arg("rays_d"), py::arg("emb_idx") = py::none(),
       py::arg("mode") = "train", py::arg("noise") = py::none(), py::arg("bg_color") = py::none(),
       py::arg("want_dist") = false, py::arg("depth_target") = py::none(),
-      py::arg("depth_eps") = 0.f,
+      py::arg("depth_eps") = 0.f, py::arg("want_opacity") = false,
       "render_for_loss handing back the RenderResult: colors, depths, weights, idx_start_end, "
-      "weight_var, weight_dist, depth_terms, normals by name (None where undefined)")
+      "weight_var, weight_dist, depth_terms, normals, opacity by name (None where undefined)")
     .def(
       "render_rays",
       [](Renderer & r, const Tensor & o, const Tensor & d, const c10::optional<Tensor> & emb_idx,
@@ -488,6 +566,31 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
       "reference train_manager.cpp:76-107 without the optimiser step; dist_loss_weight > 0 adds the "
       "distortion loss (its mean: last_dist_loss); depth_target [n_rays] with a DepthLossOptions "
       "that has a non-zero weight adds the line-of-sight depth terms (their means: last_depth_loss)")
+    .def(
+      "train_step_supervised",
+      [](Renderer & r, const Tensor & o, const Tensor & d, const Tensor & emb_idx, const Tensor & gt,
+         const f2n::RaySupervision & sup, float var_loss_weight,
+         const c10::optional<Tensor> & noise, const c10::optional<Tensor> & bg, bool backward,
+         float dist_loss_weight, const c10::optional<Tensor> & depth_target,
+         const f2n::DepthLossOptions & depth_loss) {
+        f2n::TrainStepResult out;
+        {
+          py::gil_scoped_release no_gil;
+          out = f2n::train_step(
+            r, o, d, emb_idx, gt, var_loss_weight, dist_loss_weight, opt_tensor(noise),
+            opt_tensor(bg), backward, opt_tensor(depth_target), depth_loss, sup);
+        }
+        return py::make_tuple(
+          out.loss, out.sq_err_sum, out.n_values, out.n_samples, tensor_or_none(out.weight_sum));
+      },
+      py::arg("rays_o"), py::arg("rays_d"), py::arg("emb_idx"), py::arg("gt_colors"),
+      py::arg("sup"), py::arg("var_loss_weight") = 0.f, py::arg("noise") = py::none(),
+      py::arg("bg_color") = py::none(), py::arg("backward") = true,
+      py::arg("dist_loss_weight") = 0.f, py::arg("depth_target") = py::none(),
+      py::arg("depth_loss") = f2n::DepthLossOptions(),
+      "train_step with a RaySupervision (masked rays, alpha targets): (loss, sq_err_sum, n_values, "
+      "n_samples, weight_sum | None).  A RaySupervision without ray_weight and alpha is train_step "
+      "itself, launch for launch; the opacity term's mean is left in last_opacity_loss")
     .def("named_parameters", [](Renderer & r) { return named_params(r); })
     .def("zero_grad", [](Renderer & r) { r.zero_grad(); })
     .def(
@@ -530,6 +633,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def_property_readonly(
       "last_depth_loss", [](const Renderer & r) { return tensor_or_none(r.last_depth_loss_); },
       "[3] means over the valid rays of the depth terms of the last train_step that had them, or None")
+    .def_property_readonly(
+      "last_opacity_loss", [](const Renderer & r) { return tensor_or_none(r.last_opacity_loss_); },
+      "weighted mean of (opacity - alpha)^2 of the last train_step that had the term, or None")
     .def_readonly("last_kept_fraction", &Renderer::last_kept_fraction_)
     .def_readonly("last_n_samples", &Renderer::last_n_samples_)
     .def_property_readonly("scene_field", [](Renderer & r) { return r.scene_field_; })

@@ -575,6 +575,78 @@ public:
   }
 };
 
+// f2n_loss_sup_fwd as one node.  ray_weight, alpha, opacity, bg: a tensor of no elements stands for
+// "absent" (an autograd node takes no undefined input).
+class TrainLossSupFn : public torch::autograd::Function<TrainLossSupFn>
+{
+public:
+  static variable_list forward(
+    AutogradContext * ctx, Tensor colors, Tensor gt, Tensor var, Tensor opacity, Tensor ray_weight,
+    Tensor alpha, Tensor bg, double var_weight, double opacity_weight)
+  {
+    colors = f2n::dev_f32(colors, "train_loss_sup colors");
+    gt = f2n::dev_f32(gt, "train_loss_sup gt_colors");
+    var = f2n::dev_f32(var, "train_loss_sup var");
+    const int64_t n_rays = colors.size(0);
+    TORCH_CHECK(
+      colors.dim() == 2 && colors.size(1) == 3 && gt.sizes() == colors.sizes() &&
+        var.numel() == n_rays && n_rays > 0 && n_rays <= INT32_MAX,
+      "train_loss_sup: colors/gt [n_rays,3], var [n_rays]");
+    auto per_ray = [&](Tensor & t, int64_t width, const char * name) {
+      if (t.numel() == 0) {
+        t = Tensor();
+        return;
+      }
+      t = f2n::dev_f32(t, name);
+      TORCH_CHECK(t.numel() == n_rays * width, name, " has the wrong number of elements");
+    };
+    const bool has_opacity = opacity.numel() > 0;
+    const std::vector<int64_t> opacity_shape = opacity.sizes().vec();
+    per_ray(opacity, 1, "train_loss_sup opacity");
+    per_ray(ray_weight, 1, "train_loss_sup ray_weight");
+    per_ray(alpha, 1, "train_loss_sup alpha");
+    per_ray(bg, 3, "train_loss_sup bg_color");
+    TORCH_CHECK(!alpha.defined() || bg.defined(), "train_loss_sup: alpha needs bg_color");
+    TORCH_CHECK(
+      !alpha.defined() || opacity_weight == 0. || opacity.defined(),
+      "train_loss_sup: alpha with an opacity weight needs the rendered opacity");
+    const bool with_op = alpha.defined() && opacity.defined();
+    Tensor d_colors = torch::empty_like(colors), d_var = torch::empty({n_rays}, colors.options());
+    Tensor d_opacity = with_op ? torch::empty({n_rays}, colors.options()) : Tensor();
+    Tensor partial = torch::empty({f2n_loss_sup_workspace_floats((int)n_rays)}, colors.options());
+    Tensor out = torch::empty({6}, colors.options());
+    f2n::check(
+      f2n_loss_sup_fwd(
+        colors.data_ptr<float>(), gt.data_ptr<float>(), var.data_ptr<float>(), f2n::fptr(ray_weight),
+        f2n::fptr(alpha), f2n::fptr(opacity), f2n::fptr(bg), (int)n_rays, (float)var_weight,
+        (float)opacity_weight, d_colors.data_ptr<float>(), d_var.data_ptr<float>(),
+        f2n::fptr_mut(d_opacity), partial.data_ptr<float>(), out.data_ptr<float>(),
+        f2n::current_stream(colors)),
+      "f2n_loss_sup_fwd");
+    ctx->save_for_backward({d_colors, d_var, with_op ? d_opacity : torch::empty({0}, colors.options())});
+    ctx->saved_data["var_shape"] = var.sizes().vec();
+    ctx->saved_data["opacity_shape"] = opacity_shape;
+    ctx->saved_data["has_opacity"] = has_opacity;
+    ctx->saved_data["with_op"] = with_op;
+    return {out};
+  }
+
+  static variable_list backward(AutogradContext * ctx, variable_list grad_output)
+  {
+    auto sv = ctx->get_saved_variables();
+    Tensor g = grad_output[0].select(0, 0);  // only the loss element carries gradient
+    Tensor d_var = (sv[1] * g).view(ctx->saved_data["var_shape"].toIntVector());
+    Tensor d_opacity;
+    if (ctx->saved_data["has_opacity"].toBool()) {
+      const auto shape = ctx->saved_data["opacity_shape"].toIntVector();
+      d_opacity = ctx->saved_data["with_op"].toBool() ? (sv[2] * g).view(shape)
+                                                      : torch::zeros(shape, sv[0].options());
+    }
+    return {sv[0] * g, Tensor(), d_var,    d_opacity, Tensor(),
+            Tensor(),  Tensor(), Tensor(), Tensor()};
+  }
+};
+
 }  // namespace
 
 namespace torch::autograd
@@ -692,4 +764,16 @@ Tensor f2n::train_loss(
   const Tensor & colors, const Tensor & gt_colors, const Tensor & var, float var_loss_weight)
 {
   return TrainLossFn::apply(colors, gt_colors, var, (double)var_loss_weight)[0];
+}
+
+Tensor f2n::train_loss_sup(
+  const Tensor & colors, const Tensor & gt_colors, const Tensor & var, const Tensor & opacity,
+  const Tensor & ray_weight, const Tensor & alpha, const Tensor & bg_color, float var_loss_weight,
+  float opacity_weight)
+{
+  const Tensor none = torch::empty({0}, colors.options());
+  auto or_none = [&](const Tensor & t) { return t.defined() ? t : none; };
+  return TrainLossSupFn::apply(
+    colors, gt_colors, var, or_none(opacity), or_none(ray_weight), or_none(alpha), or_none(bg_color),
+    (double)var_loss_weight, (double)opacity_weight)[0];
 }

@@ -118,6 +118,20 @@ bool shade_rays_applies(int64_t n, int64_t n_rays, int64_t S);
 Tensor train_loss(
   const Tensor & colors, const Tensor & gt_colors, const Tensor & var, float var_loss_weight);
 
+// The same loss with per-ray weights and alpha targets, as one autograd node over f2n_loss_sup_fwd
+// (it stands beside the reference's src/main_functions/train_manager.cpp:78-96, which has no mask):
+// returns [6] = {loss, colour, var, opacity term, weighted sum of squared colour error, sum of the ray
+// weights}; differentiable in colors [n_rays, 3], var [n_rays] and opacity [n_rays] through element 0.
+// opacity, ray_weight [n_rays], alpha [n_rays] and bg_color [n_rays, 3] may each be undefined:
+// no weight means 1, no alpha means the plain ground truth and no opacity term; alpha needs bg_color
+// (the background the render blended in) and, with opacity_weight != 0, the rendered opacity.
+// gt_colors, ray_weight, alpha and bg_color get no gradient.  Both means divide by the sum of the
+// weights (1 when that is not positive), formed on the device: no host read.
+Tensor train_loss_sup(
+  const Tensor & colors, const Tensor & gt_colors, const Tensor & var, const Tensor & opacity,
+  const Tensor & ray_weight, const Tensor & alpha, const Tensor & bg_color, float var_loss_weight,
+  float opacity_weight);
+
 // C = L*F values the fused kernel is built for
 inline bool shade_supported(int64_t C) { return C == 8 || C == 16 || C == 32 || C == 64; }
 

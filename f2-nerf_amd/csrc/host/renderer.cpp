@@ -323,10 +323,20 @@ RenderResult Renderer::render_for_loss(
     rays_o, rays_d, emb_idx, mode, noise_in, bg_in, true, want_dist, depth_target, depth_eps);
 }
 
+RenderResult Renderer::render_for_loss(
+  const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
+  const Tensor & noise_in, const Tensor & bg_in, bool want_dist, const Tensor & depth_target,
+  float depth_eps, bool want_opacity)
+{
+  return render_routed(
+    rays_o, rays_d, emb_idx, mode, noise_in, bg_in, true, want_dist, depth_target, depth_eps,
+    want_opacity);
+}
+
 RenderResult Renderer::render_routed(
   const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
   const Tensor & noise_in, const Tensor & bg_in, bool for_loss, bool want_dist,
-  const Tensor & depth_target, float depth_eps)
+  const Tensor & depth_target, float depth_eps, bool want_opacity)
 {
   const int64_t n_rays = rays_o.size(0);
   if (depth_target.defined()) {
@@ -348,12 +358,14 @@ RenderResult Renderer::render_routed(
     if (want_dist) none.weight_dist = torch::zeros({n_rays}, fopt);
     if (depth_target.defined()) none.depth_terms = torch::zeros({n_rays, 3}, fopt);
     if (options_.normals) none.normals = torch::zeros({n_rays, 3}, fopt);
+    if (want_opacity) none.opacity = torch::zeros({n_rays}, fopt);
     return none;
   }
   Route route = choose_route(rays_o, rays_d, bg_color);
   route.noise_raw = route.lean && raw.defined();
   route.want_var = route.lean && route.bucketed && for_loss;
   route.want_dist = want_dist;
+  route.want_opacity = want_opacity;
   if (depth_target.defined()) {
     route.depth_target = f2n::dev_f32(depth_target.detach(), "depth_target").reshape({n_rays});
     route.depth_eps = depth_eps;
@@ -474,6 +486,7 @@ RenderResult Renderer::render_op_by_op(
     res.depth_terms =
       CustomOps::DepthSight(weights, kept.t, kept.dt, idx, route.depth_target, route.depth_eps);
   if (options_.normals) res.normals = ray_normals(kept, weights);
+  if (route.want_opacity) res.opacity = FlexOps::Sum(weights, idx);
   return res;
 }
 
@@ -605,17 +618,28 @@ RenderResult Renderer::render_dense_bucketed(
   // target nothing here is launched or recorded
   const Tensor terms =
     r.depth_terms.defined() ? RayRowsUnpermuteFn::apply(r.depth_terms, perm, inv)[0] : Tensor();
+  // ... and the opacity, one float per ray, the same way
+  const Tensor opacity =
+    r.opacity.defined()
+      ? RayRowsUnpermuteFn::apply(r.opacity.unsqueeze(1), perm, inv)[0].squeeze(1)
+      : Tensor();
   if (route.want_var) {
     // the variance is a per-ray quantity: taken where the weights lie, its [n_rays] result goes back
     // with colours and depths as rows of one float -- no [n, S] gather forward or backward
     Tensor var = CustomOps::WeightVar(r.weights, r.idx_start_end);
     auto out = RayUnpermuteFn::apply(
       r.colors, r.depths, var, dist, perm, inv, r.idx_start_end, bounds, /*S=*/1, /*rows=*/true);
-    return {out[0], out[1], Tensor(), bounds, out[2], route.want_dist ? out[3] : Tensor(), terms};
+    RenderResult res{
+      out[0], out[1], Tensor(), bounds, out[2], route.want_dist ? out[3] : Tensor(), terms};
+    res.opacity = opacity;
+    return res;
   }
   auto out = RayUnpermuteFn::apply(
     r.colors, r.depths, r.weights, dist, perm, inv, r.idx_start_end, bounds, S, rows);
-  return {out[0], out[1], out[2], bounds, Tensor(), route.want_dist ? out[3] : Tensor(), terms};
+  RenderResult res{
+    out[0], out[1], out[2], bounds, Tensor(), route.want_dist ? out[3] : Tensor(), terms};
+  res.opacity = opacity;
+  return res;
 }
 
 // Dense first pass: every sample is encoded once (level-major kernel), the keep-prefix comes from
@@ -901,6 +925,9 @@ RenderResult Renderer::composite(
     res.depth_terms = CustomOps::DepthSight(
       out.weights, kept.t, kept.dt, kept.pts_idx_bounds, route.depth_target, route.depth_eps);
   if (options_.normals && final) res.normals = ray_normals(kept, out.weights);
+  // (the opacity of a ray is the plain sum of its kept samples' weights: the segment sum the
+  // op-by-op route composites with)
+  if (route.want_opacity) res.opacity = FlexOps::Sum(out.weights, kept.pts_idx_bounds);
   return res;
 }
 
@@ -1266,11 +1293,93 @@ f2n::TrainStepResult f2n::train_step(
     loss = loss + torch::dot(sums, depth_coef);
     renderer.last_depth_loss_ = sums.detach() / depth_n_valid;
   }
+  renderer.last_opacity_loss_ = Tensor();
   TrainStepResult out;
   out.loss = loss.detach();
   out.sq_err_sum = stats[3].detach();
   out.n_values = res.colors.numel();
   out.n_samples = renderer.last_n_samples_;
+  if (run_backward && loss.requires_grad()) loss.backward();
+  return out;
+}
+
+f2n::TrainStepResult f2n::train_step(
+  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
+  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
+  const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
+  const DepthLossOptions & depth_loss, const RaySupervision & sup)
+{
+  // (no supervision: the call without it, launch for launch)
+  if (!sup.ray_weight.defined() && !sup.alpha.defined())
+    return train_step(
+      renderer, rays_o, rays_d, emb_idx, gt_colors, var_loss_weight, dist_loss_weight, noise,
+      bg_color, run_backward, depth_target, depth_loss);
+  const int64_t n_rays = rays_o.size(0);
+  TORCH_CHECK(
+    !sup.alpha.defined() || bg_color.defined(),
+    "train_step: an alpha target needs the bg_color the render blends in");
+  const bool want_dist = dist_loss_weight != 0.f;
+  const bool want_depth = depth_target.defined() && (depth_loss.empty != 0.f ||
+                                                      depth_loss.near != 0.f ||
+                                                      depth_loss.expected != 0.f);
+  const bool want_opacity = sup.alpha.defined() && sup.opacity_weight != 0.f;
+  Tensor m, alpha;
+  if (sup.ray_weight.defined()) {
+    m = f2n::dev_f32(sup.ray_weight.detach(), "ray_weight").reshape({-1});
+    TORCH_CHECK(m.numel() == n_rays, "ray_weight must be [n_rays]");
+  }
+  if (sup.alpha.defined()) {
+    alpha = f2n::dev_f32(sup.alpha.detach(), "alpha").reshape({-1});
+    TORCH_CHECK(alpha.numel() == n_rays, "alpha must be [n_rays]");
+  }
+  // (the depth term's per-batch constants before the render, as in the call above)
+  Tensor depth_n_valid, depth_coef;
+  if (want_depth) {
+    torch::NoGradGuard no_grad;
+    const Tensor z = f2n::dev_f32(depth_target.detach(), "depth_target").reshape({-1});
+    depth_n_valid = z.gt(0.f)
+                      .logical_and(z.lt(std::numeric_limits<float>::infinity()))
+                      .sum()
+                      .to(torch::kFloat32)
+                      .clamp_min(1.f);
+    Tensor lambda = torch::empty({3}, z.options());
+    lambda.select(0, 0).fill_(depth_loss.empty);
+    lambda.select(0, 1).fill_(depth_loss.near);
+    lambda.select(0, 2).fill_(depth_loss.expected);
+    depth_coef = lambda / depth_n_valid;
+  }
+  RenderResult res = renderer.render_for_loss(
+    rays_o, rays_d, emb_idx, RunningMode::TRAIN, noise, bg_color, want_dist,
+    want_depth ? depth_target : Tensor(), want_depth ? depth_loss.eps : 0.f, want_opacity);
+  Tensor var = res.weight_var.defined() ? res.weight_var
+                                        : CustomOps::WeightVar(res.weights, res.idx_start_end);
+  if (var_loss_weight == 0.f) var = var.detach();
+  // {loss, colour, var, opacity term, weighted squared error, sum of the weights}: three launches
+  Tensor stats = f2n::train_loss_sup(
+    res.colors, gt_colors, var, res.opacity, m, alpha, alpha.defined() ? bg_color.detach() : Tensor(),
+    var_loss_weight, sup.opacity_weight);
+  Tensor loss = stats[0];
+  // the regularisers: a masked ray takes no part in them either (the per-ray terms are weighted
+  // before their reductions, which keep their divisors)
+  renderer.last_dist_loss_ = Tensor();
+  if (want_dist && res.weight_dist.numel() > 0) {
+    Tensor dist_loss = (m.defined() ? res.weight_dist * m : res.weight_dist).mean();
+    loss = loss + dist_loss_weight * dist_loss;
+    renderer.last_dist_loss_ = dist_loss.detach();
+  }
+  renderer.last_depth_loss_ = Tensor();
+  if (want_depth && res.depth_terms.numel() > 0) {
+    const Tensor sums = (m.defined() ? res.depth_terms * m.unsqueeze(1) : res.depth_terms).sum(0);
+    loss = loss + torch::dot(sums, depth_coef);
+    renderer.last_depth_loss_ = sums.detach() / depth_n_valid;
+  }
+  renderer.last_opacity_loss_ = want_opacity ? stats[3].detach() : Tensor();
+  TrainStepResult out;
+  out.loss = loss.detach();
+  out.sq_err_sum = stats[4].detach();
+  out.n_values = res.colors.numel();
+  out.n_samples = renderer.last_n_samples_;
+  out.weight_sum = stats[5].detach();
   if (run_backward && loss.requires_grad()) loss.backward();
   return out;
 }

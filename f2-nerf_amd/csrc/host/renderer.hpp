@@ -80,6 +80,10 @@ struct RenderResult
   // RendererOptions::normals only: N_r = sum_k w_k n^_k over the kept samples (f2n_ray_normals),
   // [n_rays, 3] in the caller's order, detached, not renormalised; undefined when the option is off
   Tensor normals;
+  // Renderer::render_for_loss with want_opacity only: FlexOps::Sum of the kept samples' weights,
+  // [n_rays] in the caller's order, on every route (1 - the transmittance left behind the last kept
+  // sample, to rounding), with the gradient going to the weights; undefined otherwise
+  Tensor opacity;
 };
 
 struct RendererOptions
@@ -192,6 +196,15 @@ public:
     const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
     const Tensor & noise, const Tensor & bg_color, bool want_dist, const Tensor & depth_target,
     float depth_eps);
+  // ... and, with want_opacity, for each ray's opacity O_r = sum_k w_k over its kept samples (what an
+  // alpha target is compared with): `opacity` [n_rays] is defined on every route want_dist works on,
+  // taken with f2n_seg_sum_fwd where the weights lie; on the bucketed routes its [n_rays] result rides
+  // back with colours and depths.  The gradient goes to the weights.  Without want_opacity this is the
+  // call above exactly; colours, depths, weights and bounds keep their bits either way.
+  RenderResult render_for_loss(
+    const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
+    const Tensor & noise, const Tensor & bg_color, bool want_dist, const Tensor & depth_target,
+    float depth_eps, bool want_opacity);
 
   // The no-grad render as one kernel launch (f2n_render_rays): colours [n, 3], depths [n], last_trans
   // [n] (1 - opacity of the ray: an alpha mask) and kept [n] int32 (samples composited per ray).
@@ -264,6 +277,10 @@ public:
   // recent f2n::train_step with a depth target and a non-zero DepthLossOptions weight ([3], device,
   // detached, no host read); undefined after a step without
   Tensor last_depth_loss_;
+  // the weighted mean over the rays of (opacity - alpha)^2 in the most recent f2n::train_step with
+  // an alpha target and the rendered opacity (device scalar, detached, no host read); undefined
+  // after a step without
+  Tensor last_opacity_loss_;
 
 private:
   // Everything the routes branch on, decided once per render() call (choose_route).
@@ -285,6 +302,7 @@ private:
     // (render_dense_bucketed permutes it with them), else undefined; hand back depth_terms too
     Tensor depth_target;
     float depth_eps = 0.f;
+    bool want_opacity = false;  // render_for_loss: hand back opacity too
   };
   // What the shading pass hands to compositing: the field head's output ([n, 1] density logit of the
   // fused network, [n, 16] otherwise) and the colours [n, 3].
@@ -297,7 +315,7 @@ private:
   RenderResult render_routed(
     const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
     const Tensor & noise, const Tensor & bg_color, bool for_loss, bool want_dist,
-    const Tensor & depth_target = Tensor(), float depth_eps = 0.f);
+    const Tensor & depth_target = Tensor(), float depth_eps = 0.f, bool want_opacity = false);
   bool fused_net_applies() const;
   // f2n_render_rays -- or, by options_.one_pass_head, the head or head + tail -- into preallocated
   // outputs (rows of one chunk)
@@ -370,6 +388,9 @@ struct TrainStepResult
   Tensor sq_err_sum;  // scalar: sum over rays and channels of (pred - gt)^2
   int64_t n_values;   // n_rays * 3
   int64_t n_samples;  // surviving samples in this step
+  // RaySupervision only: the sum of the ray weights as the loss formed it (device scalar, detached;
+  // the number of rays when no weight was given); undefined without supervision
+  Tensor weight_sum;
 };
 
 // Caller indices of the rays sorted into pixel-compact bundles: the stable sort of their
@@ -413,5 +434,29 @@ TrainStepResult train_step(
   const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
   const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
   const DepthLossOptions & depth_loss);
+
+// Per-ray supervision of a masked batch (f2n::sample_masked_rays makes one).  Both tensors undefined:
+// no supervision.
+struct RaySupervision
+{
+  Tensor ray_weight;           // [n_rays] m_r: 0 drops the ray from every term; undefined = 1
+  Tensor alpha;                // [n_rays] a_r in [0, 1]: the ground truth's alpha; undefined = opaque
+  float opacity_weight = 0.f;  // lambda of mean_r m_r (O_r - a_r)^2
+};
+
+// ... with masked rays and alpha targets (f2n::train_loss_sup).  The colour target of a ray becomes
+// a gt + (1 - a) bg with the background colour the render blended in -- bg_color, which is then
+// required -- both means divide by W = sum_r m_r (1 when that is not positive; no host read), and
+//   loss = colour + var_loss_weight * var + opacity_weight * sum_r m_r (O_r - a_r)^2 / W
+// with O_r the ray's rendered opacity (RenderResult::opacity; its mean term is left in
+// Renderer::last_opacity_loss_).  The distortion and depth terms are weighted by m_r as well, before
+// their reductions, which keep their divisors (n_rays, n_valid): a masked ray regularises nothing.
+// sq_err_sum is the weighted sum, weight_sum is sum_r m_r.  With ray_weight and alpha both undefined
+// this is the call above, launch for launch and bit for bit, whatever opacity_weight says.
+TrainStepResult train_step(
+  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
+  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
+  const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
+  const DepthLossOptions & depth_loss, const RaySupervision & sup);
 
 }  // namespace f2n

@@ -994,6 +994,70 @@ int f2n_loss_fwd(
   const float * colors, const float * gt, const float * var, int n_rays, float var_weight,
   float * d_colors, float * d_var, float * partial, float * out4, void * stream);
 
+/* The same loss with per-ray weights and alpha targets (masked training; the sky / segmentation loss
+ * of Urban Radiance Fields, Rematas et al., CVPR 2022, section 4.3, as a squared error).  The
+ * reference has NO such loss: src/main_functions/train_manager.cpp:78-96 averages over every ray of
+ * the batch.  This entry stands beside f2n_loss_fwd, which does not change.  Per-ray inputs, each
+ * nullable:
+ *   ray_weight [n_rays] m_r      null: 1 everywhere
+ *   alpha      [n_rays] a_r      null: no alpha handling
+ *   opacity    [n_rays] O_r      the rendered sum of weights; required when alpha is given and
+ *                                opacity_weight != 0
+ *   bg         [n_rays, 3]       the background the render blended in; required with alpha
+ * With W = sum_r m_r, and W = 1 when that sum is not positive:
+ *   gt'    = a gt + (1 - a) bg                                  (alpha given; else gt' = gt)
+ *   colour = sum_r m_r sum_c sqrt((C - gt')^2 + 1e-4) / (3 W)
+ *   var    = sum_r m_r sqrt(var_r + 1e-2) / W
+ *   opac   = sum_r m_r (O_r - a_r)^2 / W                        (alpha and opacity given; else 0)
+ *   loss   = colour + var_weight var + opacity_weight opac
+ *   out6   = {loss, colour, var, opac, sum_r m_r sum_c (C - gt')^2, sum_r m_r}
+ * out6[5] is the sum as it came out (0 when every ray is masked), not the divisor W.  An a_r = 0 ray
+ * (sky) has the background itself as its colour target, so the colour term does not fight the
+ * opacity term, which pulls O_r to 0; the squared error stays bounded where O reaches 0 or 1.
+ * Writes the gradients of loss w.r.t. colors [n_rays, 3], var [n_rays] and, when alpha and opacity
+ * are given, opacity [n_rays] (d_opacity is required then, ignored otherwise); gt, alpha, bg and
+ * ray_weight get none.  A ray with m_r == 0 is not read beyond its weight: its terms and gradients
+ * are exactly +0 whatever its colour holds.  partial: scratch of f2n_loss_sup_workspace_floats(n_rays)
+ * floats.  Three launches (partials, tree, the 1 / W scaling of the gradients), no host read, no
+ * atomics: deterministic.  The evaluation order is fixed in the header comment of loss_sup.hip.
+ * A null among colors, gt, var, d_colors, d_var, partial, out6, a missing bg / opacity / d_opacity as
+ * above, or n_rays <= 0: F2N_E_INVALID_ARG before any HIP work. */
+int64_t f2n_loss_sup_workspace_floats(int n_rays);
+int f2n_loss_sup_fwd(
+  const float * colors, const float * gt, const float * var, const float * ray_weight,
+  const float * alpha, const float * opacity, const float * bg, int n_rays, float var_weight,
+  float opacity_weight, float * d_colors, float * d_var, float * d_opacity, float * partial,
+  float * out6, void * stream);
+
+/* ------------------------------------------------------------------ pixel masks --------------- */
+
+/* Per-pixel validity masks of a set of E images of h x w pixels, as bits, and the training-batch
+ * draw that only lands on valid pixels.  The reference has neither: Dataset::sample_random_rays --
+ * src/dataset.cpp:150-171 -- draws (camera, row, col) with three randint calls over the whole image.
+ *   f2n_mask_pack: mask [E, h, w] u8 (non-zero = valid) -> words [f2n_mask_words(E, h, w)] u32.
+ *     Global pixel g = (e*h + i)*w + j is bit (g & 31) of word (g >> 5); unused bits of the last word
+ *     are zero.  count: one int64 on the device, the number of valid pixels.  partial: scratch of
+ *     f2n_mask_pack_workspace_words(E, h, w) u32.  One lane per pixel, a 64-lane ballot is two words;
+ *     integer sums in a fixed tree; no atomics.
+ *   f2n_draw_pixels_masked: n rays, one lane each.  Attempt a = 0 .. attempts-1 of ray r takes the
+ *     four words (x0, x1, x2, x3) of Philox4x32-10 with key (seed_lo, seed_hi) and counter (r, a, 0, 0)
+ *     (written out in full in the header comment of pixel_mask.hip), cam = mulhi(x0, E),
+ *     i = mulhi(x1, h), j = mulhi(x2, w); the first attempt whose bit is set is kept.
+ *       cam [n] i32, ij [n, 2] i32 (row, col), tries [n] i32: the attempts used, 1 .. attempts, or 0
+ *       when every attempt missed -- cam and ij then hold the last attempt.
+ *     Uniform over the valid pixels of the whole set (the camera is redrawn with the pixel); with an
+ *     all-ones mask uniform over cameras and pixels, as src/dataset.cpp:150-171.
+ * E, h, w <= 0 or E*h*w >= 2^36: the two size queries answer 0.  A null pointer, such sizes, n < 0 or
+ * attempts outside 1 .. 64: F2N_E_INVALID_ARG before any HIP work; n == 0: F2N_OK. */
+int64_t f2n_mask_words(int E, int h, int w);
+int64_t f2n_mask_pack_workspace_words(int E, int h, int w);
+int f2n_mask_pack(
+  const uint8_t * mask, int E, int h, int w, uint32_t * words, int64_t * count, uint32_t * partial,
+  void * stream);
+int f2n_draw_pixels_masked(
+  const uint32_t * bits, int E, int h, int w, uint32_t seed_lo, uint32_t seed_hi, int attempts,
+  int32_t * cam, int32_t * ij, int32_t * tries, int n, void * stream);
+
 /* ------------------------------------------------------------------ localiser ----------------- */
 
 /* The particle loop of Localizer::optimize_pose_by_random_search -- src/localizer.cpp:88-118 (per
