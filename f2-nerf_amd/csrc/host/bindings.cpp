@@ -4,6 +4,7 @@
 #include <torch/extension.h>
 
 #include "depth_targets.hpp"
+#include "error_map.hpp"
 #include "fused_adam.hpp"
 #include "hash_3d_anchored.hpp"
 #include "kernel_timer.hpp"
@@ -248,6 +249,87 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     "sample_random_rays restricted to the mask's valid pixels: dict of rays_o, rays_d, gt | None, "
     "alpha | None (images with four channels), cam, ray_weight (0 where every attempt missed), ij, "
     "tries; see f2n::sample_masked_rays");
+  py::class_<f2n::ErrorMapOptions>(m, "ErrorMapOptions")
+    .def(
+      py::init([](int gh, int gw, float decay, float uniform_fraction, int attempts,
+                  float init_value) {
+        return f2n::ErrorMapOptions{gh, gw, decay, uniform_fraction, attempts, init_value};
+      }),
+      py::arg("gh") = 32, py::arg("gw") = 32, py::arg("decay") = 0.95f,
+      py::arg("uniform_fraction") = 0.1f, py::arg("attempts") = 32, py::arg("init_value") = 1.f,
+      "cells per image, the weight of the old value in update(), the share of uniformly drawn "
+      "rays, attempts per ray and the value every cell starts at")
+    .def_readwrite("gh", &f2n::ErrorMapOptions::gh)
+    .def_readwrite("gw", &f2n::ErrorMapOptions::gw)
+    .def_readwrite("decay", &f2n::ErrorMapOptions::decay)
+    .def_readwrite("uniform_fraction", &f2n::ErrorMapOptions::uniform_fraction)
+    .def_readwrite("attempts", &f2n::ErrorMapOptions::attempts)
+    .def_readwrite("init_value", &f2n::ErrorMapOptions::init_value);
+  py::class_<f2n::ErrorMap>(m, "ErrorMap")
+    .def(
+      py::init([](int64_t E, int64_t h, int64_t w, const f2n::ErrorMapOptions & options,
+                  const f2n::PixelMask * mask) {
+        if (mask) {
+          TORCH_CHECK(
+            mask->E == E && mask->h == h && mask->w == w, "the mask and E, h, w disagree");
+          return f2n::ErrorMap(*mask, options);
+        }
+        return f2n::ErrorMap(E, h, w, options, torch::Device(torch::kCUDA));
+      }),
+      py::arg("E"), py::arg("h"), py::arg("w"), py::arg("options") = f2n::ErrorMapOptions(),
+      py::arg("mask") = py::none(),
+      "per-image error map of E images of h x w pixels, on the GPU; mask: a PixelMask or None")
+    .def(
+      "accumulate",
+      [](f2n::ErrorMap & map, const Tensor & colors, const Tensor & gt, const Tensor & cam,
+         const Tensor & ij, const c10::optional<Tensor> & ray_weight,
+         const c10::optional<Tensor> & alpha, const c10::optional<Tensor> & bg) {
+        map.accumulate(colors, gt, cam, ij, opt_tensor(ray_weight), opt_tensor(alpha), opt_tensor(bg));
+      },
+      py::arg("colors"), py::arg("gt"), py::arg("cam"), py::arg("ij"),
+      py::arg("ray_weight") = py::none(), py::arg("alpha") = py::none(), py::arg("bg") = py::none(),
+      "f2n_error_map_accum: the raw errors of one rendered batch into the accumulators")
+    .def("update", &f2n::ErrorMap::update, "f2n_error_map_apply, then f2n_error_cdf")
+    .def(
+      "draw",
+      [](const f2n::ErrorMap & map, int64_t n, uint64_t seed) {
+        f2n::GuidedDraw d = map.draw(n, seed);
+        return py::make_tuple(d.cam, d.ij, d.tries, d.ray_weight);
+      },
+      py::arg("n"), py::arg("seed"),
+      "f2n_draw_pixels_guided -> (cam [n] i32, ij [n,2] i32, tries [n] i32, ray_weight [n] f32)")
+    .def_readwrite("options", &f2n::ErrorMap::options)
+    .def_readonly("E", &f2n::ErrorMap::E)
+    .def_readonly("h", &f2n::ErrorMap::h)
+    .def_readonly("w", &f2n::ErrorMap::w)
+    .def_readonly("n_cells", &f2n::ErrorMap::n_cells)
+    .def_readonly("value", &f2n::ErrorMap::value, "[n_cells] f32")
+    .def_readonly("counts", &f2n::ErrorMap::counts, "[n_cells] i32: valid pixels per cell")
+    .def_readonly("cdf", &f2n::ErrorMap::cdf, "[n_cells] int64 holding the uint64 prefix sums")
+    .def_readonly("acc_sum", &f2n::ErrorMap::acc_sum, "[n_cells] int64 holding the uint64 sums")
+    .def_readonly("acc_cnt", &f2n::ErrorMap::acc_cnt, "[n_cells] int32 holding the uint32 counts")
+    .def_readonly("n_valid", &f2n::ErrorMap::n_valid, "[1] int64 on the device");
+  m.def(
+    "sample_guided_rays",
+    [](const Tensor & poses, const Tensor & intr, const f2n::ErrorMap & map, int64_t n, uint64_t seed,
+       const c10::optional<Tensor> & images, const c10::optional<Tensor> & dist) {
+      f2n::MaskedBatch b =
+        f2n::sample_guided_rays(poses, intr, map, n, seed, opt_tensor(images), opt_tensor(dist));
+      py::dict d;
+      d["rays_o"] = b.rays.origins;
+      d["rays_d"] = b.rays.dirs;
+      d["gt"] = tensor_or_none(b.gt);
+      d["alpha"] = tensor_or_none(b.alpha);
+      d["cam"] = b.cam;
+      d["ray_weight"] = b.ray_weight;
+      d["ij"] = b.ij;
+      d["tries"] = b.tries;
+      return d;
+    },
+    py::arg("poses"), py::arg("intrinsics"), py::arg("map"), py::arg("batch_size"), py::arg("seed"),
+    py::arg("images") = py::none(), py::arg("dist") = py::none(),
+    "sample_masked_rays with the guided draw of an ErrorMap: the same dict, ray_weight being the "
+    "importance weight (0 where every attempt missed); see f2n::sample_guided_rays");
   m.def("ray_order", &f2n::ray_order, "caller indices of rays_d sorted into pixel-compact bundles");
   m.def("manual_seed", [](uint64_t s) { torch::manual_seed(s); });
   m.def("kernel_timer_enable", &f2n::kernel_timer_enable);
@@ -377,17 +459,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
   py::class_<f2n::RaySupervision>(m, "RaySupervision")
     .def(
       py::init([](const c10::optional<Tensor> & ray_weight, const c10::optional<Tensor> & alpha,
-                  float opacity_weight) {
-        return f2n::RaySupervision{opt_tensor(ray_weight), opt_tensor(alpha), opacity_weight};
+                  float opacity_weight, bool want_colors) {
+        return f2n::RaySupervision{
+          opt_tensor(ray_weight), opt_tensor(alpha), opacity_weight, want_colors};
       }),
       py::arg("ray_weight") = py::none(), py::arg("alpha") = py::none(),
-      py::arg("opacity_weight") = 0.f,
-      "per-ray weights [n_rays], alpha targets [n_rays] and the weight of the opacity term")
+      py::arg("opacity_weight") = 0.f, py::arg("want_colors") = false,
+      "per-ray weights [n_rays], alpha targets [n_rays], the weight of the opacity term, and "
+      "whether train_step_supervised hands the render's colours back")
     .def_property_readonly(
       "ray_weight", [](const f2n::RaySupervision & s) { return tensor_or_none(s.ray_weight); })
     .def_property_readonly(
       "alpha", [](const f2n::RaySupervision & s) { return tensor_or_none(s.alpha); })
-    .def_readwrite("opacity_weight", &f2n::RaySupervision::opacity_weight);
+    .def_readwrite("opacity_weight", &f2n::RaySupervision::opacity_weight)
+    .def_readwrite("want_colors", &f2n::RaySupervision::want_colors);
   py::class_<f2n::DepthLossOptions>(m, "DepthLossOptions")
     .def(
       py::init([](float empty, float near, float expected, float eps) {
@@ -580,6 +665,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
             r, o, d, emb_idx, gt, var_loss_weight, dist_loss_weight, opt_tensor(noise),
             opt_tensor(bg), backward, opt_tensor(depth_target), depth_loss, sup);
         }
+        if (sup.want_colors)
+          return py::make_tuple(
+            out.loss, out.sq_err_sum, out.n_values, out.n_samples, tensor_or_none(out.weight_sum),
+            out.colors);
         return py::make_tuple(
           out.loss, out.sq_err_sum, out.n_values, out.n_samples, tensor_or_none(out.weight_sum));
       },
@@ -590,7 +679,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
       py::arg("depth_loss") = f2n::DepthLossOptions(),
       "train_step with a RaySupervision (masked rays, alpha targets): (loss, sq_err_sum, n_values, "
       "n_samples, weight_sum | None).  A RaySupervision without ray_weight and alpha is train_step "
-      "itself, launch for launch; the opacity term's mean is left in last_opacity_loss")
+      "itself, launch for launch; the opacity term's mean is left in last_opacity_loss.  NOTE THE "
+      "ARITY: with sup.want_colors the tuple has a sixth element, the render's colours [n_rays, 3], "
+      "detached")
     .def("named_parameters", [](Renderer & r) { return named_params(r); })
     .def("zero_grad", [](Renderer & r) { r.zero_grad(); })
     .def(

@@ -1214,6 +1214,12 @@ std::vector<torch::optim::OptimizerParamGroup> Renderer::optim_param_groups(floa
 
 // ---- training-step harness -----------------------------------------------------------------------
 
+static f2n::TrainStepResult train_step_plain(
+  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
+  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
+  const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
+  const f2n::DepthLossOptions & depth_loss, bool want_colors);
+
 f2n::TrainStepResult f2n::train_step(
   Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
   const Tensor & gt_colors, float var_loss_weight, const Tensor & noise, const Tensor & bg_color,
@@ -1240,6 +1246,19 @@ f2n::TrainStepResult f2n::train_step(
   const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
   const DepthLossOptions & depth_loss)
 {
+  return train_step_plain(
+    renderer, rays_o, rays_d, emb_idx, gt_colors, var_loss_weight, dist_loss_weight, noise, bg_color,
+    run_backward, depth_target, depth_loss, false);
+}
+
+// the step without per-ray supervision; want_colors only keeps a detached handle of the colours
+static f2n::TrainStepResult train_step_plain(
+  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
+  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
+  const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
+  const f2n::DepthLossOptions & depth_loss, bool want_colors)
+{
+  using namespace f2n;
   // (a zero distortion weight: the term is not computed and the call is the one without it)
   const bool want_dist = dist_loss_weight != 0.f;
   // (the same rule for the depth terms: no target, or three zero weights, and nothing of them exists)
@@ -1299,6 +1318,7 @@ f2n::TrainStepResult f2n::train_step(
   out.sq_err_sum = stats[3].detach();
   out.n_values = res.colors.numel();
   out.n_samples = renderer.last_n_samples_;
+  if (want_colors) out.colors = res.colors.detach();
   if (run_backward && loss.requires_grad()) loss.backward();
   return out;
 }
@@ -1311,9 +1331,9 @@ f2n::TrainStepResult f2n::train_step(
 {
   // (no supervision: the call without it, launch for launch)
   if (!sup.ray_weight.defined() && !sup.alpha.defined())
-    return train_step(
+    return train_step_plain(
       renderer, rays_o, rays_d, emb_idx, gt_colors, var_loss_weight, dist_loss_weight, noise,
-      bg_color, run_backward, depth_target, depth_loss);
+      bg_color, run_backward, depth_target, depth_loss, sup.want_colors);
   const int64_t n_rays = rays_o.size(0);
   TORCH_CHECK(
     !sup.alpha.defined() || bg_color.defined(),
@@ -1380,6 +1400,7 @@ f2n::TrainStepResult f2n::train_step(
   out.n_values = res.colors.numel();
   out.n_samples = renderer.last_n_samples_;
   out.weight_sum = stats[5].detach();
+  if (sup.want_colors) out.colors = res.colors.detach();
   if (run_backward && loss.requires_grad()) loss.backward();
   return out;
 }

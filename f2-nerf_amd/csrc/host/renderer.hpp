@@ -391,6 +391,9 @@ struct TrainStepResult
   // RaySupervision only: the sum of the ray weights as the loss formed it (device scalar, detached;
   // the number of rays when no weight was given); undefined without supervision
   Tensor weight_sum;
+  // RaySupervision::want_colors only: the render's colours [n_rays, 3], detached (what
+  // ErrorMap::accumulate takes); undefined otherwise
+  Tensor colors;
 };
 
 // Caller indices of the rays sorted into pixel-compact bundles: the stable sort of their
@@ -442,6 +445,9 @@ struct RaySupervision
   Tensor ray_weight;           // [n_rays] m_r: 0 drops the ray from every term; undefined = 1
   Tensor alpha;                // [n_rays] a_r in [0, 1]: the ground truth's alpha; undefined = opaque
   float opacity_weight = 0.f;  // lambda of mean_r m_r (O_r - a_r)^2
+  // hand the render's colours back in TrainStepResult::colors (a detached view of what the loss
+  // read: no launch, and nothing else of the step changes)
+  bool want_colors = false;
 };
 
 // ... with masked rays and alpha targets (f2n::train_loss_sup).  The colour target of a ray becomes
@@ -452,7 +458,8 @@ struct RaySupervision
 // Renderer::last_opacity_loss_).  The distortion and depth terms are weighted by m_r as well, before
 // their reductions, which keep their divisors (n_rays, n_valid): a masked ray regularises nothing.
 // sq_err_sum is the weighted sum, weight_sum is sum_r m_r.  With ray_weight and alpha both undefined
-// this is the call above, launch for launch and bit for bit, whatever opacity_weight says.
+// this is the call above, launch for launch and bit for bit, whatever opacity_weight says
+// (want_colors then still fills TrainStepResult::colors, which costs no launch).
 TrainStepResult train_step(
   Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
   const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,

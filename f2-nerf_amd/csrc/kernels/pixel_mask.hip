@@ -40,6 +40,7 @@
 // An attempt is ~40 integer instructions and one 4-byte load, so the draw stays small beside the
 // render it feeds; flattening the divergence (per-image alias tables) is not attempted here.
 #include "common.hiph"
+#include "philox.hiph"
 
 namespace
 {
@@ -91,31 +92,6 @@ __global__ __launch_bounds__(kMaskBlock) void mask_count_kernel(
     __syncthreads();
   }
   if (threadIdx.x == 0) count[0] = tree[0];
-}
-
-struct Philox4
-{
-  uint32_t x0, x1, x2, x3;
-};
-
-__device__ __forceinline__ Philox4 philox4x32_10(
-  uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1)
-{
-#pragma unroll
-  for (int n = 0; n < 10; n++) {
-    if (n > 0) {
-      k0 += 0x9E3779B9u;
-      k1 += 0xBB67AE85u;
-    }
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-    c0 = n0;
-    c1 = lo1;
-    c2 = n2;
-    c3 = lo0;
-  }
-  return {c0, c1, c2, c3};
 }
 
 __global__ __launch_bounds__(kMaskBlock) void draw_pixels_masked_kernel(

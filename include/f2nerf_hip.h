@@ -1058,6 +1058,75 @@ int f2n_draw_pixels_masked(
   const uint32_t * bits, int E, int h, int w, uint32_t seed_lo, uint32_t seed_hi, int attempts,
   int32_t * cam, int32_t * ij, int32_t * tries, int n, void * stream);
 
+/* ------------------------------------------------------------------ error map ----------------- */
+
+/* Error-guided ray sampling: a per-image grid of running colour errors, its CDF, and a batch draw
+ * that spends rays where the error is (the error map of instant-ngp, Mueller et al., SIGGRAPH 2022).
+ * The reference has none of it: Dataset::sample_random_rays -- src/dataset.cpp:150-171 -- draws
+ * uniformly over pixels.  Geometry, all integers: E images of h x w pixels, gh x gw cells per image,
+ * 1 <= gh <= h, 1 <= gw <= w; pixel (e, i, j) lies in cell c = (e*gh + (i*gh)/h)*gw + (j*gw)/w, and
+ * cell row a covers pixel rows ceil(a*h/gh) .. ceil((a+1)*h/gh) - 1 (columns alike).  Limits:
+ * n_cells = E*gh*gw < 2^24, h*w < 2^31, E*h*w < 2^36.  Every entry below answers F2N_E_INVALID_ARG
+ * before any HIP work for a null among its required pointers or sizes outside these limits; n == 0 is
+ * F2N_OK where there is an n, and excuses no bad argument.  The evaluation orders are fixed in the
+ * header comment of error_map.hip.
+ *
+ * Valid pixels per cell, beside src/dataset.cpp:150-171: counts [n_cells] i32 from the packed bits of
+ * f2n_mask_pack; bits null = no mask, the closed form rows x cols.  One wavefront per cell, no
+ * atomics. */
+int f2n_mask_cell_counts(
+  const uint32_t * bits, int E, int h, int w, int gh, int gw, int32_t * counts, void * stream);
+
+/* The errors of one rendered batch into the accumulators, beside src/dataset.cpp:150-171.  Per ray,
+ * in f64 on the f32 inputs: e_r = sum_c (C - gt')^2 with gt' = a gt + (1 - a) bg when alpha is given
+ * (bg is then required), as in f2n_loss_sup_fwd.  A ray is skipped when ray_weight is given and its
+ * m_r == 0, when e_r is not finite, and when cam / ij lie outside the set (no out-of-bounds access
+ * whatever they hold).  Otherwise llrint(min(e_r, 4) 2^20) is added to acc_sum [n_cells] u64 and 1 to
+ * acc_cnt [n_cells] u32 of the ray's cell: integer atomics, so the sums do not depend on order.  The
+ * raw error is recorded, never the error times an importance weight.
+ *   colors, gt [n, 3]; alpha, ray_weight [n] nullable; bg [n, 3]; cam [n] i32; ij [n, 2] i32 */
+int f2n_error_map_accum(
+  const float * colors, const float * gt, const float * alpha, const float * bg,
+  const float * ray_weight, const int32_t * cam, const int32_t * ij, int n, int E, int h, int w,
+  int gh, int gw, uint64_t * acc_sum, uint32_t * acc_cnt, void * stream);
+
+/* Fold the accumulators into the map, beside src/dataset.cpp:150-171.  Per cell with cnt > 0:
+ * value = f32(decay value + (1 - decay) sum / (2^20 cnt)) in f64; a cell no ray hit keeps its value;
+ * every accumulator is left at zero.  decay in [0, 1] (NaN is invalid); 1 <= n_cells < 2^24. */
+int f2n_error_map_apply(
+  float * value, uint64_t * acc_sum, uint32_t * acc_cnt, int n_cells, float decay, void * stream);
+
+/* The map's CDF, beside src/dataset.cpp:150-171.  mass[c] = clamp(llrint(value[c] 2^16), 1, 2^24)
+ * counts[c] as u64 (a non-finite value counts as the floor 1; a negative count as 0); cdf [n_cells]
+ * u64 is the inclusive prefix sum, below 2^60.  partial: scratch of
+ * f2n_error_cdf_workspace_words(n_cells) u64 words (0 for n_cells outside 1 .. 2^24 - 1).  Three
+ * launches -- tile sums, one workgroup over them, add-back -- and no workgroup waits on another. */
+int64_t f2n_error_cdf_workspace_words(int n_cells);
+int f2n_error_cdf(
+  const float * value, const int32_t * counts, int n_cells, uint64_t * cdf, uint64_t * partial,
+  void * stream);
+
+/* The batch draw that follows the map, beside src/dataset.cpp:150-171 and f2n_draw_pixels_masked.
+ * One lane per ray r; T = llrint(uniform_fraction 2^32), u = T / 2^32, uniform_fraction in [0, 1];
+ * (x0 .. x3) = Philox4x32-10 with key (seed_lo, seed_hi) and counter (r, 0, 0, 0);
+ * total = cdf[n_cells - 1].
+ *   x3 < T (as u64) or total == 0: the masked draw exactly, attempts a with counter (r, a, 0, 0).
+ *   else: t = mulhi64((x0 << 32) | x1, total), the cell is the first c with cdf[c] > t, and attempt a
+ *     with counter (r, a, 1, 0) takes i = i0 + mulhi(y0, rows), j = j0 + mulhi(y1, cols) in that cell.
+ *   The first attempt whose bit is set is kept; bits null = every pixel valid.
+ *   cam, ij, tries as f2n_draw_pixels_masked (tries 0: every attempt missed, the last one stays).
+ *   ray_weight [n] f32 = 1 / ((1 - u) q_c N / total + u) in f64, rounded once; q_c the quantised
+ *     value of the kept pixel's cell, N = n_valid[0]; 0 where tries == 0.  The uniform pdf over the
+ *     pdf used: expectation 1 under the draw, never above 1 / u, exactly 1 at u = 1 -- where cam, ij
+ *     and tries equal f2n_draw_pixels_masked's bit for bit.
+ * n_valid: one int64 on the device (PixelMask's count, or E*h*w without a mask); never read on the
+ * host.  counts and value are those the cdf was made from.  attempts in 1 .. 64. */
+int f2n_draw_pixels_guided(
+  const uint32_t * bits, const int32_t * counts, const float * value, const uint64_t * cdf,
+  const int64_t * n_valid, int E, int h, int w, int gh, int gw, uint32_t seed_lo, uint32_t seed_hi,
+  int attempts, float uniform_fraction, int32_t * cam, int32_t * ij, int32_t * tries,
+  float * ray_weight, int n, void * stream);
+
 /* ------------------------------------------------------------------ localiser ----------------- */
 
 /* The particle loop of Localizer::optimize_pose_by_random_search -- src/localizer.cpp:88-118 (per
