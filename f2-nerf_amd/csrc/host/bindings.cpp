@@ -4,6 +4,7 @@
 #include <torch/extension.h>
 
 #include "depth_targets.hpp"
+#include "env_map.hpp"
 #include "error_map.hpp"
 #include "fused_adam.hpp"
 #include "hash_3d_anchored.hpp"
@@ -183,6 +184,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
        const Tensor & d_out) { return pose_compose_bwd(base, delta, opt_tensor(fixed), d_out); },
     py::arg("base"), py::arg("delta"), py::arg("fixed"), py::arg("d_out"),
     "f2n_pose_compose_bwd: d_out [E,3,4] -> d_delta [E,6]");
+  m.def(
+    "envmap_query", &f2n::envmap_query, py::arg("dirs"), py::arg("texture"),
+    "f2n_envmap_fwd: dirs [n,3], texture [6,R,R,3] logits -> bg [n,3]; no autograd");
+  m.def(
+    "envmap_bwd", &f2n::envmap_bwd, py::arg("dirs"), py::arg("bg"), py::arg("d_bg"), py::arg("R"),
+    py::arg("acc"), py::arg("flags"),
+    "f2n_envmap_bwd: adds d_bg's fixed-point contributions to acc (int64 [6*R*R*3]), ors into "
+    "flags (int32 [1])");
+  m.def(
+    "envmap_grad_apply", &f2n::envmap_grad_apply, py::arg("acc"), py::arg("R"), py::arg("d_tex"),
+    py::arg("accumulate") = false,
+    "f2n_envmap_grad_apply: d_tex (+)= acc * 2^-48, acc = 0");
   m.def(
     "project_points",
     [](const Tensor & points, const Tensor & pose, const Tensor & intr,
@@ -459,20 +472,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
   py::class_<f2n::RaySupervision>(m, "RaySupervision")
     .def(
       py::init([](const c10::optional<Tensor> & ray_weight, const c10::optional<Tensor> & alpha,
-                  float opacity_weight, bool want_colors) {
+                  float opacity_weight, bool want_colors, bool composite_target) {
         return f2n::RaySupervision{
-          opt_tensor(ray_weight), opt_tensor(alpha), opacity_weight, want_colors};
+          opt_tensor(ray_weight), opt_tensor(alpha), opacity_weight, want_colors, composite_target};
       }),
       py::arg("ray_weight") = py::none(), py::arg("alpha") = py::none(),
       py::arg("opacity_weight") = 0.f, py::arg("want_colors") = false,
-      "per-ray weights [n_rays], alpha targets [n_rays], the weight of the opacity term, and "
-      "whether train_step_supervised hands the render's colours back")
+      py::arg("composite_target") = true,
+      "per-ray weights [n_rays], alpha targets [n_rays], the weight of the opacity term, whether "
+      "train_step_supervised hands the render's colours back, and whether the colour target is "
+      "a gt + (1 - a) bg (True) or gt itself with alpha feeding the opacity term alone (False: what "
+      "a learned background needs)")
     .def_property_readonly(
       "ray_weight", [](const f2n::RaySupervision & s) { return tensor_or_none(s.ray_weight); })
     .def_property_readonly(
       "alpha", [](const f2n::RaySupervision & s) { return tensor_or_none(s.alpha); })
     .def_readwrite("opacity_weight", &f2n::RaySupervision::opacity_weight)
-    .def_readwrite("want_colors", &f2n::RaySupervision::want_colors);
+    .def_readwrite("want_colors", &f2n::RaySupervision::want_colors)
+    .def_readwrite("composite_target", &f2n::RaySupervision::composite_target);
   py::class_<f2n::DepthLossOptions>(m, "DepthLossOptions")
     .def(
       py::init([](float empty, float near, float expected, float eps) {
@@ -696,6 +713,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
       [](Renderer & r, std::shared_ptr<OccupancyGrid> g) { r.set_occupancy(std::move(g)); },
       py::arg("grid").none(true), "attach an occupancy grid (None = off): see Renderer::set_occupancy")
     .def_property_readonly("occupancy", [](Renderer & r) { return r.occupancy(); })
+    .def(
+      "set_background",
+      [](Renderer & r, std::shared_ptr<f2n::EnvMap> e) { r.set_background(std::move(e)); },
+      py::arg("env").none(true),
+      "attach a learned background (None = off): see Renderer::set_background")
+    .def_property_readonly("background", [](Renderer & r) { return r.background(); })
     .def("set_fused", [](Renderer & r, bool f) { r.options_.fused = f; })
     .def("set_fused_shade", [](Renderer & r, bool f) { r.options_.fused_shade = f; })
     .def("set_dense_first_pass", [](Renderer & r, int m) { r.options_.dense_first_pass = m; })
@@ -942,6 +965,38 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def("infer_width", &Localizer::infer_width)
     .def_property_readonly("renderer", &Localizer::renderer)
     .def_property_readonly("intrinsic", [](Localizer & l) { return l.intrinsic(); });
+
+  // ---- EnvMap ------------------------------------------------------------------------------------
+  py::class_<f2n::EnvMap, std::shared_ptr<f2n::EnvMap>>(m, "EnvMap")
+    .def(py::init([](int64_t resolution, const std::string & dev) {
+           return std::make_shared<f2n::EnvMap>(resolution, parse_device(dev));
+         }),
+         py::arg("resolution"), py::arg("device") = "",
+         "a learned background: a cube map [6,R,R,3] of colour logits, zeros; see env_map.hpp")
+    .def("query", &f2n::EnvMap::query, py::arg("dirs"),
+         "bg [n,3] of dirs [n,3], differentiable in the texture")
+    .def("flags", &f2n::EnvMap::flags, py::call_guard<py::gil_scoped_release>(),
+         "bit 0: a non-finite gradient was dropped, bit 1: a contribution was capped; a host read "
+         "that resets the flags")
+    .def(
+      "make_adam",
+      [](f2n::EnvMap & e, float lr) {
+        AdamHandle h;
+        h.opt = std::make_shared<torch::optim::Adam>(e.optim_param_groups(lr));
+        return h;
+      },
+      "torch::optim::Adam over optim_param_groups(lr)")
+    .def("zero_grad", [](f2n::EnvMap & e) { e.zero_grad(); })
+    .def_property_readonly("resolution", &f2n::EnvMap::resolution)
+    .def_property_readonly("texture", [](f2n::EnvMap & e) { return e.texture_; })
+    .def_property_readonly("acc", [](f2n::EnvMap & e) { return e.acc_; },
+                           "int64 [6*R*R*3]: the fixed-point sums, zero between backwards")
+    .def(
+      "save",
+      [](std::shared_ptr<f2n::EnvMap> e, const std::string & path) { torch::save(e, path); })
+    .def(
+      "load",
+      [](std::shared_ptr<f2n::EnvMap> e, const std::string & path) { torch::load(e, path); });
 
   // ---- PoseRefiner -------------------------------------------------------------------------------
   py::class_<PoseRefiner, std::shared_ptr<PoseRefiner>>(m, "PoseRefiner")

@@ -348,9 +348,7 @@ RenderResult Renderer::render_routed(
   // dense route hands it to its sampler raw, every other route gets draw_noise's two passes over it
   Tensor raw = noise_in.defined() ? Tensor()
                                   : pts_sampler_->draw_noise_raw(n_rays, mode, rays_o.device());
-  Tensor bg_color = bg_in.defined() ? bg_in
-                    : (mode == RunningMode::TRAIN) ? torch::rand({n_rays, 3}, fopt)
-                                                   : torch::ones({n_rays, 3}, fopt) * .5f;
+  Tensor bg_color = background_or_default(bg_in, rays_d, mode, n_rays);
   if (n_rays <= 0) {
     record_kept(0);
     RenderResult none{
@@ -378,6 +376,16 @@ RenderResult Renderer::render_routed(
                        : render_fused(rays_o, rays_d, emb_idx, mode, noise, bg_color, route);
   if (options_.check_finite) CHECK(std::isfinite(res.colors.mean().item<float>()));
   return res;
+}
+
+Tensor Renderer::background_or_default(
+  const Tensor & bg_in, const Tensor & rays_d, RunningMode mode, int64_t n_rays) const
+{
+  if (bg_in.defined()) return bg_in;
+  if (background_) return background_->query(rays_d);
+  const auto fopt = f2n::float_on(rays_d.device());
+  return (mode == RunningMode::TRAIN) ? torch::rand({n_rays, 3}, fopt)
+                                      : torch::ones({n_rays, 3}, fopt) * .5f;
 }
 
 bool Renderer::fused_net_applies() const
@@ -1063,9 +1071,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> Renderer::render_rays(
   const auto fopt = f2n::float_on(rays_o.device());
   Tensor noise = noise_in.defined() ? noise_in
                                     : pts_sampler_->draw_noise(n_rays, mode, rays_o.device());
-  Tensor bg_color = bg_in.defined() ? bg_in
-                    : (mode == RunningMode::TRAIN) ? torch::rand({n_rays, 3}, fopt)
-                                                   : torch::ones({n_rays, 3}, fopt) * .5f;
+  Tensor bg_color = background_or_default(bg_in, rays_d, mode, n_rays);
   Tensor colors = torch::empty({n_rays, 3}, fopt), depths = torch::empty({n_rays}, fopt);
   Tensor last_trans = torch::empty({n_rays}, fopt);
   Tensor kept = torch::empty({n_rays}, f2n::int_on(rays_o.device()));
@@ -1088,13 +1094,17 @@ std::tuple<Tensor, Tensor> Renderer::render_all_rays(
     Tensor colors = torch::empty({n_rays, 3}, fopt), depths = torch::empty({n_rays, 1}, fopt);
     Tensor last_trans = torch::empty({n_rays}, fopt);
     Tensor kept = torch::empty({n_rays}, f2n::int_on(rays_d.device()));
-    const Tensor bg = torch::ones({std::min<int64_t>(batch_size, n_rays), 3}, fopt) * .5f;
+    // (an attached background is looked up per chunk, one launch each; without one the constant)
+    const Tensor bg = background_
+                        ? Tensor()
+                        : torch::ones({std::min<int64_t>(batch_size, n_rays), 3}, fopt) * .5f;
     for (int64_t lo = 0; lo < n_rays; lo += batch_size) {
       const int64_t hi = std::min<int64_t>(lo + batch_size, n_rays);
       render_rays_into(
         rays_o.slice(0, lo, hi), rays_d.slice(0, lo, hi), Tensor(), RunningMode::VALIDATE, Tensor(),
-        bg.slice(0, 0, hi - lo), colors.slice(0, lo, hi), depths.slice(0, lo, hi),
-        last_trans.slice(0, lo, hi), kept.slice(0, lo, hi));
+        background_ ? background_->query(rays_d.slice(0, lo, hi)) : bg.slice(0, 0, hi - lo),
+        colors.slice(0, lo, hi), depths.slice(0, lo, hi), last_trans.slice(0, lo, hi),
+        kept.slice(0, lo, hi));
     }
     return {colors, depths};
   }
@@ -1335,8 +1345,10 @@ f2n::TrainStepResult f2n::train_step(
       renderer, rays_o, rays_d, emb_idx, gt_colors, var_loss_weight, dist_loss_weight, noise,
       bg_color, run_backward, depth_target, depth_loss, sup.want_colors);
   const int64_t n_rays = rays_o.size(0);
+  // composite_target off: the colour target is gt itself and alpha feeds the opacity term alone
+  const bool plain_target = sup.alpha.defined() && !sup.composite_target;
   TORCH_CHECK(
-    !sup.alpha.defined() || bg_color.defined(),
+    !sup.alpha.defined() || plain_target || bg_color.defined(),
     "train_step: an alpha target needs the bg_color the render blends in");
   const bool want_dist = dist_loss_weight != 0.f;
   const bool want_depth = depth_target.defined() && (depth_loss.empty != 0.f ||
@@ -1375,10 +1387,27 @@ f2n::TrainStepResult f2n::train_step(
                                         : CustomOps::WeightVar(res.weights, res.idx_start_end);
   if (var_loss_weight == 0.f) var = var.detach();
   // {loss, colour, var, opacity term, weighted squared error, sum of the weights}: three launches
-  Tensor stats = f2n::train_loss_sup(
-    res.colors, gt_colors, var, res.opacity, m, alpha, alpha.defined() ? bg_color.detach() : Tensor(),
-    var_loss_weight, sup.opacity_weight);
+  Tensor stats =
+    plain_target
+      ? f2n::train_loss_sup(
+          res.colors, gt_colors, var, Tensor(), m, Tensor(), Tensor(), var_loss_weight, 0.f)
+      : f2n::train_loss_sup(
+          res.colors, gt_colors, var, res.opacity, m, alpha,
+          alpha.defined() ? bg_color.detach() : Tensor(), var_loss_weight, sup.opacity_weight);
   Tensor loss = stats[0];
+  // ... and the opacity term beside it, from the entry's own device scalar: W = sum m (1 when that
+  // is not positive), d = O - a where m != 0 and exactly 0 elsewhere (the term and the opacity's
+  // gradient of a masked ray are exact zeros), opac = sum m d^2 / W.  No host read.
+  Tensor opacity_term;
+  if (plain_target && want_opacity) {
+    Tensor d = res.opacity - alpha;
+    if (m.defined()) d = d.masked_fill(m.eq(0.f), 0.f);
+    const Tensor sq = d * d;
+    const Tensor sum_m = stats[5].detach();
+    const Tensor W = torch::where(sum_m.gt(0.f), sum_m, torch::ones_like(sum_m));
+    opacity_term = (m.defined() ? m * sq : sq).sum() / W;
+    loss = loss + sup.opacity_weight * opacity_term;
+  }
   // the regularisers: a masked ray takes no part in them either (the per-ray terms are weighted
   // before their reductions, which keep their divisors)
   renderer.last_dist_loss_ = Tensor();
@@ -1393,7 +1422,9 @@ f2n::TrainStepResult f2n::train_step(
     loss = loss + torch::dot(sums, depth_coef);
     renderer.last_depth_loss_ = sums.detach() / depth_n_valid;
   }
-  renderer.last_opacity_loss_ = want_opacity ? stats[3].detach() : Tensor();
+  renderer.last_opacity_loss_ = !want_opacity  ? Tensor()
+                                : plain_target ? opacity_term.detach()
+                                               : stats[3].detach();
   TrainStepResult out;
   out.loss = loss.detach();
   out.sq_err_sum = stats[4].detach();

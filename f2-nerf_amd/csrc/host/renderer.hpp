@@ -32,6 +32,7 @@
 #include <utility>
 #include <vector>
 
+#include "env_map.hpp"
 #include "hash_3d_anchored.hpp"
 #include "occupancy_grid.hpp"
 #include "points_sampler.hpp"
@@ -251,6 +252,17 @@ public:
   void set_occupancy(std::shared_ptr<OccupancyGrid> grid) { occupancy_ = std::move(grid); }
   const std::shared_ptr<OccupancyGrid> & occupancy() const { return occupancy_; }
 
+  // A learned background: null = off (the default; same routes, same kernels, same bits as without
+  // this call).  Attached, every render that is handed no bg_color blends background()->query(rays_d)
+  // -- in the caller's ray order, in every mode -- where it would have blended rand (TRAIN) or 0.5:
+  // render(), render_for_loss(), render_rays() and, through them, render_all_rays / render_image, their
+  // _with_normals forms, the one-pass path and the Localizer.  A caller-supplied bg_color always wins.
+  // Under grad mode the query carries a gradient to the texture, so choose_route keeps the dense
+  // route in the caller's order and off its lean form (the known price).  Not a
+  // parameter or buffer, like the occupancy grid: renderer.pt keeps the reference's layout.
+  void set_background(std::shared_ptr<f2n::EnvMap> env) { background_ = std::move(env); }
+  const std::shared_ptr<f2n::EnvMap> & background() const { return background_; }
+
   RendererOptions options_;
   std::shared_ptr<PtsSampler> pts_sampler_;
   std::shared_ptr<Hash3DAnchored> scene_field_;
@@ -373,7 +385,12 @@ private:
   // n_all < 0: the kept fraction (what the adaptive first-pass choice reads) keeps its value
   void record_kept(int64_t n_kept, int64_t n_all = -1);
 
+  // bg_in when defined, else the attached map's colours of rays_d, else rand (TRAIN) / 0.5
+  Tensor background_or_default(
+    const Tensor & bg_in, const Tensor & rays_d, RunningMode mode, int64_t n_rays) const;
+
   std::shared_ptr<OccupancyGrid> occupancy_;
+  std::shared_ptr<f2n::EnvMap> background_;
 };
 
 namespace f2n
@@ -448,6 +465,11 @@ struct RaySupervision
   // hand the render's colours back in TrainStepResult::colors (a detached view of what the loss
   // read: no launch, and nothing else of the step changes)
   bool want_colors = false;
+  // true: the colour target of a ray is a gt + (1 - a) bg (a sky ray's target is the background the
+  // render blended in).  false: the colour target is gt unchanged and alpha feeds only the opacity
+  // term -- what a learned background (Renderer::set_background) needs, or its texture never sees
+  // the image; bg_color may then be left undefined.
+  bool composite_target = true;
 };
 
 // ... with masked rays and alpha targets (f2n::train_loss_sup).  The colour target of a ray becomes
@@ -460,6 +482,11 @@ struct RaySupervision
 // sq_err_sum is the weighted sum, weight_sum is sum_r m_r.  With ray_weight and alpha both undefined
 // this is the call above, launch for launch and bit for bit, whatever opacity_weight says
 // (want_colors then still fills TrainStepResult::colors, which costs no launch).
+// With composite_target = false the colour and variance terms are f2n_loss_sup_fwd's without alpha
+// (gt' = gt), and the opacity term is formed in ATen from that entry's device scalar W:
+//   d = O - a on the rays with m != 0, else 0;  opac = sum_r m_r d_r^2 / W;  loss += opacity_weight opac
+// -- no host read, last_opacity_loss_ filled, a ray with m_r = 0 contributes exact zeros to the term
+// and to the opacity's gradient.
 TrainStepResult train_step(
   Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
   const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,

@@ -1127,6 +1127,47 @@ int f2n_draw_pixels_guided(
   int attempts, float uniform_fraction, int32_t * cam, int32_t * ij, int32_t * tries,
   float * ray_weight, int n, void * stream);
 
+/* ------------------------------------------------------------------ learned background -------- */
+
+/* A cube map of colour logits looked up by ray direction: the background a render blends behind the
+ * field, learned from the images.  The reference has none: src/renderer.cpp:103-110 blends a
+ * constant (rand in TRAIN, 0.5 otherwise).
+ *   tex   [6, R, R, 3] f32 logits, 2 <= R <= 4096; face = 2*axis + (component < 0) of the largest
+ *         |component| (ties: x before y before z), in-face coordinates the other two components
+ *         divided by it, in axis order and without sign flips; bilinear, clamped to the face's edge
+ *         (no filtering across faces); bg = sigmoid(logit).  A texture of zeros gives 0.5f exactly.
+ *   dirs  [n_rays, 3], any length.  A ray whose largest |component| is not finite and positive
+ *         (zero vector, NaN, inf) gets bg = 0.5 and contributes no gradient.
+ *   bg    [n_rays, 3]
+ * The evaluation order is fixed in the header comment of envmap.hip.  Every entry of this section
+ * answers F2N_E_INVALID_ARG before any HIP work for a null pointer, R outside 2 .. 4096 or
+ * n_rays < 0; n_rays == 0 is F2N_OK without a launch, and excuses no bad argument.  Directions
+ * receive no gradient (pose optimisation through the sky is not covered).
+ *   f2n_envmap_texels: 6*R*R, or 0 when R is out of range.
+ *   f2n_envmap_fwd: one lane per ray, one launch. */
+#define F2N_ENVMAP_SHIFT 48 /* the fixed point of the texture gradient: units of 2^-48 */
+int64_t f2n_envmap_texels(int R);
+int f2n_envmap_fwd(
+  const float * dirs, const float * tex, int R, float * bg, int n_rays, void * stream);
+
+/* The texture's gradient, beside src/renderer.cpp:103-110.  bg is f2n_envmap_fwd's saved output, the
+ * geometry is recomputed.  Per ray and channel gl = d_bg * (bg * (1 - bg)) in f32; gl == 0 adds
+ * nothing (an opaque ray issues no atomic); gl not finite adds nothing and sets bit 0 of flags [1]
+ * i32; otherwise each of the four corners gets llrint(gl * w * 2^F2N_ENVMAP_SHIFT), the product
+ * exact in f64, |.| capped at 2^62 (bit 1 of flags), added to acc [6*R*R*3] i64 by a 64-bit integer
+ * atomicAdd when it is not 0.  Integer sums do not depend on their order: the gradient has the same
+ * bits on every run.  The quantum is 2^-48 = 3.6e-15, the range of a texel's sum +-2^14.  acc must
+ * hold zeros before the first call; flags is only ever or-ed into.  The host reads neither. */
+int f2n_envmap_bwd(
+  const float * dirs, const float * bg, const float * d_bg, int R, int64_t * acc, int32_t * flags,
+  int n_rays, void * stream);
+
+/* The sums as a gradient, beside src/renderer.cpp:103-110:
+ * d_tex[i] (+)= (float)ldexp((double)acc[i], -F2N_ENVMAP_SHIFT) over the 6*R*R*3 elements, and
+ * acc[i] = 0: ready for the next step without a memset, so a whole step stays capturable in a
+ * hipGraph.  accumulate is 0 or 1 (anything else: F2N_E_INVALID_ARG). */
+int f2n_envmap_grad_apply(int64_t * acc, int R, float * d_tex, int accumulate, void * stream);
+
 /* ------------------------------------------------------------------ localiser ----------------- */
 
 /* The particle loop of Localizer::optimize_pose_by_random_search -- src/localizer.cpp:88-118 (per
