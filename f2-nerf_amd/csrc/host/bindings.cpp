@@ -20,6 +20,7 @@
 #include "scene_files.hpp"
 #include "renderer.hpp"
 #include "sh_shader.hpp"
+#include "ssim.hpp"
 
 namespace py = pybind11;
 using torch::Tensor;
@@ -343,6 +344,68 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     py::arg("images") = py::none(), py::arg("dist") = py::none(),
     "sample_masked_rays with the guided draw of an ErrorMap: the same dict, ray_weight being the "
     "importance weight (0 where every attempt missed); see f2n::sample_guided_rays");
+  m.def(
+    "ssim",
+    [](const Tensor & pred, const Tensor & gt, bool clip, bool want_map) {
+      f2n::SsimOut o = f2n::ssim(pred, gt, clip, want_map);
+      return py::make_tuple(o.ssim, tensor_or_none(o.map));
+    },
+    py::arg("pred"), py::arg("gt"), py::arg("clip") = true, py::arg("want_map") = false,
+    "f2n_ssim_fwd: pred, gt [B,h,w,3] or [h,w,3] -> (ssim [B], map [B,h-10,w-10,3] | None); clip: "
+    "the reference's clamps (the metric form).  Not differentiated");
+  m.def("ssim_loss", &CustomOps::Ssim, py::arg("pred"), py::arg("gt"),
+        "CustomOps::Ssim(pred, gt) -> [B]: the unclamped form, differentiable in pred only");
+  m.def(
+    "image_scores",
+    [](const Tensor & pred, const Tensor & gt) {
+      f2n::ImageScores sc = f2n::image_scores(pred, gt);
+      py::dict d;
+      d["mse"] = sc.mse;
+      d["psnr"] = sc.psnr;
+      d["ssim"] = sc.ssim;
+      d["score"] = sc.score;
+      return d;
+    },
+    py::arg("pred"), py::arg("gt"),
+    "per-view mse, psnr, ssim (clipped, inputs clamped to [0,1]) and the Localizer's score, device "
+    "tensors [B]; see f2n::image_scores");
+  m.def(
+    "draw_patches",
+    [](int64_t E, int64_t h, int64_t w, int64_t n_patches, int64_t P, uint64_t seed,
+       const f2n::PixelMask * mask, int attempts) {
+      f2n::PatchDraw d = f2n::draw_patches(
+        E, h, w, n_patches, P, seed, mask ? *mask : f2n::PixelMask(), attempts);
+      return py::make_tuple(d.cam, d.ij, d.tries, d.patch_weight);
+    },
+    py::arg("E"), py::arg("h"), py::arg("w"), py::arg("n_patches"), py::arg("P"), py::arg("seed"),
+    py::arg("mask") = py::none(), py::arg("attempts") = 32,
+    "f2n_draw_patches -> (cam [n P^2] i32, ij [n P^2,2] i32, tries [n] i32, patch_weight [n] f32)");
+  m.def(
+    "sample_patch_rays",
+    [](const Tensor & poses, const Tensor & intr, int64_t h, int64_t w, int64_t n_patches, int64_t P,
+       uint64_t seed, const c10::optional<Tensor> & images, const f2n::PixelMask * mask,
+       const c10::optional<Tensor> & dist, int attempts) {
+      f2n::PatchBatch pb = f2n::sample_patch_rays(
+        poses, intr, h, w, n_patches, P, seed, opt_tensor(images),
+        mask ? *mask : f2n::PixelMask(), opt_tensor(dist), attempts);
+      const f2n::MaskedBatch & b = pb.batch;
+      py::dict d;
+      d["rays_o"] = b.rays.origins;
+      d["rays_d"] = b.rays.dirs;
+      d["gt"] = tensor_or_none(b.gt);
+      d["alpha"] = tensor_or_none(b.alpha);
+      d["cam"] = b.cam;
+      d["ray_weight"] = b.ray_weight;
+      d["ij"] = b.ij;
+      d["tries"] = b.tries;
+      d["patch_weight"] = pb.patch_weight;
+      return d;
+    },
+    py::arg("poses"), py::arg("intrinsics"), py::arg("h"), py::arg("w"), py::arg("n_patches"),
+    py::arg("P"), py::arg("seed"), py::arg("images") = py::none(), py::arg("mask") = py::none(),
+    py::arg("dist") = py::none(), py::arg("attempts") = 32,
+    "a batch of n_patches P x P patches: sample_masked_rays' dict (tries and patch_weight per "
+    "patch, ray_weight the patch's weight on its rays); see f2n::sample_patch_rays");
   m.def("ray_order", &f2n::ray_order, "caller indices of rays_d sorted into pixel-compact bundles");
   m.def("manual_seed", [](uint64_t s) { torch::manual_seed(s); });
   m.def("kernel_timer_enable", &f2n::kernel_timer_enable);
@@ -490,6 +553,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def_readwrite("opacity_weight", &f2n::RaySupervision::opacity_weight)
     .def_readwrite("want_colors", &f2n::RaySupervision::want_colors)
     .def_readwrite("composite_target", &f2n::RaySupervision::composite_target);
+  py::class_<f2n::PatchLoss>(m, "PatchLoss")
+    .def(
+      py::init([](int patch, float ssim_weight, const c10::optional<Tensor> & patch_weight) {
+        return f2n::PatchLoss{patch, ssim_weight, opt_tensor(patch_weight)};
+      }),
+      py::arg("patch") = 0, py::arg("ssim_weight") = 0.f, py::arg("patch_weight") = py::none(),
+      "the patch side P (the rays are n_patches * P^2, patch-major), the weight of the D-SSIM term "
+      "and per-patch weights [n_patches]; patch 0 or weight 0: no term")
+    .def_readwrite("patch", &f2n::PatchLoss::patch)
+    .def_readwrite("ssim_weight", &f2n::PatchLoss::ssim_weight)
+    .def_property_readonly(
+      "patch_weight", [](const f2n::PatchLoss & p) { return tensor_or_none(p.patch_weight); });
   py::class_<f2n::DepthLossOptions>(m, "DepthLossOptions")
     .def(
       py::init([](float empty, float near, float expected, float eps) {
@@ -699,6 +774,33 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
       "itself, launch for launch; the opacity term's mean is left in last_opacity_loss.  NOTE THE "
       "ARITY: with sup.want_colors the tuple has a sixth element, the render's colours [n_rays, 3], "
       "detached")
+    .def(
+      "train_step_patches",
+      [](Renderer & r, const Tensor & o, const Tensor & d, const Tensor & emb_idx, const Tensor & gt,
+         const f2n::PatchLoss & patch, const f2n::RaySupervision & sup, float var_loss_weight,
+         const c10::optional<Tensor> & noise, const c10::optional<Tensor> & bg, bool backward,
+         float dist_loss_weight, const c10::optional<Tensor> & depth_target,
+         const f2n::DepthLossOptions & depth_loss) {
+        f2n::TrainStepResult out;
+        {
+          py::gil_scoped_release no_gil;
+          out = f2n::train_step(
+            r, o, d, emb_idx, gt, var_loss_weight, dist_loss_weight, opt_tensor(noise),
+            opt_tensor(bg), backward, opt_tensor(depth_target), depth_loss, sup, patch);
+        }
+        return py::make_tuple(
+          out.loss, out.sq_err_sum, out.n_values, out.n_samples, tensor_or_none(out.weight_sum),
+          tensor_or_none(out.colors));
+      },
+      py::arg("rays_o"), py::arg("rays_d"), py::arg("emb_idx"), py::arg("gt_colors"),
+      py::arg("patch"), py::arg("sup") = f2n::RaySupervision(), py::arg("var_loss_weight") = 0.f,
+      py::arg("noise") = py::none(), py::arg("bg_color") = py::none(), py::arg("backward") = true,
+      py::arg("dist_loss_weight") = 0.f, py::arg("depth_target") = py::none(),
+      py::arg("depth_loss") = f2n::DepthLossOptions(),
+      "train_step with a PatchLoss (a D-SSIM term on patches; its unweighted mean: last_ssim_loss) "
+      "and an optional RaySupervision: always six elements, (loss, sq_err_sum, n_values, "
+      "n_samples, weight_sum | None, colors | None).  patch 0 or ssim_weight 0 is "
+      "train_step_supervised, launch for launch")
     .def("named_parameters", [](Renderer & r) { return named_params(r); })
     .def("zero_grad", [](Renderer & r) { r.zero_grad(); })
     .def(
@@ -750,6 +852,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def_property_readonly(
       "last_opacity_loss", [](const Renderer & r) { return tensor_or_none(r.last_opacity_loss_); },
       "weighted mean of (opacity - alpha)^2 of the last train_step that had the term, or None")
+    .def_property_readonly(
+      "last_ssim_loss", [](const Renderer & r) { return tensor_or_none(r.last_ssim_loss_); },
+      "unweighted mean of 1 - SSIM_b of the last train_step with an active PatchLoss, or None")
     .def_readonly("last_kept_fraction", &Renderer::last_kept_fraction_)
     .def_readonly("last_n_samples", &Renderer::last_n_samples_)
     .def_property_readonly("scene_field", [](Renderer & r) { return r.scene_field_; })

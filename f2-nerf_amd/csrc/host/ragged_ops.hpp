@@ -3,6 +3,7 @@
 //   CustomOps::WeightVar                           (src/CustomOps/CustomOps.hpp:23-28)
 //   CustomOps::WeightDist                          (no counterpart: the distortion loss beside it)
 //   CustomOps::DepthSight                          (no counterpart: the line-of-sight depth losses)
+//   CustomOps::Ssim                                (no counterpart: SSIM with a gradient, ssim.cpp)
 //   CustomOps::ScatterAdd / CustomOps::ScatterIdx  (src/CustomOps/Scatter.hpp:16-21)
 //   torch::autograd::TruncExp                      (src/CustomOps/CustomOps.hpp:13-19)
 // Same names, argument meaning and autograd behaviour; the kernels behind them are the wave-per-ray
@@ -49,6 +50,11 @@ torch::Tensor WeightDist(
 torch::Tensor DepthSight(
   torch::Tensor weights, torch::Tensor t, torch::Tensor dt, torch::Tensor idx_start_end,
   torch::Tensor z, double eps);
+// Not in the reference, whose rgb_ssim (scripts/eval.py:29-75) is a host-side metric: the structural
+// similarity of image pairs in its unclamped, differentiable form (f2n_ssim_fwd with clip = 0 /
+// f2n_ssim_bwd; defined in ssim.cpp).  pred, gt [B,h,w,3] (or [h,w,3]: B = 1), h, w >= 11  ->  [B].
+// The gradient goes to `pred` only.
+torch::Tensor Ssim(torch::Tensor pred, torch::Tensor gt);
 torch::Tensor ScatterAdd(torch::Tensor emb, torch::Tensor idx, torch::Tensor to_add);
 torch::Tensor ScatterIdx(int n_all_pts, torch::Tensor idx_start_end, torch::Tensor emb_idx);
 }  // namespace CustomOps

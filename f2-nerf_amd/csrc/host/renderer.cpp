@@ -1224,11 +1224,42 @@ std::vector<torch::optim::OptimizerParamGroup> Renderer::optim_param_groups(floa
 
 // ---- training-step harness -----------------------------------------------------------------------
 
+// The D-SSIM term of a batch of patches: loss + ssim_weight * sum_b m_b (1 - SSIM_b) / M on the
+// colours viewed as [n, P, P, 3] against `target` (no gradient), M = sum_b m_b (1 when that is not
+// positive; no host read).  The unweighted mean is left in last_ssim_loss_.
+static Tensor add_patch_term(
+  Renderer & renderer, const Tensor & loss, const Tensor & colors, const Tensor & target,
+  const f2n::PatchLoss & pl)
+{
+  const int64_t P = pl.patch, n_rays = colors.size(0);
+  TORCH_CHECK(
+    P >= 11 && n_rays > 0 && n_rays % (P * P) == 0,
+    "train_step: a PatchLoss needs n_patches * patch^2 rays in patch-major order, patch >= 11");
+  const int64_t n = n_rays / (P * P);
+  TORCH_CHECK(target.numel() == n_rays * 3, "train_step: the colour target must be [n_rays, 3]");
+  const Tensor one_minus = 1.f - CustomOps::Ssim(
+                                   colors.reshape({n, P, P, 3}),
+                                   target.detach().reshape({n, P, P, 3}));  // [n]
+  Tensor term;
+  if (pl.patch_weight.defined()) {
+    const Tensor m = f2n::dev_f32(pl.patch_weight.detach(), "patch_weight").reshape({-1});
+    TORCH_CHECK(m.numel() == n, "train_step: patch_weight must be [n_rays / patch^2]");
+    const Tensor sum_m = m.sum();
+    const Tensor M = torch::where(sum_m.gt(0.f), sum_m, torch::ones_like(sum_m));
+    term = (m * one_minus).sum() / M;
+  } else {
+    term = one_minus.mean();
+  }
+  renderer.last_ssim_loss_ = one_minus.detach().mean();
+  return loss + pl.ssim_weight * term;
+}
+
 static f2n::TrainStepResult train_step_plain(
   Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
   const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
   const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
-  const f2n::DepthLossOptions & depth_loss, bool want_colors);
+  const f2n::DepthLossOptions & depth_loss, bool want_colors,
+  const f2n::PatchLoss * patch = nullptr);
 
 f2n::TrainStepResult f2n::train_step(
   Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
@@ -1266,7 +1297,7 @@ static f2n::TrainStepResult train_step_plain(
   Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
   const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
   const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
-  const f2n::DepthLossOptions & depth_loss, bool want_colors)
+  const f2n::DepthLossOptions & depth_loss, bool want_colors, const f2n::PatchLoss * patch)
 {
   using namespace f2n;
   // (a zero distortion weight: the term is not computed and the call is the one without it)
@@ -1323,6 +1354,8 @@ static f2n::TrainStepResult train_step_plain(
     renderer.last_depth_loss_ = sums.detach() / depth_n_valid;
   }
   renderer.last_opacity_loss_ = Tensor();
+  renderer.last_ssim_loss_ = Tensor();
+  if (patch) loss = add_patch_term(renderer, loss, res.colors, gt_colors, *patch);
   TrainStepResult out;
   out.loss = loss.detach();
   out.sq_err_sum = stats[3].detach();
@@ -1333,17 +1366,19 @@ static f2n::TrainStepResult train_step_plain(
   return out;
 }
 
-f2n::TrainStepResult f2n::train_step(
+static f2n::TrainStepResult train_step_sup(
   Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
   const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
   const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
-  const DepthLossOptions & depth_loss, const RaySupervision & sup)
+  const f2n::DepthLossOptions & depth_loss, const f2n::RaySupervision & sup,
+  const f2n::PatchLoss * patch)
 {
+  using namespace f2n;
   // (no supervision: the call without it, launch for launch)
   if (!sup.ray_weight.defined() && !sup.alpha.defined())
     return train_step_plain(
       renderer, rays_o, rays_d, emb_idx, gt_colors, var_loss_weight, dist_loss_weight, noise,
-      bg_color, run_backward, depth_target, depth_loss, sup.want_colors);
+      bg_color, run_backward, depth_target, depth_loss, sup.want_colors, patch);
   const int64_t n_rays = rays_o.size(0);
   // composite_target off: the colour target is gt itself and alpha feeds the opacity term alone
   const bool plain_target = sup.alpha.defined() && !sup.composite_target;
@@ -1425,6 +1460,16 @@ f2n::TrainStepResult f2n::train_step(
   renderer.last_opacity_loss_ = !want_opacity  ? Tensor()
                                 : plain_target ? opacity_term.detach()
                                                : stats[3].detach();
+  renderer.last_ssim_loss_ = Tensor();
+  if (patch) {
+    // the colour target the colour loss used: a gt + (1 - a) bg when the alpha target composites
+    Tensor target = gt_colors;
+    if (alpha.defined() && !plain_target) {
+      const Tensor a = alpha.unsqueeze(1);
+      target = a * gt_colors.detach() + (1.f - a) * bg_color.detach();
+    }
+    loss = add_patch_term(renderer, loss, res.colors, target, *patch);
+  }
   TrainStepResult out;
   out.loss = loss.detach();
   out.sq_err_sum = stats[4].detach();
@@ -1434,4 +1479,28 @@ f2n::TrainStepResult f2n::train_step(
   if (sup.want_colors) out.colors = res.colors.detach();
   if (run_backward && loss.requires_grad()) loss.backward();
   return out;
+}
+
+f2n::TrainStepResult f2n::train_step(
+  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
+  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
+  const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
+  const DepthLossOptions & depth_loss, const RaySupervision & sup)
+{
+  return train_step_sup(
+    renderer, rays_o, rays_d, emb_idx, gt_colors, var_loss_weight, dist_loss_weight, noise, bg_color,
+    run_backward, depth_target, depth_loss, sup, nullptr);
+}
+
+f2n::TrainStepResult f2n::train_step(
+  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
+  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
+  const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
+  const DepthLossOptions & depth_loss, const RaySupervision & sup, const PatchLoss & patch)
+{
+  // (no patch term: the call without it, launch for launch -- the rule for dist_loss_weight == 0)
+  const bool want_ssim = patch.patch != 0 && patch.ssim_weight != 0.f;
+  return train_step_sup(
+    renderer, rays_o, rays_d, emb_idx, gt_colors, var_loss_weight, dist_loss_weight, noise, bg_color,
+    run_backward, depth_target, depth_loss, sup, want_ssim ? &patch : nullptr);
 }

@@ -293,6 +293,9 @@ public:
   // an alpha target and the rendered opacity (device scalar, detached, no host read); undefined
   // after a step without
   Tensor last_opacity_loss_;
+  // the unweighted mean over the patches of 1 - SSIM_b in the most recent f2n::train_step with an
+  // active PatchLoss (device scalar, detached); undefined when the last step had none
+  Tensor last_ssim_loss_;
 
 private:
   // Everything the routes branch on, decided once per render() call (choose_route).
@@ -492,5 +495,29 @@ TrainStepResult train_step(
   const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
   const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
   const DepthLossOptions & depth_loss, const RaySupervision & sup);
+
+// A structural term on patches (f2n::sample_patch_rays makes such a batch; CustomOps::Ssim).
+// patch == 0 or ssim_weight == 0: no term.
+struct PatchLoss
+{
+  int patch = 0;             // P: the rays are n_patches * P^2, patch-major, row-major in a patch
+  float ssim_weight = 0.f;   // lambda of sum_b m_b (1 - SSIM_b) / M
+  Tensor patch_weight;       // [n_patches] m_b: 0 drops the patch; undefined = 1
+};
+
+// ... with a D-SSIM term on patches:
+//   loss += ssim_weight * sum_b m_b (1 - SSIM_b) / M,  M = sum_b m_b (1 when that is not positive;
+// no host read), SSIM_b the unclamped SSIM of the render's colours viewed as [n_patches, P, P, 3]
+// against the colour target the colour loss used (a gt + (1 - a) bg where the alpha target
+// composites).  The gradient reaches the colours through CustomOps::Ssim as the distortion term's
+// reaches the weights; a patch with m_b = 0 contributes exact zeros.  The unweighted mean of
+// 1 - SSIM_b is left in Renderer::last_ssim_loss_.  A ray count that is no multiple of P^2, P < 11
+// or a patch_weight of another length throws.  patch == 0 or ssim_weight == 0 is the call above,
+// launch for launch and bit for bit.
+TrainStepResult train_step(
+  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
+  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
+  const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
+  const DepthLossOptions & depth_loss, const RaySupervision & sup, const PatchLoss & patch);
 
 }  // namespace f2n

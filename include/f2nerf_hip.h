@@ -1168,6 +1168,66 @@ int f2n_envmap_bwd(
  * hipGraph.  accumulate is 0 or 1 (anything else: F2N_E_INVALID_ARG). */
 int f2n_envmap_grad_apply(int64_t * acc, int R, float * d_tex, int accumulate, void * stream);
 
+/* ------------------------------------------------------------------ SSIM ---------------------- */
+
+/* Structural similarity of B image pairs and its gradient, beside the reference's rgb_ssim --
+ * scripts/eval.py:29-75, which runs in scipy on the host (its C++ scores a view by squared error
+ * alone, src/main_functions/test.cpp:38-40): an 11-tap Gaussian (sigma 1.5, centred, normalised),
+ * `valid` borders, k1 = 0.01, k2 = 0.03, max_val = 1, so c1 = 1e-4 and c2 = 9e-4.
+ *   pred, gt [B, h, w, 3] f32, interleaved and contiguous; h, w >= 11; B <= 65535.
+ *   Per channel, with mux, muy, Exx, Eyy, Exy the separable `valid` correlations of x, y, x^2, y^2, xy:
+ *     sxx = Exx - mux^2, syy = Eyy - muy^2, sxy = Exy - mux muy
+ *     S = (2 mux muy + c1)(2 sxy + c2) / ((mux^2 + muy^2 + c1)(sxx + syy + c2))
+ *   ssim [B] = the mean of S over the (h-10)(w-10) 3 values of the map.
+ *   clip = 1: the reference's clamps before S -- sxx, syy >= 0, |sxy| <= sqrt(sxx syy), sign kept: the
+ *     metric.  clip = 0: the plain expression: the differentiable form.  The clamps act on rounding
+ *     error only.
+ *   map [B, h-10, w-10, 3] or null: S itself.
+ *   gmaps [B, h-10, w-10, 9] or null, clip = 0 only: per channel c the partials of S by mux, Exx and
+ *     Exy at index 3 c + {0, 1, 2}; what f2n_ssim_bwd reads.
+ *   partial: scratch of f2n_ssim_workspace_doubles(B, h, w) doubles (one per tile; 0 for bad sizes).
+ * A tile of F2N_SSIM_TILE^2 map pixels per workgroup, staged in LDS with its 10-pixel halo; each tile
+ * writes one f64 partial and a second launch adds an image's partials in a fixed order in f64,
+ * divides and rounds once.  No atomics: the same bits on every run.  The evaluation order is fixed in
+ * the header comment of ssim.hip.  f2n_ssim_filter writes the eleven f32 taps (host only).
+ * A null among pred, gt, ssim, partial, sizes outside the above, clip not 0 or 1, or gmaps with
+ * clip = 1: F2N_E_INVALID_ARG before any HIP work; B == 0: F2N_OK without a launch. */
+#define F2N_SSIM_TILE 16
+int f2n_ssim_filter(float * taps11);
+int64_t f2n_ssim_workspace_doubles(int B, int h, int w);
+int f2n_ssim_fwd(
+  const float * pred, const float * gt, int B, int h, int w, int clip, float * ssim, float * map,
+  float * gmaps, double * partial, void * stream);
+
+/* The gradient of the clip = 0 form by pred, beside scripts/eval.py:29-75 (which has none; the
+ * reference's loss, src/main_functions/train_manager.cpp:78-96, has no structural term):
+ *   d_pred(p) = d_ssim_b / n_b [ (f * gmu)(p) + 2 x(p) (f * gxx)(p) + y(p) (f * gxy)(p) ]
+ * with * the `full` separable convolution over the map, n_b = (h-10)(w-10) 3, and gmaps those the
+ * forward wrote for the same pred and gt.  A workgroup owns 16 x 16 input pixels and gathers: every
+ * element of d_pred [B, h, w, 3] is written exactly once, no atomics, no memset; an image whose
+ * d_ssim is 0 gets exact zeros.  gt receives no gradient.  Any null pointer or sizes as above:
+ * F2N_E_INVALID_ARG; B == 0: F2N_OK. */
+int f2n_ssim_bwd(
+  const float * pred, const float * gt, const float * gmaps, const float * d_ssim, int B, int h,
+  int w, float * d_pred, void * stream);
+
+/* A training batch of n_patches patches of P x P pixels from E images of h x w, beside
+ * src/dataset.cpp:150-171 and f2n_draw_pixels_masked.  One wavefront per patch b; attempt a takes
+ * Philox4x32-10 with key (seed_lo, seed_hi) and counter (b, a, 2, 0), cam = mulhi(x0, E),
+ * i0 = mulhi(x1, h - P + 1), j0 = mulhi(x2, w - P + 1).  bits (the words of f2n_mask_pack) or null:
+ * with bits an attempt is kept only if all P^2 pixels are valid (lanes test pixels, a ballot
+ * decides); without, the first attempt is kept.
+ *   cam [n P^2] i32, ij [n P^2, 2] i32 (row, col): patch-major, row-major inside a patch -- pixel
+ *   (u, v) of patch b is ray b P^2 + u P + v.  tries [n] i32: attempts used, or 0 when every attempt
+ *   missed (the last one stays); patch_weight [n] f32: 1, or 0 where tries is 0.
+ * Integers decide everything and nothing is read on the host.  A null among the outputs, n_patches
+ * < 0, E < 1, h or w below 11, P outside 11 .. min(h, w), attempts outside 1 .. 64, E*h*w >= 2^36 or
+ * n_patches P^2 >= 2^31: F2N_E_INVALID_ARG before any HIP work; n_patches == 0: F2N_OK. */
+int f2n_draw_patches(
+  const uint32_t * bits, int E, int h, int w, int n_patches, int P, uint32_t seed_lo,
+  uint32_t seed_hi, int attempts, int32_t * cam, int32_t * ij, int32_t * tries,
+  float * patch_weight, void * stream);
+
 /* ------------------------------------------------------------------ localiser ----------------- */
 
 /* The particle loop of Localizer::optimize_pose_by_random_search -- src/localizer.cpp:88-118 (per
