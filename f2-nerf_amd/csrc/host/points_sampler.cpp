@@ -119,3 +119,44 @@ SampleResultFlex PtsSampler::get_samples_aten(
   res.pts_idx_bounds = torch::stack({starts, starts + (int)S}, 1).contiguous();
   return res;
 }
+
+namespace
+{
+// the positions of f2n_sample_rays pass through; the backward hands their gradient to the rays
+class SamplePtsFn : public torch::autograd::Function<SamplePtsFn>
+{
+public:
+  static torch::autograd::variable_list forward(
+    torch::autograd::AutogradContext * ctx, Tensor pts, Tensor rays_o, Tensor rays_d, Tensor t)
+  {
+    ctx->save_for_backward({rays_d.detach(), t});
+    ctx->saved_data["n_rays"] = rays_o.size(0);
+    return {pts.clone()};
+  }
+
+  static torch::autograd::variable_list backward(
+    torch::autograd::AutogradContext * ctx, torch::autograd::variable_list grads)
+  {
+    const auto saved = ctx->get_saved_variables();
+    const Tensor & rays_d = saved[0];
+    const Tensor & t = saved[1];
+    const int64_t n_rays = ctx->saved_data["n_rays"].toInt();
+    if (!grads[0].defined()) return {Tensor(), Tensor(), Tensor(), Tensor()};
+    const Tensor g = grads[0].reshape({n_rays, -1, 3});
+    const Tensor d_o = g.sum(1);
+    const Tensor d_unit = (g * t.reshape({n_rays, -1, 1})).sum(1);
+    const Tensor norm = torch::linalg_norm(rays_d, 2, -1, true);
+    const Tensor unit = rays_d / norm;
+    const Tensor d_d = (d_unit - unit * (unit * d_unit).sum(-1, true)) / norm;
+    return {Tensor(), d_o, d_d, Tensor()};
+  }
+};
+}  // namespace
+
+SampleResultFlex PtsSampler::get_samples_grad(
+  const Tensor & rays_o, const Tensor & rays_d, const Tensor & noise)
+{
+  SampleResultFlex res = get_samples(rays_o.detach(), rays_d.detach(), noise);
+  res.pts = SamplePtsFn::apply(res.pts, rays_o, rays_d, res.t)[0];
+  return res;
+}

@@ -37,7 +37,7 @@ public:
   explicit PtsSampler(const PtsSamplerOptions & opt = {});
 
   // One kernel instead of the reference's ~20 ATen launches (points_sampler.cpp:20-64).  Not
-  // differentiable in the rays: use get_samples_aten() when rays carry gradients.
+  // differentiable in the rays: use get_samples_grad() when rays carry gradients.
   SampleResultFlex get_samples(const Tensor & rays_o, const Tensor & rays_d, RunningMode mode);
   // Same, with the step-noise tensor [n_rays, max_samples] supplied (undefined = all ones).
   SampleResultFlex get_samples(const Tensor & rays_o, const Tensor & rays_d, const Tensor & noise);
@@ -52,8 +52,16 @@ public:
     const Tensor & rays_o, const Tensor & rays_d, const Tensor & noise, const Tensor & noise_rows,
     bool noise_raw);
 
-  // The reference's own ATen formulation (differentiable in rays_o / rays_d through autograd).
+  // The reference's own ATen formulation (differentiable in rays_o / rays_d through autograd).  Its
+  // positions differ from the kernel's in their last bit; no render route takes it any more.
   SampleResultFlex get_samples_aten(
+    const Tensor & rays_o, const Tensor & rays_d, const Tensor & noise);
+
+  // get_samples' own samples, bit for bit, with the positions differentiable in rays_o / rays_d:
+  // pts = o + d^ t with d^ = d / |d|, so d_o = sum_k d_pts_k and d_d = (I - d^ d^T) / |d| sum_k t_k
+  // d_pts_k.  dt = |d^| (t_k - t_{k-1}) and t do not depend on the rays.  The op-by-op route takes
+  // this when rays carry a gradient, so that it renders the positions every other route renders.
+  SampleResultFlex get_samples_grad(
     const Tensor & rays_o, const Tensor & rays_d, const Tensor & noise);
 
   // TRAIN: U[0,1) - 0.5 + 1 per sample (points_sampler.cpp:35); VALIDATE: undefined tensor (= ones).

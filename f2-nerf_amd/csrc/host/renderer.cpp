@@ -443,8 +443,9 @@ RenderResult Renderer::render_op_by_op(
 {
   const int64_t n_rays = rays_o.size(0);
   const int64_t S = pts_sampler_->options_.max_samples;
+  // (rays with a gradient: the same samples, their positions differentiable in the rays)
   SampleResultFlex all = route.grad_rays.origins.defined()
-                           ? pts_sampler_->get_samples_aten(rays_o, rays_d, noise)
+                           ? pts_sampler_->get_samples_grad(rays_o, rays_d, noise)
                            : pts_sampler_->get_samples(rays_o, rays_d, noise);
 
   auto density_act = [](const Tensor & x) {

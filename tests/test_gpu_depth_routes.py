@@ -13,7 +13,7 @@ import torch
 from tests import depth_sight_model as dm
 from tests import ragged_cases as rc
 from tests.test_gpu_weight_dist import (N_RAYS, N_TRAIN, ROUTES, S, _route, _scene, _step,
-                                        hr_occupied)
+                                        _term_against_op_by_op, hr_occupied)
 
 pytestmark = pytest.mark.gpu
 
@@ -167,7 +167,7 @@ def test_train_step_with_depth_loss(host, capi, dev, thin_scene, route):
     z = _targets(scene, 7).to(dev)
     lam = (0.3, 0.05, 0.2)
     opts = host.DepthLossOptions(empty=lam[0], near=lam[1], expected=lam[2], eps=EPS)
-    loss0, sq0, ns0, g0 = _step(hr, scene)                          # the existing call
+    loss0, sq0, ns0, g0, all0 = _step(hr, scene, all_grads=True)    # the existing call
     assert hr.last_depth_loss is None and float(g0.abs().max()) > 0
     # no target, or three zero weights: that call, launch for launch
     for kw in (dict(depth_loss=opts), dict(depth_target=z),
@@ -178,7 +178,7 @@ def test_train_step_with_depth_loss(host, capi, dev, thin_scene, route):
 
     with torch.no_grad():
         terms = hr.render_for_loss(*scene["args"], depth_target=z, depth_eps=EPS)[6]
-    loss2, sq2, ns2, g2 = _step(hr, scene, depth_target=z, depth_loss=opts)
+    loss2, sq2, ns2, g2, all2 = _step(hr, scene, all_grads=True, depth_target=z, depth_loss=opts)
     assert torch.equal(sq2, sq0) and ns2 == ns0 == N_TRAIN * S
     n_valid = int((torch.isfinite(z) & (z > 0)).sum())
     assert n_valid == N_TRAIN - N_TRAIN // 8
@@ -197,6 +197,8 @@ def test_train_step_with_depth_loss(host, capi, dev, thin_scene, route):
     assert all(float(m) > 1e-6 for m in m64) and abs(float(loss2) - want) <= tol
     assert not torch.equal(g2, g0)
     assert bool(torch.isfinite(g2).all()) and float((g2 - g0).abs().max()) > 0
+    # ... and it is the right one: the op-by-op route's
+    _term_against_op_by_op(hr, host, dev, scene, route, all2, all0, depth_target=z, depth_loss=opts)
 
     # a batch without a single return: the terms are exact zeros and so is their gradient
     none = torch.zeros_like(z)

@@ -307,10 +307,11 @@ def test_fused_and_op_by_op_agree_at_reference_sampler(host, dev):
     assert torch.equal(grads[False][3], grads[True][3])
     _close(grads[True][2], grads[False][2], 1e-4)
     # The Q5 point gradient is piecewise constant in the contracted point and jumps at cell faces.
-    # The op-by-op route samples with ATen ops (its positions differ from the sampler kernel's in the
-    # last bit), so among 4 M samples a handful land across a fine-level face and move their ray's
-    # gradient by a jump of about mul * feature * g: those few rays are allowed outside the
-    # per-element bar, the gradient as a whole is not.
+    # When this was written the op-by-op route sampled with ATen ops (positions that differ from the
+    # sampler kernel's in the last bit), so among 4 M samples a handful landed across a fine-level face
+    # and moved their ray's gradient by a jump of about mul * feature * g: those few rays are allowed
+    # outside the per-element bar, the gradient as a whole is not.  (It samples with the kernel now,
+    # PtsSampler::get_samples_grad; the allowance stays as it was.)
     for got, ref in ((grads[True][0], grads[False][0]), (grads[True][1], grads[False][1])):
         scale = float(ref.abs().max())
         bad = (got - ref).abs() > 2e-3 * scale + 5e-2 * ref.abs()

@@ -180,9 +180,11 @@ def test_rays_that_require_grad_and_one_pass(dev, scene):
         og, dg = o.clone().requires_grad_(True), d.clone().requires_grad_(True)
         r = hr.render_result(og, dg, None, "validate")                     # op by op, under autograd
         assert r.colors.requires_grad and not r.normals.requires_grad
-        # the ATen sampler of this route rounds o + t d/|d| in another order than the sampler kernel: a
-        # last-bit difference of a position is 2e-4 of a cell at the finest level (pt is of the order of
-        # 2000), which the piecewise-linear gradient passes on -- the same vectors, not the same bits
+        # When this was written the ATen sampler of this route rounded o + t d/|d| in another order than
+        # the sampler kernel: a last-bit difference of a position is 2e-4 of a cell at the finest level
+        # (pt is of the order of 2000), which the piecewise-linear gradient passes on -- the same vectors,
+        # not the same bits.  (The route samples with the kernel now, PtsSampler::get_samples_grad; the
+        # allowance stays as it was.)
         assert bool(torch.isfinite(r.normals).all())
         assert float((r.normals - want.normals).abs().max()) <= 1e-2 * float(want.normals.abs().max())
         r.colors.sum().backward()

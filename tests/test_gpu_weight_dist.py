@@ -227,12 +227,39 @@ def test_thinned_lists_have_gaps(host, dev, scene):
 
 # ---- training step --------------------------------------------------------------------------------
 
-def _step(hr, scene, *extra, **kw):
+def _step(hr, scene, *extra, all_grads=False, **kw):
+    """-> (loss, sq_err_sum, n_samples, table gradient), and with all_grads a fifth element: every
+    gradient the step left, by name"""
     o, d, emb, _, noise, bg = scene["args"]
     hr.zero_grad()
     loss, sq, n_val, n_samp = hr.train_step(o, d, emb, scene["gt"], 1e-2, noise, bg, True, *extra, **kw)
     torch.cuda.synchronize()
-    return loss.clone(), sq.clone(), n_samp, hr.grads()["scene_field.feat_pool"].clone()
+    out = (loss.clone(), sq.clone(), n_samp, hr.grads()["scene_field.feat_pool"].clone())
+    if all_grads:
+        out += ({k: v.clone() for k, v in hr.grads().items() if v is not None},)
+    return out
+
+
+def _term_against_op_by_op(hr, host, dev, scene, route, with_term, without, **kw):
+    """The term's own gradient D = g(with) - g(without), and g(with) itself, against the op-by-op
+    route's, which adds the term through ATen's autograd on operators of its own: every gradient the
+    step leaves, to 1e-4 of the largest norm among the full gradients involved (the figure this file
+    holds a table gradient to between two routes; tests/step_terms_cases.py has the reasoning)."""
+    from tests import step_terms_cases as stc
+    _route(hr, host, dev, "op_by_op", N_TRAIN)
+    ref = dict(none=_step(hr, scene, all_grads=True)[4], all=_step(hr, scene, all_grads=True, **kw)[4])
+    _route(hr, host, dev, route, N_TRAIN)
+    got = dict(none=without, all=with_term)
+    for name, g in (("D", {"none": got["none"], "term": got["all"]}), ("g", got)):
+        r = dict(none=ref["none"], term=ref["all"]) if name == "D" else ref
+        ratios = stc.against(g, r)
+        key, worst = stc.worst(ratios)
+        print("  %s: %s against op by op, largest residual / (1e-4 max|g|) = %.4f at %s" % (
+            route, name, worst, key))
+        assert worst <= 1.0, (route, name, key, worst)
+    share = stc.shares(dict(none=got["none"], term=got["all"]))["term"]
+    print("  %s: |D| / |g(none)| = %.3f" % (route, share))
+    assert share >= stc.MIN_SHARE
 
 
 @pytest.mark.parametrize("route", ["march", "dense", "lean_bucketed"])
@@ -241,7 +268,7 @@ def test_train_step_with_distortion_weight(host, capi, dev, thin_scene, route):
     hr = scene["hr"]
     _route(hr, host, dev, route, N_TRAIN)
     capi.set_option("BWD_PHASES", 1)          # table gradient sums independent of the order
-    loss0, sq0, ns0, g0 = _step(hr, scene)                          # the existing call
+    loss0, sq0, ns0, g0, all0 = _step(hr, scene, all_grads=True)    # the existing call
     assert hr.last_dist_loss is None
     loss1, sq1, ns1, g1 = _step(hr, scene, dist_loss_weight=0.0)
     assert torch.equal(loss1, loss0) and torch.equal(sq1, sq0) and ns1 == ns0
@@ -251,7 +278,7 @@ def test_train_step_with_distortion_weight(host, capi, dev, thin_scene, route):
     lam = 0.1
     with torch.no_grad():
         dist = hr.render_for_loss(*scene["args"], want_dist=True)[5]
-    loss2, sq2, ns2, g2 = _step(hr, scene, dist_loss_weight=lam)
+    loss2, sq2, ns2, g2, all2 = _step(hr, scene, all_grads=True, dist_loss_weight=lam)
     assert torch.equal(sq2, sq0) and ns2 == ns0 == N_TRAIN * S
     mean = dist.mean()
     assert torch.equal(hr.last_dist_loss, mean) and not hr.last_dist_loss.requires_grad
@@ -264,6 +291,8 @@ def test_train_step_with_distortion_weight(host, capi, dev, thin_scene, route):
     assert not torch.equal(g2, g0)
     # the term pulls: its gradient is there, and finite
     assert bool(torch.isfinite(g2).all()) and float((g2 - g0).abs().max()) > 0
+    # ... and it is the right one: the op-by-op route's
+    _term_against_op_by_op(hr, host, dev, scene, route, all2, all0, dist_loss_weight=lam)
     _step(hr, scene)
     assert hr.last_dist_loss is None
 
