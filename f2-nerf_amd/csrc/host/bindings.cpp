@@ -8,6 +8,7 @@
 #include "error_map.hpp"
 #include "fused_adam.hpp"
 #include "hash_3d_anchored.hpp"
+#include "intrinsics_refiner.hpp"
 #include "kernel_timer.hpp"
 #include "localizer.hpp"
 #include "mesh.hpp"
@@ -185,6 +186,40 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
        const Tensor & d_out) { return pose_compose_bwd(base, delta, opt_tensor(fixed), d_out); },
     py::arg("base"), py::arg("delta"), py::arg("fixed"), py::arg("d_out"),
     "f2n_pose_compose_bwd: d_out [E,3,4] -> d_delta [E,6]");
+  m.def(
+    "get_rays_from_calibrated_cameras",
+    [](const Tensor & poses, const Tensor & intr, const c10::optional<Tensor> & dist,
+       const Tensor & cam_idx, const Tensor & ij, bool sorted) {
+      Rays r = get_rays_from_calibrated_cameras(poses, intr, opt_tensor(dist), cam_idx, ij, sorted);
+      return py::make_tuple(r.origins, r.dirs);
+    },
+    py::arg("poses"), py::arg("intrinsics"), py::arg("dist"), py::arg("cam_idx"), py::arg("ij"),
+    py::arg("sorted") = false,
+    "get_rays_from_cameras, differentiable in the poses (f2n_cam_pose_grad) and in the intrinsics "
+    "and dist (f2n_cam_intr_grad)");
+  m.def(
+    "intr_compose",
+    [](const Tensor & base_K, const c10::optional<Tensor> & base_dist, const Tensor & gamma,
+       const Tensor & group, const c10::optional<Tensor> & learn) {
+      auto [K, dist] = intr_compose(base_K, opt_tensor(base_dist), gamma, group, opt_tensor(learn));
+      return py::make_tuple(K, dist);
+    },
+    py::arg("base_K"), py::arg("base_dist"), py::arg("gamma"), py::arg("group"),
+    py::arg("learn") = py::none(),
+    "f2n_intr_compose: a shared calibration correction per camera group -> (K' [E,3,3], "
+    "dist' [E,4]), differentiable in gamma");
+  m.def(
+    "intr_compose_bwd",
+    [](const Tensor & base_K, const c10::optional<Tensor> & base_dist, const Tensor & gamma,
+       const Tensor & group, const c10::optional<Tensor> & learn, const c10::optional<Tensor> & d_K,
+       const c10::optional<Tensor> & d_dist) {
+      return intr_compose_bwd(
+        base_K, opt_tensor(base_dist), gamma, group, opt_tensor(learn), opt_tensor(d_K),
+        opt_tensor(d_dist));
+    },
+    py::arg("base_K"), py::arg("base_dist"), py::arg("gamma"), py::arg("group"), py::arg("learn"),
+    py::arg("d_K"), py::arg("d_dist"),
+    "f2n_intr_compose_bwd: d_K [E,3,3], d_dist [E,4] -> d_gamma [G,8]");
   m.def(
     "envmap_query", &f2n::envmap_query, py::arg("dirs"), py::arg("texture"),
     "f2n_envmap_fwd: dirs [n,3], texture [6,R,R,3] logits -> bg [n,3]; no autograd");
@@ -1141,6 +1176,64 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def(
       "load",
       [](std::shared_ptr<PoseRefiner> r, const std::string & path) { torch::load(r, path); });
+
+  // ---- IntrinsicsRefiner -------------------------------------------------------------------------
+  py::class_<IntrinsicsRefiner, std::shared_ptr<IntrinsicsRefiner>>(m, "IntrinsicsRefiner")
+    .def(py::init([](const Tensor & base_K, const c10::optional<Tensor> & base_dist,
+                     const c10::optional<Tensor> & group) {
+           return std::make_shared<IntrinsicsRefiner>(base_K, opt_tensor(base_dist), opt_tensor(group));
+         }),
+         py::arg("base_intrinsics"), py::arg("base_dist") = py::none(), py::arg("group") = py::none(),
+         "a shared correction of (fx, fy, cx, cy, k1, k2, p1, p2) per physical camera; see "
+         "intrinsics_refiner.hpp")
+    .def("intrinsics", &IntrinsicsRefiner::intrinsics,
+         "the effective intrinsics [E,3,3], differentiable in gamma")
+    .def("dist", &IntrinsicsRefiner::dist, "the effective (k1, k2, p1, p2) [E,4], differentiable in gamma")
+    .def(
+      "calibration",
+      [](IntrinsicsRefiner & r) {
+        auto [K, D] = r.calibration();
+        return py::make_tuple(K, D);
+      },
+      "(intrinsics, dist) from one launch")
+    .def("set_learned", &IntrinsicsRefiner::set_learned, py::arg("mask"),
+         "mask: 8 bools for (fx, fy, cx, cy, k1, k2, p1, p2)")
+    .def("set_fixed", &IntrinsicsRefiner::set_fixed, py::arg("image_mask"))
+    .def(
+      "sample_random_rays",
+      [](IntrinsicsRefiner & r, const Tensor & poses, int h, int w, int64_t n,
+         const c10::optional<Tensor> & images, const c10::optional<Tensor> & cam_idx,
+         const c10::optional<Tensor> & ij) {
+        auto [rays, gt, cam] = r.sample_random_rays(
+          poses, h, w, n, opt_tensor(images), opt_tensor(cam_idx), opt_tensor(ij));
+        return py::make_tuple(rays.origins, rays.dirs, gt, cam);
+      },
+      py::arg("poses"), py::arg("h"), py::arg("w"), py::arg("batch_size"),
+      py::arg("images") = py::none(), py::arg("cam_idx") = py::none(), py::arg("ij") = py::none())
+    .def(
+      "make_adam",
+      [](IntrinsicsRefiner & r, float lr) {
+        AdamHandle h;
+        h.opt = std::make_shared<torch::optim::Adam>(r.optim_param_groups(lr));
+        return h;
+      },
+      "torch::optim::Adam over optim_param_groups(lr)")
+    .def("corrections", &IntrinsicsRefiner::corrections,
+         "[E,8]: effective minus base (fx, fy, cx, cy, k1, k2, p1, p2)")
+    .def("zero_grad", [](IntrinsicsRefiner & r) { r.zero_grad(); })
+    .def_property_readonly("n_images", &IntrinsicsRefiner::n_images)
+    .def_property_readonly("n_groups", &IntrinsicsRefiner::n_groups)
+    .def_property_readonly("gamma", [](IntrinsicsRefiner & r) { return r.gamma_; })
+    .def_property_readonly("base_K", [](IntrinsicsRefiner & r) { return r.base_K_; })
+    .def_property_readonly("base_dist", [](IntrinsicsRefiner & r) { return r.base_dist_; })
+    .def_property_readonly("group", [](IntrinsicsRefiner & r) { return r.group_; })
+    .def_property_readonly("learn", [](IntrinsicsRefiner & r) { return r.learn_; })
+    .def(
+      "save",
+      [](std::shared_ptr<IntrinsicsRefiner> r, const std::string & path) { torch::save(r, path); })
+    .def(
+      "load",
+      [](std::shared_ptr<IntrinsicsRefiner> r, const std::string & path) { torch::load(r, path); });
 
   py::class_<AdamHandle>(m, "Adam")
     .def("step", [](AdamHandle & h) { h.opt->step(); }, py::call_guard<py::gil_scoped_release>())

@@ -108,33 +108,10 @@ std::tuple<Rays, Tensor, Tensor> PoseRefiner::sample_random_rays(
   const Tensor & intrinsics, int h, int w, int64_t batch_size, const Tensor & images,
   const Tensor & dist, const Tensor & cam_idx, const Tensor & ij)
 {
-  const auto iopt = f2n::int_on(base_.device());
-  const bool drawn = !cam_idx.defined();
-  Tensor cam;
-  if (drawn) {
-    // sorted values only: which ray gets which camera does not matter before the pixels are drawn
-    cam = std::get<0>(torch::randint(n_cameras(), {batch_size}, iopt).sort());
-  } else {
-    TORCH_CHECK(cam_idx.dim() == 1 && cam_idx.size(0) == batch_size, "cam_idx must be [batch_size]");
-    cam = f2n::dev_i32(cam_idx, "cam_idx");
-  }
-  Tensor pix;
-  if (ij.defined()) {
-    TORCH_CHECK(ij.dim() == 2 && ij.size(0) == batch_size && ij.size(1) == 2, "ij must be [n,2]");
-    pix = f2n::dev_i32(ij, "ij");
-  } else {
-    Tensor i = torch::randint(0, h, {batch_size}, iopt);
-    Tensor j = torch::randint(0, w, {batch_size}, iopt);
-    pix = torch::stack({i, j}, -1).contiguous();
-  }
-  Rays rays = get_rays_from_cameras(poses(), intrinsics, cam, pix, dist, /*sorted=*/drawn);
-  Tensor gt;
-  if (images.defined()) {
-    Tensor flat = (cam.to(torch::kLong) * h + pix.select(1, 0).to(torch::kLong)) * w +
-                  pix.select(1, 1).to(torch::kLong);
-    gt = images.view({-1, 3}).index({flat}).to(base_.device()).contiguous();
-  }
-  return {rays, gt, cam};
+  const CameraBatch b =
+    draw_camera_batch(n_cameras(), h, w, batch_size, cam_idx, ij, base_.device());
+  Rays rays = get_rays_from_cameras(poses(), intrinsics, b.cam, b.ij, dist, b.sorted);
+  return {rays, gather_colors(images, b, h, w), b.cam};
 }
 
 std::vector<torch::optim::OptimizerParamGroup> PoseRefiner::optim_param_groups(float lr)

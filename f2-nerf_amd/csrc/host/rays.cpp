@@ -136,9 +136,50 @@ Rays gen_rays(
   return {out[0], out[1]};
 }
 
+// The camera-sorted ray list that the per-camera sums walk, made with ATen ops on the device:
+// cam_start (the E + 1 segment bounds) and `order`, empty when cam_idx is already sorted.
+struct CamOrder
+{
+  Tensor cam_start, order;
+};
+
+CamOrder camera_order(const Tensor & cam_idx, int64_t E, bool sorted)
+{
+  Tensor order = torch::empty({0}, cam_idx.options());
+  Tensor cam_sorted = cam_idx;
+  if (!sorted && cam_idx.size(0) > 0) {
+    // stable: equal cameras keep the caller's order, so the sums' order is fixed by cam_idx alone
+    auto [vals, idx] = at::sort(cam_idx, /*stable=*/true, /*dim=*/0, /*descending=*/false);
+    cam_sorted = vals;
+    order = idx.to(torch::kInt32);
+  }
+  // cam_start[c] = number of rays whose camera is below c
+  Tensor cam_start = torch::searchsorted(
+    cam_sorted, torch::arange(E + 1, cam_idx.options()), /*out_int32=*/true, /*right=*/false);
+  return {cam_start, order};
+}
+
+// d(poses) in `shape` ([E,3|4,4]) of a batch's ray gradients: f2n_cam_pose_grad
+Tensor launch_cam_pose_grad(
+  const Tensor & K, const Tensor & dist, const Tensor & ij, const Tensor & d_o, const Tensor & d_d,
+  const CamOrder & co, const std::vector<int64_t> & shape)
+{
+  const int64_t E = shape[0], n = ij.size(0);
+  const int pose_ld = (int)(shape[1] * 4);
+  Tensor ws = torch::empty({f2n_cam_pose_grad_workspace_floats(n, E)}, K.options());
+  Tensor d_poses = torch::empty(shape, K.options());
+  f2n::check(
+    f2n_cam_pose_grad(
+      K.data_ptr<float>(), f2n::fptr(dist), ij.data_ptr<int32_t>(), d_o.data_ptr<float>(),
+      d_d.data_ptr<float>(), co.cam_start.data_ptr<int32_t>(),
+      co.order.numel() ? co.order.data_ptr<int32_t>() : nullptr, d_poses.data_ptr<float>(), pose_ld,
+      ws.data_ptr<float>(), n, E, f2n::current_stream(K)),
+    "f2n_cam_pose_grad");
+  return d_poses;
+}
+
 // launch_gen_rays with a camera per ray and a backward to the poses: the per-camera sums of
-// f2n_cam_pose_grad.  cam_start (the E + 1 segment bounds of the camera-sorted rays) is made with ATen
-// ops on the device; `order` is empty when cam_idx is already sorted.
+// f2n_cam_pose_grad.
 class CamRaysFn : public torch::autograd::Function<CamRaysFn>
 {
 public:
@@ -150,18 +191,9 @@ public:
     dist = dist_rows(dist, poses.size(0), poses);
     const int64_t n = cam_idx.size(0), E = poses.size(0);
     Rays rays = launch_gen_rays(poses, intrinsics, cam_idx, ij, 0, 1, n, dist);
-    Tensor order = torch::empty({0}, cam_idx.options());
-    Tensor cam_sorted = cam_idx;
-    if (!sorted && n > 0) {
-      // stable: equal cameras keep the caller's order, so the sums' order is fixed by cam_idx alone
-      auto [vals, idx] = at::sort(cam_idx, /*stable=*/true, /*dim=*/0, /*descending=*/false);
-      cam_sorted = vals;
-      order = idx.to(torch::kInt32);
-    }
-    // cam_start[c] = number of rays whose camera is below c
-    Tensor cam_start = torch::searchsorted(
-      cam_sorted, torch::arange(E + 1, cam_idx.options()), /*out_int32=*/true, /*right=*/false);
-    ctx->save_for_backward({f2n::dev_f32(intrinsics, "intrinsics"), ij, dist, cam_start, order});
+    const CamOrder co = camera_order(cam_idx, E, sorted);
+    ctx->save_for_backward(
+      {f2n::dev_f32(intrinsics, "intrinsics"), ij, dist, co.cam_start, co.order});
     ctx->saved_data["pose_shape"] = poses.sizes().vec();
     return {rays.origins, rays.dirs};
   }
@@ -172,29 +204,137 @@ public:
     auto saved = ctx->get_saved_variables();
     const Tensor & K = saved[0];
     const Tensor & ij = saved[1];
-    const Tensor & dist = saved[2];
-    const Tensor & cam_start = saved[3];
-    const Tensor & order = saved[4];
-    const auto shape = ctx->saved_data["pose_shape"].toIntVector();
-    const int64_t E = shape[0], n = ij.size(0);
-    const int pose_ld = (int)(shape[1] * 4);
+    const int64_t n = ij.size(0);
     const auto opt = K.options();
     Tensor d_o = grad[0].defined() ? f2n::dev_f32(grad[0], "grad rays_o") : torch::zeros({n, 3}, opt);
     Tensor d_d = grad[1].defined() ? f2n::dev_f32(grad[1], "grad rays_d") : torch::zeros({n, 3}, opt);
-    Tensor ws = torch::empty({f2n_cam_pose_grad_workspace_floats(n, E)}, opt);
-    Tensor d_poses = torch::empty(shape, opt);
-    f2n::check(
-      f2n_cam_pose_grad(
-        K.data_ptr<float>(), f2n::fptr(dist), ij.data_ptr<int32_t>(), d_o.data_ptr<float>(),
-        d_d.data_ptr<float>(), cam_start.data_ptr<int32_t>(),
-        order.numel() ? order.data_ptr<int32_t>() : nullptr, d_poses.data_ptr<float>(), pose_ld,
-        ws.data_ptr<float>(), n, E, f2n::current_stream(K)),
-      "f2n_cam_pose_grad");
+    Tensor d_poses = launch_cam_pose_grad(
+      K, saved[2], ij, d_o, d_d, {saved[3], saved[4]}, ctx->saved_data["pose_shape"].toIntVector());
     return {d_poses, Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
   }
 };
 
+// CamRaysFn with the calibration as an input: the backward reaches the poses through
+// f2n_cam_pose_grad (CamRaysFn's launch, the same bits) and the intrinsics and the coefficients
+// through f2n_cam_intr_grad, each only if its input asks for it, over one shared cam_start / order.
+// dist empty = pinhole cameras, which then have no coefficients to hand a gradient to.
+class CalibratedCamRaysFn : public torch::autograd::Function<CalibratedCamRaysFn>
+{
+public:
+  static torch::autograd::variable_list forward(
+    torch::autograd::AutogradContext * ctx, Tensor poses, Tensor intrinsics, Tensor dist,
+    Tensor cam_idx, Tensor ij, bool sorted)
+  {
+    ctx->saved_data["dist_shape"] = dist.sizes().vec();
+    if (dist.numel() == 0) dist = Tensor();
+    dist = dist_rows(dist, poses.size(0), poses);
+    const int64_t n = cam_idx.size(0), E = poses.size(0);
+    Rays rays = launch_gen_rays(poses, intrinsics, cam_idx, ij, 0, 1, n, dist);
+    const CamOrder co = camera_order(cam_idx, E, sorted);
+    auto [pose_rows, pose_ld] = pose_blocks(poses);
+    (void)pose_ld;
+    ctx->save_for_backward(
+      {pose_rows, f2n::dev_f32(intrinsics, "intrinsics"), ij, dist, co.cam_start, co.order});
+    return {rays.origins, rays.dirs};
+  }
+
+  static torch::autograd::variable_list backward(
+    torch::autograd::AutogradContext * ctx, torch::autograd::variable_list grad)
+  {
+    auto saved = ctx->get_saved_variables();
+    const Tensor & poses = saved[0];
+    const Tensor & K = saved[1];
+    const Tensor & ij = saved[2];
+    const Tensor & dist = saved[3];
+    const CamOrder co = {saved[4], saved[5]};
+    const int64_t E = poses.size(0), n = ij.size(0);
+    const auto opt = K.options();
+    Tensor d_d = grad[1].defined() ? f2n::dev_f32(grad[1], "grad rays_d") : torch::zeros({n, 3}, opt);
+    Tensor d_poses, d_K, d_dist;
+    if (ctx->needs_input_grad(0)) {
+      Tensor d_o =
+        grad[0].defined() ? f2n::dev_f32(grad[0], "grad rays_o") : torch::zeros({n, 3}, opt);
+      d_poses = launch_cam_pose_grad(K, dist, ij, d_o, d_d, co, poses.sizes().vec());
+    }
+    const bool want_K = ctx->needs_input_grad(1);
+    const bool want_dist = dist.defined() && ctx->needs_input_grad(2);
+    if (want_K || want_dist) {
+      Tensor ws = torch::empty({f2n_cam_intr_grad_workspace_floats(n, E)}, opt);
+      Tensor d_intr = torch::empty({E, 8}, opt);
+      f2n::check(
+        f2n_cam_intr_grad(
+          poses.data_ptr<float>(), (int)(poses.size(1) * 4), K.data_ptr<float>(), f2n::fptr(dist),
+          ij.data_ptr<int32_t>(), d_d.data_ptr<float>(), co.cam_start.data_ptr<int32_t>(),
+          co.order.numel() ? co.order.data_ptr<int32_t>() : nullptr, d_intr.data_ptr<float>(),
+          ws.data_ptr<float>(), n, E, f2n::current_stream(K)),
+        "f2n_cam_intr_grad");
+      if (want_K) {
+        d_K = torch::zeros({E, 3, 3}, opt);
+        d_K.select(1, 0).select(1, 0).copy_(d_intr.select(1, 0));
+        d_K.select(1, 1).select(1, 1).copy_(d_intr.select(1, 1));
+        d_K.select(1, 0).select(1, 2).copy_(d_intr.select(1, 2));
+        d_K.select(1, 1).select(1, 2).copy_(d_intr.select(1, 3));
+      }
+      if (want_dist)
+        d_dist = d_intr.slice(1, 4, 8).contiguous().view(ctx->saved_data["dist_shape"].toIntVector());
+    }
+    return {d_poses, d_K, d_dist, Tensor(), Tensor(), Tensor()};
+  }
+};
+
 }  // namespace
+
+CameraBatch draw_camera_batch(
+  int64_t n_cameras, int h, int w, int64_t batch_size, const Tensor & cam_idx, const Tensor & ij,
+  const torch::Device & device)
+{
+  const auto iopt = f2n::int_on(device);
+  CameraBatch b;
+  b.sorted = !cam_idx.defined();
+  if (b.sorted) {
+    // sorted values only: which ray gets which camera does not matter before the pixels are drawn
+    b.cam = std::get<0>(torch::randint(n_cameras, {batch_size}, iopt).sort());
+  } else {
+    TORCH_CHECK(cam_idx.dim() == 1 && cam_idx.size(0) == batch_size, "cam_idx must be [batch_size]");
+    b.cam = f2n::dev_i32(cam_idx, "cam_idx");
+  }
+  if (ij.defined()) {
+    TORCH_CHECK(ij.dim() == 2 && ij.size(0) == batch_size && ij.size(1) == 2, "ij must be [n,2]");
+    b.ij = f2n::dev_i32(ij, "ij");
+  } else {
+    Tensor i = torch::randint(0, h, {batch_size}, iopt);
+    Tensor j = torch::randint(0, w, {batch_size}, iopt);
+    b.ij = torch::stack({i, j}, -1).contiguous();
+  }
+  return b;
+}
+
+Tensor gather_colors(const Tensor & images, const CameraBatch & b, int h, int w)
+{
+  if (!images.defined()) return Tensor();
+  Tensor flat = (b.cam.to(torch::kLong) * h + b.ij.select(1, 0).to(torch::kLong)) * w +
+                b.ij.select(1, 1).to(torch::kLong);
+  return images.view({-1, 3}).index({flat}).to(b.cam.device()).contiguous();
+}
+
+Rays get_rays_from_calibrated_cameras(
+  const Tensor & poses, const Tensor & intrinsics, const Tensor & dist, const Tensor & cam_idx,
+  const Tensor & ij, bool sorted)
+{
+  const bool grad_mode = torch::GradMode::is_enabled();
+  const bool want_calib =
+    grad_mode && (intrinsics.requires_grad() || (dist.defined() && dist.requires_grad()));
+  // nothing for f2n_cam_intr_grad to do: today's route, the same graph
+  if (!want_calib) return get_rays_from_cameras(poses, intrinsics, cam_idx, ij, dist, sorted);
+  TORCH_CHECK(ij.dim() == 2 && ij.size(1) == 2, "ij must be [n,2]");
+  TORCH_CHECK(cam_idx.dim() == 1 && cam_idx.size(0) == ij.size(0), "cam_idx must be [n]");
+  TORCH_CHECK(poses.size(0) >= 1, "get_rays_from_calibrated_cameras: no cameras");
+  Tensor cam = f2n::dev_i32(cam_idx, "cam_idx");
+  Tensor ij32 = f2n::dev_i32(ij, "ij");
+  const Tensor lens = dist.defined() ? dist : torch::empty({0}, f2n::float_on(poses.device()));
+  auto out = CalibratedCamRaysFn::apply(poses, intrinsics, lens, cam, ij32, sorted);
+  return {out[0], out[1]};
+}
 
 Rays get_rays_from_cameras(
   const Tensor & poses, const Tensor & intrinsics, const Tensor & cam_idx, const Tensor & ij,

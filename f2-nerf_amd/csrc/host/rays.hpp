@@ -17,14 +17,16 @@ struct alignas(32) Rays
 // and pose.requires_grad() (the reference's Localizer optimises a [3,4] pose through render_image,
 // src/localizer.cpp:142-167): the backward (f2n_gen_rays_bwd) returns d(pose) in the pose's own shape
 // ([B,3,4] / [B,4,4], or [3,4] / [4,4] through get_view_rays), row 3 of a [4,4] pose zero, the sum
-// over the rays in a fixed order.  The intrinsics are constants: they never receive a gradient.
+// over the rays in a fixed order.  The intrinsics are constants there: only
+// get_rays_from_calibrated_cameras hands them a gradient.
 //
 // Lens distortion: every function takes an optional `dist` holding (k1, k2, p1, p2) per camera, the
 // columns CamsMeta::dist_params reads from cams_meta.tsv (src/dataset.cpp:59-63; the reference's
 // src/rays.cpp:7-28 ignores them).  Defined: the pixel is undistorted in the kernel
 // (f2n_gen_rays_dist, 8 Newton steps) and the backward is f2n_gen_rays_dist_bwd.  Undefined: the
 // pinhole entry points, as before.  A camera whose four numbers are zero gives the pinhole bits
-// either way.  Like the intrinsics, `dist` never receives a gradient.
+// either way.  Like the intrinsics, `dist` receives a gradient from
+// get_rays_from_calibrated_cameras alone; every other function detaches it.
 
 // pose [B,3,4] (or [B,4,4]), intrinsic [B,3,3], ij [N,2] = (row, col), float or integer; B == 1 or
 // B == N.  Pixel centres (+0.5), camera looks down -z, y up.  One kernel (f2n_gen_rays).
@@ -70,6 +72,34 @@ std::tuple<Rays, torch::Tensor, torch::Tensor> sample_random_rays(
 Rays get_rays_from_cameras(
   const torch::Tensor & poses, const torch::Tensor & intrinsics, const torch::Tensor & cam_idx,
   const torch::Tensor & ij, const torch::Tensor & dist = {}, bool sorted = false);
+
+// get_rays_from_cameras with the calibration as a variable: the one function here whose intrinsics
+// and `dist` receive a gradient (self-calibration, intrinsics_refiner.hpp).  The rays are the bits of
+// get_rays_from_cameras.  Under grad mode the backward forms, each only if its input requires it,
+//   d(poses)       f2n_cam_pose_grad, the bits of get_rays_from_cameras' backward
+//   d(intrinsics)  [E,3,3], zero outside [0][0], [1][1], [0][2], [1][2]   } f2n_cam_intr_grad, one
+//   d(dist)        in dist's shape; an undefined dist (pinhole) has none   } launch for both
+// over one sort and one cam_start.  Without a calibration that requires a gradient it is
+// get_rays_from_cameras.
+Rays get_rays_from_calibrated_cameras(
+  const torch::Tensor & poses, const torch::Tensor & intrinsics, const torch::Tensor & dist,
+  const torch::Tensor & cam_idx, const torch::Tensor & ij, bool sorted = false);
+
+// The camera and pixel draw that the refiners' sample_random_rays share: cameras drawn on the device
+// and SORTED before the pixels are drawn, so the per-camera sums of the backward need no permutation.
+// cam_idx [n] i32 and ij [n,2] i32, when defined, replace the draws; a given cam_idx need not be
+// sorted (sorted = false then).
+struct CameraBatch
+{
+  torch::Tensor cam;  // [n] i32
+  torch::Tensor ij;   // [n,2] i32
+  bool sorted;
+};
+CameraBatch draw_camera_batch(
+  int64_t n_cameras, int h, int w, int64_t batch_size, const torch::Tensor & cam_idx,
+  const torch::Tensor & ij, const torch::Device & device);
+// images [E,h,w,3] at the batch's pixels -> [n,3] on the batch's device; undefined without images
+torch::Tensor gather_colors(const torch::Tensor & images, const CameraBatch & b, int h, int w);
 
 // The forward model, world point -> pixel (f2n_project_points): points [N,3]; pose [B,3,4] (or
 // [B,4,4], or one [3,4] / [4,4]), intrinsic [B,3,3] (or [3,3]), dist [B,4] (or [4]; undefined =

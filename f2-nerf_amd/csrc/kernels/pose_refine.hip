@@ -9,105 +9,55 @@
 //   f2n_pose_compose      R' = Exp(omega) R, t' = t + tau: the parameterisation that stays on SO(3),
 //   f2n_pose_compose_bwd  where Adam on the twelve raw entries of a pose (src/localizer.cpp:142-167)
 //                         leaves it after one step.
-#include "camera.hiph"
+#include "cam_pieces.hiph"
 
 namespace
 {
 
 // ---- f2n_cam_pose_grad ----------------------------------------------------------------------------
 //
-// The camera-sorted ray list is cut into pieces of kPiece positions counted from the START OF THE LIST,
-// one wavefront per piece.  A piece meets the cameras c_first .. c_last (two binary searches in
-// cam_start); the wavefront takes them 64 at a time, one per lane:
-//   * a run (camera intersected with piece) shorter than kLaneRun is summed by its lane alone, in
-//     position order;
-//   * a longer run is summed by the whole wavefront: 64-position strides from the run's start, twelve
-//     lane accumulators, wave_sum in the fixed DPP tree.
-// Where a run goes:
-//   * the camera lies inside the piece          -> its d_poses block, finished;
-//   * the camera begins here and goes on        -> workspace slot G + c;
-//   * the camera came in from the piece before  -> workspace slot g (only one camera can).
-// That is G + E slots of 12 floats and no scan of pieces per camera.  The second kernel, one thread per
-// (camera, component), writes zeros for an empty camera and adds a spanning camera's slots in piece
-// order.  The partition depends on cam_start alone and every order is fixed: the same bits on every
-// run, no float atomics, no host read, two launches.  Work is O(n + E/64) per launch: one camera does
-// not serialise through one wavefront, and empty cameras cost a lane each.
+// The per-camera sums of cam_pieces.hiph with the twelve terms of a pose: pieces of kPiece positions,
+// one wavefront each, a camera that spans pieces finished by the second kernel in piece order.
 
-constexpr int kPiece = 1024;
-constexpr int kLaneRun = 32;
-
-__device__ __forceinline__ int clamp_int(int v, int lo, int hi)
+struct PoseRays
 {
-  return v < lo ? lo : (v > hi ? hi : v);
-}
+  const float * __restrict__ intrinsics;
+  const float * __restrict__ dist;
+  const int32_t * __restrict__ ij;
+  const float * __restrict__ d_o;
+  const float * __restrict__ d_d;
+  const int32_t * __restrict__ order;
+  int n;
 
-// largest i in [0, E - 1] with cam_start[i] <= p: the camera that owns position p
-__device__ __forceinline__ int camera_of(const int32_t * __restrict__ cam_start, int E, int p)
-{
-  int lo = 0, hi = E - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (cam_start[mid] <= p)
-      lo = mid;
-    else
-      hi = mid - 1;
+  struct Cam
+  {
+    const float * K;
+    LensDist lens;
+  };
+
+  __device__ __forceinline__ Cam camera(int c) const
+  {
+    return {intrinsics + (int64_t)c * 9, load_lens(dist, c)};
   }
-  return lo;
-}
 
-// the twelve terms of the ray at position p, added to acc (row-major [3,4]: d_d[i] v[j] | d_o[i])
-__device__ __forceinline__ void add_ray(
-  float (&acc)[12], const float * __restrict__ K, const LensDist & lens,
-  const int32_t * __restrict__ ij, const float * __restrict__ d_o, const float * __restrict__ d_d,
-  const int32_t * __restrict__ order, int p, int n)
-{
-  const int64_t r = order ? order[p] : p;
-  if (r < 0 || r >= n) return;  // a caller's order is not trusted with an address
-  float u, v;
-  camera_pixel_to_dir(K, lens, (float)ij[2 * r], (float)ij[2 * r + 1], u, v);
-  const float w = -1.f;
+  // the twelve terms of the ray at position p, added to acc (row-major [3,4]: d_d[i] v[j] | d_o[i])
+  __device__ __forceinline__ void add(float (&acc)[12], const Cam & cam, int p) const
+  {
+    const int64_t r = order ? order[p] : p;
+    if (r < 0 || r >= n) return;  // a caller's order is not trusted with an address
+    float u, v;
+    camera_pixel_to_dir(cam.K, cam.lens, (float)ij[2 * r], (float)ij[2 * r + 1], u, v);
+    const float w = -1.f;
 #pragma unroll
-  for (int a = 0; a < 3; a++) {
-    const float g = d_d[3 * r + a];
-    acc[4 * a] += g * u;
-    acc[4 * a + 1] += g * v;
-    acc[4 * a + 2] += g * w;
-    acc[4 * a + 3] += d_o[3 * r + a];
+    for (int a = 0; a < 3; a++) {
+      const float g = d_d[3 * r + a];
+      acc[4 * a] += g * u;
+      acc[4 * a + 1] += g * v;
+      acc[4 * a + 2] += g * w;
+      acc[4 * a + 3] += d_o[3 * r + a];
+    }
   }
-}
-
-struct RunSpan
-{
-  int s_full, e_full;  // the camera's positions
-  int s, e;            // ... inside the piece
 };
-
-__device__ __forceinline__ RunSpan run_span(
-  const int32_t * __restrict__ cam_start, int c, int lo, int hi, int n)
-{
-  RunSpan r;
-  r.s_full = clamp_int(cam_start[c], 0, n);
-  r.e_full = clamp_int(cam_start[c + 1], r.s_full, n);
-  r.s = r.s_full > lo ? r.s_full : lo;
-  r.e = r.e_full < hi ? r.e_full : hi;
-  if (r.e < r.s) r.e = r.s;
-  return r;
-}
-
-__device__ __forceinline__ void store_run(
-  const float (&acc)[12], const RunSpan & run, int c, int g, int G, int lo, int hi,
-  float * __restrict__ d_poses, int pose_ld, float * __restrict__ ws)
-{
-  const bool whole = run.s_full >= lo && run.e_full <= hi;
-  float * dst = whole ? d_poses + (int64_t)c * pose_ld
-                      : ws + 12 * (run.s_full >= lo ? (int64_t)G + c : (int64_t)g);
-#pragma unroll
-  for (int k = 0; k < 12; k++) dst[k] = acc[k];
-  if (whole && pose_ld == 16) {
-#pragma unroll
-    for (int k = 12; k < 16; k++) dst[k] = 0.f;
-  }
-}
 
 __global__ __launch_bounds__(F2N_BLOCK) void cam_pose_grad_piece_kernel(
   const float * __restrict__ intrinsics, const float * __restrict__ dist,
@@ -115,66 +65,15 @@ __global__ __launch_bounds__(F2N_BLOCK) void cam_pose_grad_piece_kernel(
   const int32_t * __restrict__ cam_start, const int32_t * __restrict__ order,
   float * __restrict__ d_poses, int pose_ld, float * __restrict__ ws, int n, int E, int G)
 {
-  const int g = (int)blockIdx.x * F2N_WAVES_PER_BLOCK + (int)(threadIdx.x >> 6);
-  if (g >= G) return;  // wave-uniform
-  const int lane = lane_id();
-  const int lo = g * kPiece;
-  const int hi = (n - lo < kPiece) ? n : lo + kPiece;
-  const int c_first = camera_of(cam_start, E, lo), c_last = camera_of(cam_start, E, hi - 1);
-  for (int base = c_first; base <= c_last; base += F2N_WAVE) {
-    const int c = base + lane;
-    RunSpan run = {0, 0, 0, 0};
-    if (c <= c_last) run = run_span(cam_start, c, lo, hi, n);
-    const int len = run.e - run.s;
-    if (len > 0 && len < kLaneRun) {
-      float acc[12];
-#pragma unroll
-      for (int k = 0; k < 12; k++) acc[k] = 0.f;
-      const float * K = intrinsics + (int64_t)c * 9;
-      const LensDist lens = load_lens(dist, c);
-      for (int p = run.s; p < run.e; p++) add_ray(acc, K, lens, ij, d_o, d_d, order, p, n);
-      store_run(acc, run, c, g, G, lo, hi, d_poses, pose_ld, ws);
-    }
-    unsigned long long longs = __ballot(len >= kLaneRun);
-    while (longs) {  // wave-uniform
-      const int cc = base + (__ffsll(longs) - 1);
-      longs &= longs - 1;
-      const RunSpan wide = run_span(cam_start, cc, lo, hi, n);
-      float acc[12];
-#pragma unroll
-      for (int k = 0; k < 12; k++) acc[k] = 0.f;
-      const float * K = intrinsics + (int64_t)cc * 9;
-      const LensDist lens = load_lens(dist, cc);
-      for (int p0 = wide.s; p0 < wide.e; p0 += F2N_WAVE) {
-        const int p = p0 + lane;
-        if (p < wide.e) add_ray(acc, K, lens, ij, d_o, d_d, order, p, n);
-      }
-#pragma unroll
-      for (int k = 0; k < 12; k++) acc[k] = wave_sum(acc[k]);
-      if (lane == 0) store_run(acc, wide, cc, g, G, lo, hi, d_poses, pose_ld, ws);
-    }
-  }
+  const PoseRays rays = {intrinsics, dist, ij, d_o, d_d, order, n};
+  cam_piece_sums<12>(rays, cam_start, d_poses, pose_ld, ws, n, E, G);
 }
 
 __global__ __launch_bounds__(F2N_BLOCK) void cam_pose_grad_final_kernel(
   const int32_t * __restrict__ cam_start, const float * __restrict__ ws,
   float * __restrict__ d_poses, int pose_ld, int n, int E, int G)
 {
-  const int64_t t = (int64_t)blockIdx.x * F2N_BLOCK + threadIdx.x;
-  if (t >= (int64_t)E * 12) return;
-  const int c = (int)(t / 12), k = (int)(t % 12);
-  const int s = clamp_int(cam_start[c], 0, n), e = clamp_int(cam_start[c + 1], s, n);
-  float * P = d_poses + (int64_t)c * pose_ld;
-  if (pose_ld == 16 && k < 4 && (s == e || ((e - 1) / kPiece != s / kPiece))) P[12 + k] = 0.f;
-  if (s == e) {
-    P[k] = 0.f;
-    return;
-  }
-  const int g0 = s / kPiece, g1 = (e - 1) / kPiece;
-  if (g0 == g1) return;  // written by the piece kernel
-  float acc = ws[12 * ((int64_t)G + c) + k];
-  for (int g = g0 + 1; g <= g1; g++) acc += ws[12 * (int64_t)g + k];
-  P[k] = acc;
+  cam_piece_finish<12>(cam_start, ws, d_poses, pose_ld, n, E, G);
 }
 
 // ---- f2n_pose_compose -----------------------------------------------------------------------------
@@ -303,8 +202,6 @@ __global__ __launch_bounds__(F2N_BLOCK) void pose_compose_bwd_kernel(
   D[4] = Gm[7];
   D[5] = Gm[11];
 }
-
-inline int64_t cam_pieces(int64_t n) { return (n + kPiece - 1) / kPiece; }
 
 }  // namespace
 

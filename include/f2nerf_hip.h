@@ -496,7 +496,8 @@ int f2n_gen_rays_dist(
  * f2n_gen_rays_bwd stand as they are.  dist [n_cams, 4] or NULL, n_cams is 1 or n.  The workspace is
  * f2n_gen_rays_bwd_workspace_floats(n) floats; n_cams == 1 sums in the same fixed partition and
  * order (the same bits on every run; with zero coefficients the bits of f2n_gen_rays_bwd).  Neither
- * the intrinsics nor the coefficients receive a gradient.  n == 0 returns F2N_OK and writes nothing. */
+ * the intrinsics nor the coefficients receive a gradient here (f2n_cam_intr_grad forms theirs).
+ * n == 0 returns F2N_OK and writes nothing. */
 int f2n_gen_rays_dist_bwd(
   const float * intrinsics, const float * dist, int64_t n_cams, const int32_t * ij,
   int64_t first_pixel, int width, const float * d_rays_o, const float * d_rays_d, float * d_poses,
@@ -553,6 +554,62 @@ int f2n_pose_compose(
 int f2n_pose_compose_bwd(
   const float * base, int pose_ld, const float * delta, const int32_t * fixed, const float * d_out,
   float * d_delta, int64_t n_cams, void * stream);
+
+/* The gradient of a batch's ray directions with respect to the calibration of each camera: the
+ * fx, fy, cx, cy of its intrinsic and the k1, k2, p1, p2 of f2n_gen_rays_dist, which cams_meta.tsv
+ * carries (src/dataset.cpp:59-63) and src/rays.cpp:7-28 treats as exact.  The batch, its addressing,
+ * cam_start, order, the clamping of values outside 0..n and n == 0 (zero-fills d_intr) are those of
+ * f2n_cam_pose_grad; rays_o does not depend on the calibration, so there is no d_rays_o.
+ *   poses      [n_cams] blocks of pose_ld floats (12 or 16): R of each camera
+ *   d_intr     [n_cams, 8] = d(fx, fy, cx, cy, k1, k2, p1, p2), every element overwritten
+ *   workspace  f2n_cam_intr_grad_workspace_floats(n, n_cams) floats, contents undefined on entry.
+ * For a ray of camera c with (x, y) the ideal point the forward returned (the same device function,
+ * the same bits), xd = (col+.5-cx)/fx, yd = (row+.5-cy)/fy, r2 = x^2 + y^2:
+ *     gx =  sum_i d_rays_d[r][i] R_c[i][0],   gy = -sum_i d_rays_d[r][i] R_c[i][1]
+ *     J = [[a, b], [b, d]] the Jacobian of the distortion model at (x, y),  det = a d - b b
+ *     lx = (d gx - b gy) / det,   ly = (a gy - b gx) / det
+ *     d_intr[c] += ( -lx xd / fx, -ly yd / fy, -lx / fx, -ly / fy,
+ *                    -r2 (lx x + ly y), -r2^2 (lx x + ly y),
+ *                    -(2 x y lx + (r2 + 2 y^2) ly), -((r2 + 2 x^2) lx + 2 x y ly) )
+ * the implicit-function gradient at the forward's point, not the derivative of its Newton steps.  A
+ * camera whose four coefficients are zero (or a NULL dist) takes J = I and still receives the gradient
+ * to its coefficients.  A ray with |det| <= 1e-8 or a non-finite lx, ly contributes exact zeros.  The
+ * sums per camera are f2n_cam_pose_grad's: pieces of 1024 positions, no float atomics, the same bits
+ * on every run, no host read, two launches. */
+int64_t f2n_cam_intr_grad_workspace_floats(int64_t n, int64_t n_cams);
+int f2n_cam_intr_grad(
+  const float * poses, int pose_ld, const float * intrinsics, const float * dist,
+  const int32_t * ij, const float * d_rays_d, const int32_t * cam_start, const int32_t * order,
+  float * d_intr, float * workspace, int64_t n, int64_t n_cams, void * stream);
+
+/* A shared correction of the calibration per physical camera, the parameterisation of
+ * self-calibration (the reference reads fx, fy, cx, cy and k1, k2, p1, p2 per image from
+ * cams_meta.tsv, src/dataset.cpp:59-63, and never changes them).  Image e belongs to group
+ * g = group[e]; a negative group marks a fixed image.  With c = gamma[g]:
+ *     fx' = fx exp(c0)    fy' = fy exp(c1)    cx' = cx + c2 fx    cy' = cy + c3 fy   (base fx, fy)
+ *     k1' = k1 + c4       k2' = k2 + c5       p1' = p1 + c6       p2' = p2 + c7
+ * eight dimensionless numbers of one scale.
+ *   base_K     [n_images, 3, 3];  base_dist [n_images, 4] or NULL (zeros)
+ *   gamma      [n_groups, 8];     group [n_images] i32
+ *   out_K      [n_images, 3, 3], the other entries of K copied;  out_dist [n_images, 4]
+ * f64 inside, each output rounded once.  An image whose eight numbers all compare equal to zero, or
+ * whose group is negative, gets its base rows bit for bit.  A group >= n_groups is the caller's error:
+ * the kernel treats it as fixed and never uses it as an address.  One thread per image. */
+int f2n_intr_compose(
+  const float * base_K, const float * base_dist, const float * gamma, const int32_t * group,
+  float * out_K, float * out_dist, int64_t n_images, int64_t n_groups, void * stream);
+
+/* Backward of f2n_intr_compose with respect to gamma: d_K [n_images, 3, 3] or NULL (zeros; only
+ * [0][0], [1][1], [0][2], [1][2] are read), d_dist [n_images, 4] or NULL (zeros) ->
+ *     d_gamma[g] = sum over the images of group g of
+ *                  (dfx' fx', dfy' fy', dcx' fx, dcy' fy, dk1', dk2', dp1', dp2'),
+ * every element of d_gamma [n_groups, 8] overwritten.  The sum is taken in f64 in image-index order
+ * and rounded once: the same bits on every run, no float atomics.  learn [8] i32 or NULL: a column
+ * whose flag is 0 gets exact zeros.  A group without images gets exact zeros. */
+int f2n_intr_compose_bwd(
+  const float * base_K, const float * base_dist, const float * gamma, const int32_t * group,
+  const int32_t * learn, const float * d_K, const float * d_dist, float * d_gamma,
+  int64_t n_images, int64_t n_groups, void * stream);
 
 /* The forward model of the same camera, the inverse of f2n_gen_rays_dist (the projection that
  * src/rays.cpp:7-28 inverts, with the coefficients of src/dataset.cpp:59-63): world point -> pixel.
