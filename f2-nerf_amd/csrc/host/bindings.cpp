@@ -477,6 +477,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def(
       "set_accumulate_in_place", [](Hash3DAnchored & s, bool on) { s.options_.accumulate_in_place = on; },
       "Hash3DAnchoredOptions::accumulate_in_place: add into feat_pool.grad directly once it exists")
+    .def("set_exact_point_grad", &Hash3DAnchored::set_exact_point_grad,
+         "Hash3DAnchoredOptions::exact_point_grad: points and rays that require a gradient receive the "
+         "encoding's true derivative instead of the reference's point gradient (quirk Q5)")
     .def_readonly("pool_size", &Hash3DAnchored::pool_size_)
     .def_readonly("local_size", &Hash3DAnchored::local_size_)
     .def_readonly("level_stride", &Hash3DAnchored::level_stride_)
@@ -863,6 +866,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def("set_pixel_tiles", [](Renderer & r, int b) { r.options_.pixel_tiles = b; })
     .def("set_fused_ray_grad", [](Renderer & r, bool f) { r.options_.fused_ray_grad = f; },
          "rays that require grad take the fused path: see RendererOptions::fused_ray_grad")
+    .def("set_exact_ray_grad", [](Renderer & r, bool on) { r.scene_field_->set_exact_point_grad(on); },
+         "the scene field's Hash3DAnchoredOptions::exact_point_grad, on every route")
     .def("set_margin_min_samples", [](Renderer & r, int64_t n) { r.options_.margin_min_samples = n; })
     .def("set_ray_order_min_rays", [](Renderer & r, int64_t n) { r.options_.ray_order_min_rays = n; },
          "dense first pass: bucket the rays from this many on (RendererOptions::ray_order_min_rays)")
@@ -1016,7 +1021,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def_readwrite("resize_factor", &LocalizerParam::resize_factor)
     .def_readwrite("one_pass", &LocalizerParam::one_pass)
     .def_readwrite("one_pass_head", &LocalizerParam::one_pass_head)
-    .def_readwrite("dist_params", &LocalizerParam::dist_params);
+    .def_readwrite("dist_params", &LocalizerParam::dist_params)
+    .def_readwrite("exact_ray_grad", &LocalizerParam::exact_ray_grad);
 
   py::class_<Localizer, std::shared_ptr<Localizer>>(m, "Localizer")
     .def(py::init<const LocalizerParam &>(), py::arg("param"),

@@ -326,6 +326,10 @@ variable_list Hash3DAnchoredFunction::backward(AutogradContext * ctx, variable_l
   // points need a gradient only for pose optimisation; training rays are data
   const bool want_points = ctx->needs_input_grad(0);
   Tensor points_grad = want_points ? torch::empty({n, 3}, points.options()) : Tensor();
+  // options_.exact_point_grad: the table gradient takes the call it takes when points need no
+  // gradient, and f2n_hash_pts_grad_exact fills the point gradient afterwards
+  const bool exact_points = want_points && field->options_.exact_point_grad;
+  const bool q5_points = want_points && !exact_points;
   // add into the gradient feat_pool already has (options_.accumulate_in_place), or start a new one
   Tensor embeds_grad;
   bool in_place = false;
@@ -345,7 +349,7 @@ variable_list Hash3DAnchoredFunction::backward(AutogradContext * ctx, variable_l
   // capped at 64 GiB: bigger batches run in rounds); it is further capped at half of the device's
   // free memory, and when even that cannot be allocated the atomic kernel takes over.
   int64_t ws_bytes =
-    want_points ? 0 : f2n_hash_bwd_workspace_bytes(n, L, F, g.T);
+    q5_points ? 0 : f2n_hash_bwd_workspace_bytes(n, L, F, g.T);
   Tensor ws;
   if (ws_bytes > 0 && field->options_.binned_backward) {
     size_t free_b = 0, total_b = 0;
@@ -381,9 +385,17 @@ variable_list Hash3DAnchoredFunction::backward(AutogradContext * ctx, variable_l
       f2n_hash_bwd(
         points.data_ptr<float>(), g.table, g.primes, g.bias, g.mul, grad_in.data_ptr<float>(),
         ld_point, ld_chan, embeds_grad.data_ptr<float>(),
-        want_points ? points_grad.data_ptr<float>() : nullptr, n, g.L, g.F, g.T, g.level_stride,
+        q5_points ? points_grad.data_ptr<float>() : nullptr, n, g.L, g.F, g.T, g.level_stride,
         grad_scale, stream),
       "f2n_hash_bwd");
+  }
+  if (exact_points && n > 0) {
+    f2n::ScopedKernelTimer timer("hash_pts_grad_exact", stream, (double)n);
+    f2n::check(
+      f2n_hash_pts_grad_exact(
+        points.data_ptr<float>(), g.table, g.primes, g.bias, g.mul, grad_in.data_ptr<float>(),
+        ld_point, ld_chan, points_grad.data_ptr<float>(), n, g.L, g.F, g.T, g.level_stride, stream),
+      "f2n_hash_pts_grad_exact");
   }
   return {points_grad, in_place ? Tensor() : embeds_grad, Tensor()};
 }

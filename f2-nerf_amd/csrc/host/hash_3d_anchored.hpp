@@ -32,6 +32,12 @@ struct Hash3DAnchoredOptions
   // gradient, the kernels add into it directly and autograd is told "no gradient" for that input.
   // Tensor hooks on feat_pool do not see those calls; switch it off if you rely on them.
   bool accumulate_in_place = true;
+  // Points (and rays) that require a gradient receive the encoding's true derivative -- the
+  // interpolant differentiated with all three axes' weights, in f32 (f2n_hash_pts_grad_exact,
+  // f2n_hash_rays_grad_exact) -- instead of the reference's point gradient (quirk Q5, about 4 times
+  // a cell-centre derivative and rounded through f16): the magnitude changes, learning rates tuned
+  // with it off do not carry over.  Off: every route launches what it always launched.
+  bool exact_point_grad = false;
   torch::Device device = f2n::default_device();
 };
 
@@ -90,6 +96,11 @@ public:
   // contraction (f2n_density_grad).  Not the point gradient autograd returns for query(), which is
   // the reference's (quirk Q5: no interpolation weights of the other two axes).  No-grad, detached.
   Tensor density_grad(const Tensor & points);
+
+  // Hash3DAnchoredOptions::exact_point_grad, for a field that exists already.  Both autograd nodes
+  // that form a point gradient (Hash3DAnchoredFunction, the Renderer's RayGradFn) read it at
+  // backward time.
+  void set_exact_point_grad(bool on) { options_.exact_point_grad = on; }
 
   // f16 working copy of feat_pool_, refreshed if feat_pool_ was modified since the last call.
   Tensor table_f16();

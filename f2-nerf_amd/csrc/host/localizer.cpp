@@ -106,6 +106,7 @@ void Localizer::init(
   // the pose optimisation renders 65536-ray chunks of 1024 samples with rays that require grad:
   // they take the fused path (RendererOptions::fused_ray_grad)
   renderer_->options_.fused_ray_grad = true;
+  if (param_.exact_ray_grad) renderer_->scene_field_->set_exact_point_grad(true);
   if (param_.one_pass) {
     renderer_->set_one_pass(true);
     renderer_->set_one_pass_head(param_.one_pass_head);

@@ -48,6 +48,11 @@ struct LocalizerParam
   // ray kernel, so the image handed in is the raw one.  They act on normalised coordinates:
   // resize_factor leaves them alone.  Zeros = pinhole.  Not part of inference_params.yaml either.
   std::array<float, 4> dist_params = {0.f, 0.f, 0.f, 0.f};
+  // optimize_pose_by_differential receives the encoding's true derivative instead of the reference's
+  // point gradient (Hash3DAnchoredOptions::exact_point_grad, set on the renderer's field in init).
+  // The gradient is about a quarter the size: a learning rate tuned without it does not carry over.
+  // Not part of inference_params.yaml either.
+  bool exact_ray_grad = false;
 };
 
 namespace f2n

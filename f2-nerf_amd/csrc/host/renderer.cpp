@@ -242,14 +242,26 @@ public:
         const f2n::FieldArgs fa = field->kernel_args(table16);
         const auto [g, ld_point, ld_chan] = f2n::encoding_grad_strides(g_enc, n, (int64_t)fa.L * fa.F);
         void * stream = f2n::current_stream(pts);
-        f2n::ScopedKernelTimer timer("hash_rays_grad", stream, (double)n);
-        f2n::check(
-          f2n_hash_rays_grad(
-            pts.data_ptr<float>(), t.data_ptr<float>(), bounds.data_ptr<int32_t>(),
-            rays_d.data_ptr<float>(), fa.table, fa.primes, fa.bias, fa.mul, g.data_ptr<float>(),
-            ld_point, ld_chan, d_o.data_ptr<float>(), d_d.data_ptr<float>(), (int)n_rays, fa.L, fa.F,
-            fa.T, fa.level_stride, 128.f /* hash_3d_anchored.cu:190 */, stream),
-          "f2n_hash_rays_grad");
+        if (field->options_.exact_point_grad) {
+          // the encoding's true derivative instead of quirk Q5: same kept samples, same sums
+          f2n::ScopedKernelTimer timer("hash_rays_grad_exact", stream, (double)n);
+          f2n::check(
+            f2n_hash_rays_grad_exact(
+              pts.data_ptr<float>(), t.data_ptr<float>(), bounds.data_ptr<int32_t>(),
+              rays_d.data_ptr<float>(), fa.table, fa.primes, fa.bias, fa.mul, g.data_ptr<float>(),
+              ld_point, ld_chan, d_o.data_ptr<float>(), d_d.data_ptr<float>(), (int)n_rays, fa.L,
+              fa.F, fa.T, fa.level_stride, stream),
+            "f2n_hash_rays_grad_exact");
+        } else {
+          f2n::ScopedKernelTimer timer("hash_rays_grad", stream, (double)n);
+          f2n::check(
+            f2n_hash_rays_grad(
+              pts.data_ptr<float>(), t.data_ptr<float>(), bounds.data_ptr<int32_t>(),
+              rays_d.data_ptr<float>(), fa.table, fa.primes, fa.bias, fa.mul, g.data_ptr<float>(),
+              ld_point, ld_chan, d_o.data_ptr<float>(), d_d.data_ptr<float>(), (int)n_rays, fa.L,
+              fa.F, fa.T, fa.level_stride, 128.f /* hash_3d_anchored.cu:190 */, stream),
+            "f2n_hash_rays_grad");
+        }
       }
     }
     return {g_enc, want_o ? d_o : Tensor(), want_d ? d_d : Tensor(), Tensor(), Tensor(), Tensor(),

@@ -236,6 +236,47 @@ int f2n_hash_rays_grad(
   float * d_rays_d, int n_rays, int L, int F, uint32_t T, int64_t level_stride, float grad_scale,
   void * stream);
 
+/* The encoding's true derivative with respect to position, as a vector-Jacobian product with the
+ * gradient of the encoding: the trilinear interpolant of Hash3DAnchoredForwardKernel
+ * (src/hash_3d_anchored.cu:25-93), enc[p, lF+k] = sum_d w_d(frac_l) f_{l,d,k}, differentiated in f32
+ * with all three axes' interpolation weights,
+ *   pts_grad[p] = sum_l mul_l sum_pairs (s_hi - s_lo) w_pair,  s_d = sum_k g[p, lF+k] f_{l,d,k},
+ * in the evaluation order of f2n_density_grad (the same device function, with the sample's own
+ * g[p, lF .. lF+F) where that entry takes w0; g is read as unscaled f32: no f16 rounding, no
+ * grad_scale).  This is NOT quirk Q5: it replaces the form of src/hash_3d_anchored.cu:138-143 (the
+ * corner features signed by the corner bit, the other two axes' weights missing, every term rounded
+ * to f16), which f2n_hash_bwd's pts_grad keeps, for callers that ask for the derivative itself.  The
+ * magnitude differs: Q5 is about 4 times the derivative taken at the centre of the other two axes.
+ *   pts        [n,3] f32, ALREADY CONTRACTED, as f2n_hash_bwd takes it
+ *   table_f16 .. level_stride: as f2n_hash_bwd; grad_out element (p, c) at
+ *              grad_out[p*g_ld_point + c*g_ld_chan], f32
+ *   pts_grad   [n,3] f32, overwritten: the levels' terms in level order, the first onto 0.  No
+ *              contraction Jacobian: f2n_contract_bwd follows, as it follows f2n_hash_bwd.
+ * One lane per point, no atomics, no workspace, the same bits on every run; n == 0 is F2N_OK without
+ * a launch. */
+int f2n_hash_pts_grad_exact(
+  const float * pts, const uint16_t * table_f16, const int32_t * primes, const float * bias,
+  const float * mul, const float * grad_out, int64_t g_ld_point, int64_t g_ld_chan,
+  float * pts_grad, int64_t n, int L, int F, uint32_t T, int64_t level_stride, void * stream);
+
+/* f2n_hash_rays_grad with the encoding's true derivative: per kept sample the vector
+ * f2n_hash_pts_grad_exact forms (the interpolant of src/hash_3d_anchored.cu:25-93 differentiated with
+ * all three axes' weights, f2n_density_grad's evaluation order, g unscaled f32), then, exactly as in
+ * f2n_hash_rays_grad, the contraction's Jacobian at the raw point (NaN at |p| == 0), d o += dp,
+ * m = fmaf(t, dp, m), the wave sums and d d = (m - n (n.m)) / |d|.  This is NOT quirk Q5: it
+ * replaces the form of src/hash_3d_anchored.cu:138-143 that f2n_hash_rays_grad keeps.  Arguments as
+ * f2n_hash_rays_grad, without grad_scale (pts RAW).  d_rays_o, d_rays_d [n_rays, 3] overwritten; a
+ * ray with an empty segment gets zeros, a non-finite sample poisons its own ray only.  Still not
+ * formed: the path through dt (quirk Q7), a gradient through the SH directions
+ * (src/sh_shader.cu:105-115) and a gradient to t.
+ * One wavefront per ray, one launch, no atomics, no workspace, the same bits on every run;
+ * n_rays == 0 is F2N_OK without a launch. */
+int f2n_hash_rays_grad_exact(
+  const float * pts, const float * t, const int32_t * bounds, const float * rays_d,
+  const uint16_t * table_f16, const int32_t * primes, const float * bias, const float * mul,
+  const float * grad_out, int64_t g_ld_point, int64_t g_ld_chan, float * d_rays_o,
+  float * d_rays_d, int n_rays, int L, int F, uint32_t T, int64_t level_stride, void * stream);
+
 /* The density logit's spatial gradient: d(logit)/d(p) of the trilinear interpolant the forward
  * computes (src/hash_3d_anchored.cu:25-93 behind the contraction of src/hash_3d_anchored.cpp:79-82)
  * followed by row 0 of the field head,

@@ -11,7 +11,15 @@
                               of the camera draw, f2n_cam_pose_grad and f2n_pose_compose_bwd.
                    Median of --reps after --warmup (defaults 5 and 2).  --arms / --shapes pick a
                    subset (one arm and one shape per rocprofv3 --kernel-trace --stats run gives that
-                   arm's kernel times).
+                   arm's kernel times).  --exact-grad switches the field's exact_point_grad on for
+                   the whole part (the leaf and refiner arms then run f2n_hash_rays_grad_exact).
+
+  --part kernels   f2n_hash_rays_grad (quirk Q5) against f2n_hash_rays_grad_exact on the same kept
+                   samples, at the same two shapes: the samples a validation render of the step part's
+                   field keeps for a batch drawn from the camera ring, a random d(enc) in the
+                   channel-major storage the shade backward leaves.  The two kernels alternate in one
+                   process, --inner launches (default 20) per timed window, --reps windows each
+                   (at least five pairs), device events around each window.
 
   --part recover   The analytic sphere scene and the ring of 24 cameras of microbench_occupancy.py
                    --part train.  The training poses are the true ones displaced by a known noise
@@ -20,6 +28,8 @@
                    one without from the same seed.  Every --report-every iterations: the mean rotation
                    error (angle of R_est R_true^T) and the mean translation error over the displaced
                    cameras, and the PSNR of four held-out views rendered from their true poses.
+                   --exact-grad: the refiner run receives the encoding's true derivative.  Its
+                   magnitude is a third to a quarter of Q5's: --pose-lr is NOT rescaled.
 
 Prints one JSON line per measurement (also appended to --out).
 """
@@ -38,6 +48,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import microbench_occupancy as scene  # noqa: E402  (the sphere scene, the camera ring, the timers)
 
 N_CAMS = 24
+SHAPES = (("c4_batch", 512, 1024, 1.0 / 256), ("headline_chunk", 65536, 128, 4.0 / 128))
 
 
 def intrinsics(hw, dev):
@@ -49,8 +60,7 @@ def part_step(host, dev, args):
     hw = args.image
     Kc, intr = intrinsics(hw, dev)
     poses = scene.ring_poses(N_CAMS, 0.9, 0.25).to(dev)
-    for name, n_rays, S, step in (("c4_batch", 512, 1024, 1.0 / 256),
-                                  ("headline_chunk", 65536, 128, 4.0 / 128)):
+    for name, n_rays, S, step in SHAPES:
         if name not in args.shapes.split(","):
             continue
         host.manual_seed(7)
@@ -59,6 +69,7 @@ def part_step(host, dev, args):
         with torch.no_grad():
             hr.named_parameters()["scene_field.feat_pool"].normal_(0.0, 0.1)
         hr.set_fused_ray_grad(True)
+        hr.set_exact_ray_grad(args.exact_grad)
         refiner = host.PoseRefiner(poses)
         fixed = torch.zeros(N_CAMS, dtype=torch.int32, device=dev)
         fixed[0] = 1
@@ -90,7 +101,7 @@ def part_step(host, dev, args):
         arms = {"plain": plain, "leaf": leaf, "refiner": refined}
         ts = scene.alternating({k: arms[k] for k in args.arms.split(",")}, args.reps, args.warmup)
         rec = {"part": "step", "shape": name, "n_rays": n_rays, "samples_per_ray": S,
-               "n_cameras": N_CAMS, "kept_samples": kept}
+               "n_cameras": N_CAMS, "kept_samples": kept, "exact_grad": args.exact_grad}
         for k, v in ts.items():
             rec["step_ms_" + k] = scene.med(v)
             rec["step_min_ms_" + k] = round(v[0], 4)
@@ -98,6 +109,61 @@ def part_step(host, dev, args):
         if len(ts) == 3:
             rec["route_and_hash_rays_grad_ms"] = round(rec["step_ms_leaf"] - rec["step_ms_plain"], 4)
             rec["refiner_over_leaf_ms"] = round(rec["step_ms_refiner"] - rec["step_ms_leaf"], 4)
+        scene.emit(rec, args.out)
+
+
+def part_kernels(host, capi, dev, args):
+    hw = args.image
+    Kc, intr = intrinsics(hw, dev)
+    poses = scene.ring_poses(N_CAMS, 0.9, 0.25).to(dev)
+    L, F = 16, 2
+    for name, n_rays, S, step in SHAPES:
+        if name not in args.shapes.split(","):
+            continue
+        host.manual_seed(7)
+        torch.manual_seed(7)
+        hr = host.Renderer(N_CAMS, n_levels=L, n_channels=F, log2_table=19, max_samples=S, step=step)
+        with torch.no_grad():
+            hr.named_parameters()["scene_field.feat_pool"].normal_(0.0, 0.1)
+        o, d, _, cam = host.sample_random_rays(poses, intr, hw, hw, n_rays)
+        with torch.no_grad():
+            bounds = hr.render(o, d, None, "validate")[3].contiguous()
+            pts_all, _, _, t_all, b_all = hr.pts_sampler.get_samples(o, d, "validate", None)
+        length = (bounds[:, 1] - bounds[:, 0]).long()
+        k = torch.arange(S, device=dev)[None]
+        keep = k < length[:, None]
+        src = (b_all[:, :1].long() + k)[keep]                   # a ray keeps a prefix of its samples
+        pts, t = pts_all[src].contiguous(), t_all[src].contiguous()
+        n = int(pts.shape[0])
+        assert n == int(bounds[-1, 1]) and n > 0
+        f = hr.scene_field
+        fa = (f.table_f16(), f.prim_pool, f.bias_pool.detach(), f.level_mul)
+        shape = (L, F, f.local_size, f.level_stride)
+        g = torch.Generator(device=dev).manual_seed(5)
+        g_enc = torch.randn(L * F, n, device=dev, generator=g) * 5e-3
+        outs = {a: (torch.empty(n_rays, 3, device=dev), torch.empty(n_rays, 3, device=dev))
+                for a in ("q5", "exact")}
+
+        def q5():
+            for _ in range(args.inner):
+                capi.call("hash_rays_grad", pts, t, bounds, d, *fa, g_enc, 1, n, *outs["q5"], n_rays, *shape,
+                          128.0)
+
+        def exact():
+            for _ in range(args.inner):
+                capi.call("hash_rays_grad_exact", pts, t, bounds, d, *fa, g_enc, 1, n, *outs["exact"], n_rays,
+                          *shape)
+
+        ts = scene.alternating({"hash_rays_grad": q5, "hash_rays_grad_exact": exact}, max(args.reps, 5),
+                               args.warmup)
+        rec = {"part": "kernels", "shape": name, "n_rays": n_rays, "samples_per_ray": S, "kept_samples": n,
+               "L": L, "F": F, "log2_T": 19, "pairs": max(args.reps, 5), "launches_per_window": args.inner}
+        for key, v in ts.items():
+            per = [x / args.inner for x in v]
+            rec[key + "_ms"] = scene.med(per)
+            rec[key + "_min_max_ms"] = [round(per[0], 4), round(per[-1], 4)]
+        rec["exact_over_q5"] = round(rec["hash_rays_grad_exact_ms"] / rec["hash_rays_grad_ms"], 3)
+        rec["norm_ratio_q5_over_exact_d_o"] = round(float(outs["q5"][0].norm() / outs["exact"][0].norm()), 3)
         scene.emit(rec, args.out)
 
 
@@ -145,6 +211,7 @@ def recover_once(host, dev, args, refine):
                        max_samples=scene.S, step=scene.STEP)
     hr.set_dense_first_pass(-1)
     hr.set_fused_ray_grad(True)
+    hr.set_exact_ray_grad(args.exact_grad and refine)
     opt = hr.make_fused_adam(args.lr)
     refiner = pose_opt = None
     if refine:
@@ -166,7 +233,8 @@ def recover_once(host, dev, args, refine):
                     "rot_err_deg": round(rot, 4), "pos_err": round(pos, 5),
                     "psnr_heldout": round(scene.psnr(views, truth), 3),
                     "rot_noise_deg": round(math.degrees(args.rot_noise), 3),
-                    "pos_noise": args.pos_noise, "pose_lr": args.pose_lr if refine else None},
+                    "pos_noise": args.pos_noise, "pose_lr": args.pose_lr if refine else None,
+                    "exact_grad": bool(args.exact_grad and refine)},
                    args.out)
 
     report(0)
@@ -187,7 +255,7 @@ def recover_once(host, dev, args, refine):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", default="step", choices=["step", "recover"])
+    ap.add_argument("--part", default="step", choices=["step", "kernels", "recover"])
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--arms", default="plain,leaf,refiner",
@@ -200,14 +268,22 @@ def main():
     ap.add_argument("--pose-lr", type=float, default=1e-3)
     ap.add_argument("--rot-noise", type=float, default=0.03, help="radians")
     ap.add_argument("--pos-noise", type=float, default=0.02)
+    ap.add_argument("--exact-grad", action="store_true",
+                    help="Hash3DAnchoredOptions::exact_point_grad on: the encoding's true derivative")
+    ap.add_argument("--inner", type=int, default=20, help="--part kernels: launches per timed window")
+    ap.add_argument("--no-baseline", action="store_true",
+                    help="--part recover: skip the run without a refiner")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
-    host = importlib.import_module("f2-nerf_amd").load_host()
+    pkg = importlib.import_module("f2-nerf_amd")
+    host = pkg.load_host()
     if args.part == "step":
         part_step(host, dev, args)
+    elif args.part == "kernels":
+        part_kernels(host, pkg.capi, dev, args)
     else:
-        for refine in (True, False):
+        for refine in (True,) if args.no_baseline else (True, False):
             recover_once(host, dev, args, refine)
 
 
