@@ -441,12 +441,16 @@ public:
 
 // ShadeFn on the sampler's dense [n_rays, S] grid, S % 64 == 0 (f2n_shade_fwd_rays /
 // f2n_shade_bwd_rays): `ray_img` [n_rays] in place of the per-sample ids, the rest as above.
+// ray_const (with dirs_per_ray): the per-ray half of the hidden layer is formed once per ray into a
+// [n_rays, 80] buffer (f2n_shade_ray_const) that both network kernels load
+// (f2n_shade_fwd_rays_const / f2n_shade_bwd_rays_const); the same bits.
 class ShadeRaysFn : public torch::autograd::Function<ShadeRaysFn>
 {
 public:
   static variable_list forward(
     AutogradContext * ctx, Tensor enc, Tensor dirs, Tensor ray_img, int64_t S, Tensor w_h,
-    Tensor b_h, Tensor w1, Tensor b1, Tensor w2, Tensor b2, Tensor app_emb, bool dirs_per_ray)
+    Tensor b_h, Tensor w1, Tensor b1, Tensor w2, Tensor b2, Tensor app_emb, bool dirs_per_ray,
+    bool ray_const)
   {
     TORCH_CHECK(enc.is_cuda() && enc.scalar_type() == torch::kFloat32 && enc.dim() == 2, "enc");
     const int64_t n = enc.size(0);
@@ -475,18 +479,39 @@ public:
         w2.size(0) == 3 && w2.size(1) == 64,
       "shade: layer shapes must be 16xC, 64x32, 3x64");
     Tensor logit = torch::empty({n}, enc.options()), rgb = torch::empty({n, 3}, enc.options());
+    TORCH_CHECK(!ray_const || dirs_per_ray, "shade_rays: the per-ray constant needs one direction per ray");
+    Tensor rconst;  // [n_rays, 80]: c[64] and SH16[16] of every ray, from the caching allocator
+    if (ray_const) {
+      torch::NoGradGuard no_grad;
+      rconst = torch::empty({(int64_t)n_rays, F2N_SHADE_RAY_CONST_FLOATS}, enc.options());
+    }
     {
     f2n::ScopedKernelTimer timer("shade_fwd", f2n::current_stream(enc_cm), (double)n);
-    f2n::check(
-      (dirs_per_ray ? f2n_shade_fwd_raydirs : f2n_shade_fwd_rays)(
-        enc_cm.data_ptr<float>(), C, dirs.data_ptr<float>(), use_emb ? f2n::iptr(ray_img) : nullptr,
-        f2n::fptr(w_h), f2n::fptr(b_h), f2n::fptr(w1), f2n::fptr(b1), f2n::fptr(w2), f2n::fptr(b2),
-        f2n::fptr(emb), logit.data_ptr<float>(), rgb.data_ptr<float>(), n_rays, (int)S,
-        f2n::current_stream(enc_cm)),
-      "f2n_shade_fwd_rays");
+    if (ray_const) {
+      f2n::check(
+        f2n_shade_ray_const(
+          dirs.data_ptr<float>(), f2n::fptr(w1), f2n::fptr(b1), rconst.data_ptr<float>(), n_rays,
+          f2n::current_stream(enc_cm)),
+        "f2n_shade_ray_const");
+      f2n::check(
+        f2n_shade_fwd_rays_const(
+          enc_cm.data_ptr<float>(), C, rconst.data_ptr<float>(), use_emb ? f2n::iptr(ray_img) : nullptr,
+          f2n::fptr(w_h), f2n::fptr(b_h), f2n::fptr(w1), f2n::fptr(b1), f2n::fptr(w2), f2n::fptr(b2),
+          f2n::fptr(emb), logit.data_ptr<float>(), rgb.data_ptr<float>(), n_rays, (int)S,
+          f2n::current_stream(enc_cm)),
+        "f2n_shade_fwd_rays_const");
+    } else {
+      f2n::check(
+        (dirs_per_ray ? f2n_shade_fwd_raydirs : f2n_shade_fwd_rays)(
+          enc_cm.data_ptr<float>(), C, dirs.data_ptr<float>(), use_emb ? f2n::iptr(ray_img) : nullptr,
+          f2n::fptr(w_h), f2n::fptr(b_h), f2n::fptr(w1), f2n::fptr(b1), f2n::fptr(w2), f2n::fptr(b2),
+          f2n::fptr(emb), logit.data_ptr<float>(), rgb.data_ptr<float>(), n_rays, (int)S,
+          f2n::current_stream(enc_cm)),
+        "f2n_shade_fwd_rays");
+    }
     }
     ctx->save_for_backward(
-      {enc_cm, dirs, use_emb ? ray_img : Tensor(), w_h, b_h, w1, b1, w2, b2, emb});
+      {enc_cm, dirs, use_emb ? ray_img : Tensor(), w_h, b_h, w1, b1, w2, b2, emb, rconst});
     ctx->saved_data["S"] = S;
     ctx->saved_data["dirs_per_ray"] = dirs_per_ray;
     return {logit, rgb};
@@ -496,7 +521,7 @@ public:
   {
     auto sv = ctx->get_saved_variables();
     Tensor &enc_cm = sv[0], &dirs = sv[1], &ray_img = sv[2], &w_h = sv[3], &b_h = sv[4],
-           &w1 = sv[5], &b1 = sv[6], &w2 = sv[7], &b2 = sv[8], &emb = sv[9];
+           &w1 = sv[5], &b1 = sv[6], &w2 = sv[7], &b2 = sv[8], &emb = sv[9], &rconst = sv[10];
     const int C = (int)enc_cm.size(0);
     const int64_t n = enc_cm.size(1), S = ctx->saved_data["S"].toInt();
     const bool dirs_per_ray = ctx->saved_data["dirs_per_ray"].toBool();
@@ -525,19 +550,33 @@ public:
     Tensor g_emb = use_emb ? take(emb, sizes[6]) : Tensor();  // undefined = no gradient
     {
     f2n::ScopedKernelTimer timer("shade_bwd", f2n::current_stream(enc_cm), (double)n);
-    f2n::check(
-      (dirs_per_ray ? f2n_shade_bwd_raydirs : f2n_shade_bwd_rays)(
-        enc_cm.data_ptr<float>(), C, dirs.data_ptr<float>(), use_emb ? f2n::iptr(ray_img) : nullptr,
-        f2n::fptr(w_h), f2n::fptr(b_h), f2n::fptr(w1), f2n::fptr(b1), f2n::fptr(w2), f2n::fptr(b2),
-        f2n::fptr(emb), f2n::fptr(d_logit), f2n::fptr(d_rgb), d_enc_cm.data_ptr<float>(),
-        g_w_h.data_ptr<float>(), g_b_h.data_ptr<float>(), g_w1.data_ptr<float>(),
-        g_b1.data_ptr<float>(), g_w2.data_ptr<float>(), g_b2.data_ptr<float>(),
-        use_emb ? g_emb.data_ptr<float>() : nullptr, (int)(n / S), (int)S,
-        f2n::current_stream(enc_cm)),
-      "f2n_shade_bwd_rays");
+    if (rconst.defined()) {
+      f2n::check(
+        f2n_shade_bwd_rays_const(
+          enc_cm.data_ptr<float>(), C, dirs.data_ptr<float>(), rconst.data_ptr<float>(),
+          use_emb ? f2n::iptr(ray_img) : nullptr, f2n::fptr(w_h), f2n::fptr(b_h), f2n::fptr(w1),
+          f2n::fptr(b1), f2n::fptr(w2), f2n::fptr(b2), f2n::fptr(emb), f2n::fptr(d_logit),
+          f2n::fptr(d_rgb), d_enc_cm.data_ptr<float>(), g_w_h.data_ptr<float>(),
+          g_b_h.data_ptr<float>(), g_w1.data_ptr<float>(), g_b1.data_ptr<float>(),
+          g_w2.data_ptr<float>(), g_b2.data_ptr<float>(),
+          use_emb ? g_emb.data_ptr<float>() : nullptr, (int)(n / S), (int)S,
+          f2n::current_stream(enc_cm)),
+        "f2n_shade_bwd_rays_const");
+    } else {
+      f2n::check(
+        (dirs_per_ray ? f2n_shade_bwd_raydirs : f2n_shade_bwd_rays)(
+          enc_cm.data_ptr<float>(), C, dirs.data_ptr<float>(), use_emb ? f2n::iptr(ray_img) : nullptr,
+          f2n::fptr(w_h), f2n::fptr(b_h), f2n::fptr(w1), f2n::fptr(b1), f2n::fptr(w2), f2n::fptr(b2),
+          f2n::fptr(emb), f2n::fptr(d_logit), f2n::fptr(d_rgb), d_enc_cm.data_ptr<float>(),
+          g_w_h.data_ptr<float>(), g_b_h.data_ptr<float>(), g_w1.data_ptr<float>(),
+          g_b1.data_ptr<float>(), g_w2.data_ptr<float>(), g_b2.data_ptr<float>(),
+          use_emb ? g_emb.data_ptr<float>() : nullptr, (int)(n / S), (int)S,
+          f2n::current_stream(enc_cm)),
+        "f2n_shade_bwd_rays");
+    }
     }
     return {d_enc_cm.t(), Tensor(), Tensor(), Tensor(), g_w_h, g_b_h, g_w1, g_b1, g_w2, g_b2, g_emb,
-            Tensor()};
+            Tensor(), Tensor()};
   }
 };
 
@@ -741,9 +780,13 @@ f2n::ShadeOut f2n::shade_rays(
   const Tensor no_img = torch::empty({0}, f2n::int_on(enc.device()));
   const Tensor no_emb = torch::empty({0, 16}, enc.options());
   const bool use_emb = ray_img.defined() && app_emb.defined();
+  // one direction per ray (the lean dense route) that carries no gradient: the per-ray half of the
+  // hidden layer is formed once per ray.  F2N_OPT_DENSE_LEAN = 1 hands over per-sample directions
+  // and so keeps the kernels that form it per stride.
+  const bool ray_const = dirs_per_ray && !dirs.requires_grad();
   auto out = ShadeRaysFn::apply(
     enc, dirs, use_emb ? ray_img : no_img, S, w_h, b_h, w1, b1, w2, b2, use_emb ? app_emb : no_emb,
-    dirs_per_ray);
+    dirs_per_ray, ray_const);
   return {out[0], out[1]};
 }
 

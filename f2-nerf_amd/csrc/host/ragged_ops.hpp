@@ -102,7 +102,11 @@ ShadeOut shade(
 // row, the SH half of the hidden layer) is done once per 64 samples (f2n_shade_fwd_rays /
 // f2n_shade_bwd_rays).  logit equals shade()'s bit for bit, rgb and the gradients to rounding.
 // dirs_per_ray: `dirs` is [n_rays, 3], one direction per ray (f2n_shade_fwd_raydirs /
-// f2n_shade_bwd_raydirs): the same kernels and, for the same directions, the same bits.
+// f2n_shade_bwd_raydirs): the same kernels and, for the same directions, the same bits.  Such
+// directions that carry no gradient take the per-ray constant: the forward allocates [n_rays, 80],
+// runs f2n_shade_ray_const once inside its own timed operator and calls f2n_shade_fwd_rays_const,
+// the backward calls f2n_shade_bwd_rays_const on the saved buffer -- the same bits again, 16 matrix
+// products per stride fewer in each kernel.
 ShadeOut shade_rays(
   const Tensor & enc, const Tensor & dirs, const Tensor & ray_img, int64_t S, const Tensor & w_h,
   const Tensor & b_h, const Tensor & w1, const Tensor & b1, const Tensor & w2, const Tensor & b2,

@@ -626,3 +626,53 @@ extern "C" int f2n_shade_bwd_raydirs(
     enc_cm, C, ray_dirs, ray_img, w_h, b_h, w1, b1, w2, b2, app_emb, d_logit, d_rgb, d_enc_cm,
     g_w_h, g_b_h, g_w1, g_b1, g_w2, g_b2, g_app_emb, n_rays, S, true, stream);
 }
+
+// ---- the ray-uniform forms with the per-ray constant formed once per ray (shade_mfma.hip)
+
+extern "C" int f2n_shade_ray_const(
+  const float * ray_dirs, const float * w1, const float * b1, float * ray_const, int n_rays,
+  void * stream)
+{
+  if (n_rays < 0) return F2N_E_INVALID_ARG;
+  if (n_rays == 0) return F2N_OK;
+  if (!ray_dirs || !w1 || !b1 || !ray_const) return F2N_E_INVALID_ARG;
+  return f2n_detail::launch_shade_ray_const(ray_dirs, w1, b1, ray_const, n_rays, (hipStream_t)stream);
+}
+
+extern "C" int f2n_shade_fwd_rays_const(
+  const float * enc_cm, int C, const float * ray_const, const int32_t * ray_img, const float * w_h,
+  const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
+  const float * app_emb, float * logit, float * rgb, int n_rays, int S, void * stream)
+{
+  if (n_rays < 0 || S <= 0 || S % 64 != 0) return F2N_E_INVALID_ARG;
+  if (C != 8 && C != 16 && C != 32 && C != 64) return F2N_E_UNSUPPORTED;
+  if (n_rays == 0) return F2N_OK;
+  if (!enc_cm || !ray_const || !w_h || !b_h || !w1 || !b1 || !w2 || !b2 || !logit || !rgb)
+    return F2N_E_INVALID_ARG;
+  if (!f2n_detail::shade_bwd_mfma_supports(C, (int64_t)n_rays * S)) return F2N_E_UNSUPPORTED;
+  return f2n_detail::launch_shade_fwd_mfma_rays_const(
+    enc_cm, C, ray_const, ray_img, w_h, b_h, w1, b1, w2, b2, app_emb, logit, rgb, n_rays, S,
+    (hipStream_t)stream);
+}
+
+extern "C" int f2n_shade_bwd_rays_const(
+  const float * enc_cm, int C, const float * ray_dirs, const float * ray_const,
+  const int32_t * ray_img, const float * w_h, const float * b_h, const float * w1, const float * b1,
+  const float * w2, const float * b2, const float * app_emb, const float * d_logit,
+  const float * d_rgb, float * d_enc_cm, float * g_w_h, float * g_b_h, float * g_w1, float * g_b1,
+  float * g_w2, float * g_b2, float * g_app_emb, int n_rays, int S, void * stream)
+{
+  if (n_rays < 0 || S <= 0 || S % 64 != 0) return F2N_E_INVALID_ARG;
+  if (C != 8 && C != 16 && C != 32 && C != 64) return F2N_E_UNSUPPORTED;
+  if (n_rays == 0) return F2N_OK;
+  if (!enc_cm || !ray_dirs || !ray_const || !w_h || !b_h || !w1 || !b1 || !w2 || !b2 || !d_logit ||
+      !d_rgb || !d_enc_cm || !g_w_h || !g_b_h || !g_w1 || !g_b1 || !g_w2 || !g_b2)
+    return F2N_E_INVALID_ARG;
+  if (app_emb && ray_img && !g_app_emb) return F2N_E_INVALID_ARG;
+  if (!f2n_detail::shade_bwd_mfma_supports(C, (int64_t)n_rays * S)) return F2N_E_UNSUPPORTED;
+  // (every instantiation of the loading kernels fits the registers of its forming twin, so no launch
+  // keeps the forming kernel and ray_dirs is not read)
+  return f2n_detail::launch_shade_bwd_mfma_rays_const(
+    enc_cm, C, ray_const, ray_img, w_h, b_h, w1, b1, w2, b2, app_emb, d_logit, d_rgb, d_enc_cm, g_w_h,
+    g_b_h, g_w1, g_b1, g_w2, g_b2, g_app_emb, n_rays, S, (hipStream_t)stream);
+}

@@ -46,6 +46,16 @@
 // F2N_SHADE_BWD_TWO_WAVES_MIN_SAMPLES samples (few strides per wave) take the one-wave form, which
 // is faster there.  The data-gradient chain per sample is unchanged:
 // d_enc is bit-identical to the TS = 4 form, the parameter gradients differ in the order of sums.
+//
+// The per-ray constant.  On a dense [n_rays, S] grid the ray-uniform kernels (RAYS) form the SH half
+// of the hidden layer, c = b1 + w1[:, 16:32] . SH16(dir), once per stride: 16 products whose 16
+// columns are all the same vector, twice per ray forward and four times backward at S = 128.  Where
+// the caller has one direction per ray, shade_ray_const_kernel forms c ONCE per ray -- a wave takes
+// 16 rays as the 16 columns of those same products, so a row holds the bits the kernels form
+// themselves -- into [n_rays, 80] (c[64], then SH16[16]), and shade_*_mfma_rays_kernel_const (the
+// same bodies, RC = true) load it: 160 instead of 176 products per 64-sample stride forward, 154
+// instead of 170 per 32-sample stride backward, no direction loads, no sh_basis.  The kernels that
+// form c stay as they were, for per-sample directions and for callers of the older entries.
 #include "shade_mfma.hiph"
 #include "shade_fwd_mfma.hiph"
 
@@ -55,6 +65,16 @@
 
 namespace
 {
+
+constexpr int kRayConst = F2N_SHADE_RAY_CONST_FLOATS;  // floats per ray of the per-ray constant: c[64], SH16[16]
+// The forward loads c for the first kRcEarly neuron tiles with the stride's encoding, ahead of the
+// head layer, and for the rest behind it, with the embedding row.  All four ahead is 16 live registers
+// where the forming kernel holds a direction: 2 to 8 registers MORE than that kernel in six of the
+// sixteen instantiations (C = 32 at four waves per SIMD: 98 against 96).  All four behind fits
+// everywhere but leaves tile 0 waiting for memory: 0.412 against 0.395 ms per 8.4 M samples.  One
+// ahead fits every instantiation with room (C = 32: 90), and tiles 1..3 have tile 0's 32 products
+// to arrive in.
+constexpr int kRcEarly = 1;
 
 // TS = 16-sample column tiles per stride: 2 (the default, two waves per SIMD) or 4 (round 3, one).
 template <int C, int TS>
@@ -179,10 +199,18 @@ __device__ __forceinline__ float quarter_sum(float v)
 // The head layer is untouched (logit and d_h are the per-sample form's terms in the same order); pre,
 // d_enc and the parameter gradients are the same f32 terms added in another order (the SH part first
 // instead of last, d w1[:, 16:] summed per stride before the product).
-template <int C, int V, bool WIDE, int TS, bool RAYS>
+//
+// RC (with RAYS; f2n_shade_bwd_rays_const): c and SH16(dir) were formed once per ray by
+// shade_ray_const_kernel into `ray_const` [n_rays, 80].  load_inputs fetches the stride's c -- one
+// 16-byte load per neuron tile, the address wave-uniform apart from q -- and its SH row m; the
+// direction loads, sh_basis and the 16 products that formed c drop out, and the hidden layer's
+// accumulators start from the loaded registers.  The buffer's c is a column of the same products, so
+// every result keeps its bits.  `dirs` is not read.
+template <int C, int V, bool WIDE, int TS, bool RAYS, bool RC = false>
 __device__ __forceinline__ void shade_bwd_mfma_body(
   const float * __restrict__ enc, const float * __restrict__ dirs,
-  const int32_t * __restrict__ sample_img, const float * __restrict__ p_w_h,
+  const float * __restrict__ ray_const, const int32_t * __restrict__ sample_img,
+  const float * __restrict__ p_w_h,
   const float * __restrict__ p_b_h, const float * __restrict__ p_w1,
   const float * __restrict__ p_b1, const float * __restrict__ p_w2,
   const float * __restrict__ p_b2, const float * __restrict__ p_emb,
@@ -191,6 +219,7 @@ __device__ __forceinline__ void shade_bwd_mfma_body(
   float * __restrict__ g_b1, float * __restrict__ g_w2, float * __restrict__ g_b2,
   float * __restrict__ g_emb, int64_t n, int n_per_ray, int dir_per_ray)
 {
+  static_assert(RAYS || !RC, "the per-ray constant belongs to the ray-uniform form");
   using S = MShape<C, TS>;
   constexpr int kS1 = S::kS1, kM6 = S::kM6, kP = S::kP, kStride = S::kStride;
   __shared__ __attribute__((aligned(16))) float lds_all[S::kLdsFloats];
@@ -308,6 +337,8 @@ __device__ __forceinline__ void shade_bwd_mfma_body(
 #pragma unroll
   for (int T = 0; T < TS; T++) img[T] = 0;
   float dir[3];
+  f32x4 cR[4];     // RC: the stride's c, rows 16M+4q+r
+  float shR = 0.f; // RC: the stride's SH row m
   // SH: lane l evaluates sample s0 + l % kStride (at TS = 2 both halves of the wave the same 32)
   const int lS = lane % kStride;
   auto load_inputs = [&](int64_t st_, float (&eB_)[kS1][TS], int (&img_)[TS], float (&dir_)[3]) {
@@ -319,11 +350,18 @@ __device__ __forceinline__ void shade_bwd_mfma_body(
 #pragma unroll
         for (int T = 0; T < TS; T++) eB_[t][T] = ld_row(enc + (int64_t)t * n, (sc + 16 * T + m) * 4 + cE);
       // the stride's ray (a scalar): its image id, and its row of a per-ray `dirs`
-      const uint32_t ray = (has_emb || dir_per_ray) ? sc / (uint32_t)n_per_ray : 0u;
+      const uint32_t ray = (RC || has_emb || dir_per_ray) ? sc / (uint32_t)n_per_ray : 0u;
       if (has_emb) {
         const int id = sample_img[ray];
 #pragma unroll
         for (int T = 0; T < TS; T++) img_[T] = id;
+      }
+      if constexpr (RC) {
+        const float * rc = ray_const + (int64_t)ray * kRayConst;
+#pragma unroll
+        for (int M = 0; M < 4; M++) cR[M] = *reinterpret_cast<const f32x4 *>(rc + 16 * M + 4 * q);
+        shR = rc[kHid + m];
+        return;
       }
       const int64_t drow = dir_per_ray ? (int64_t)ray : (int64_t)sc;
 #pragma unroll
@@ -402,8 +440,10 @@ __device__ __forceinline__ void shade_bwd_mfma_body(
       // directly (at TS = 2 the lower half of the wave rows 16..23, the upper half rows 24..31)
       // RAYS: one direction per stride, every lane evaluates it and keeps the rows it supplies
       float sh[16];
-      sh_basis<4>(dir[0], dir[1], dir[2], sh);
-      if constexpr (RAYS) {
+      if constexpr (!RC) sh_basis<4>(dir[0], dir[1], dir[2], sh);
+      if constexpr (RC) {
+        shm = shR;
+      } else if constexpr (RAYS) {
 #pragma unroll
         for (int t = 0; t < 4; t++)
           shq[t] = pick4(q, sh[t], sh[4 + t], sh[8 + t], sh[12 + t]);
@@ -434,13 +474,18 @@ __device__ __forceinline__ void shade_bwd_mfma_body(
     f32x4 pre[4][TS];
     if constexpr (RAYS) {
       // the SH half once for one sample tile (four independent chains), then the shading features
+      if constexpr (RC) {
 #pragma unroll
-      for (int M = 0; M < 4; M++)
-        pre[M][0] = *reinterpret_cast<const f32x4 *>(lds_w + S::oB1 + 16 * M + 4 * q);
+        for (int M = 0; M < 4; M++) pre[M][0] = cR[M];
+      } else {
 #pragma unroll
-      for (int t = 4; t < 8; t++)
+        for (int M = 0; M < 4; M++)
+          pre[M][0] = *reinterpret_cast<const f32x4 *>(lds_w + S::oB1 + 16 * M + 4 * q);
 #pragma unroll
-        for (int M = 0; M < 4; M++) pre[M][0] = mfma16(W(S::oWA2 + M * 8 + t), shq[t - 4], pre[M][0]);
+        for (int t = 4; t < 8; t++)
+#pragma unroll
+          for (int M = 0; M < 4; M++) pre[M][0] = mfma16(W(S::oWA2 + M * 8 + t), shq[t - 4], pre[M][0]);
+      }
 #pragma unroll
       for (int M = 0; M < 4; M++) {
 #pragma unroll
@@ -864,8 +909,8 @@ __device__ __forceinline__ void shade_bwd_mfma_body(
   }
 }
 
-#define F2N_SHADE_BWD_PARAMS(IMG)                                                                     \
-  const float * __restrict__ enc, const float * __restrict__ dirs, const int32_t * __restrict__ IMG,  \
+#define F2N_SHADE_BWD_PARAMS(DIRS, IMG)                                                               \
+  const float * __restrict__ enc, const float * __restrict__ DIRS, const int32_t * __restrict__ IMG,  \
     const float * __restrict__ p_w_h, const float * __restrict__ p_b_h,                               \
     const float * __restrict__ p_w1, const float * __restrict__ p_b1,                                 \
     const float * __restrict__ p_w2, const float * __restrict__ p_b2,                                 \
@@ -873,25 +918,35 @@ __device__ __forceinline__ void shade_bwd_mfma_body(
     const float * __restrict__ d_rgb, float * __restrict__ d_enc, float * __restrict__ g_w_h,         \
     float * __restrict__ g_b_h, float * __restrict__ g_w1, float * __restrict__ g_b1,                 \
     float * __restrict__ g_w2, float * __restrict__ g_b2, float * __restrict__ g_emb
-#define F2N_SHADE_BWD_ARGS(IMG)                                                                       \
-  enc, dirs, IMG, p_w_h, p_b_h, p_w1, p_b1, p_w2, p_b2, p_emb, d_logit, d_rgb, d_enc, g_w_h, g_b_h,    \
-    g_w1, g_b1, g_w2, g_b2, g_emb
+#define F2N_SHADE_BWD_ARGS(DIRS, RCONST, IMG)                                                         \
+  enc, DIRS, RCONST, IMG, p_w_h, p_b_h, p_w1, p_b1, p_w2, p_b2, p_emb, d_logit, d_rgb, d_enc, g_w_h,   \
+    g_b_h, g_w1, g_b1, g_w2, g_b2, g_emb
 
 // per-sample form: any n, one image id per sample
 template <int C, int V, bool WIDE, int TS>
 __global__ __launch_bounds__((MShape<C, TS>::kWaves * 64)) void shade_bwd_mfma_kernel(
-  F2N_SHADE_BWD_PARAMS(sample_img), int64_t n)
+  F2N_SHADE_BWD_PARAMS(dirs, sample_img), int64_t n)
 {
-  shade_bwd_mfma_body<C, V, WIDE, TS, false>(F2N_SHADE_BWD_ARGS(sample_img), n, 0, 0);
+  shade_bwd_mfma_body<C, V, WIDE, TS, false>(F2N_SHADE_BWD_ARGS(dirs, nullptr, sample_img), n, 0, 0);
 }
 
 // ray-uniform form: n = n_rays * S samples in ray-major order, S % 64 == 0, one image id per ray;
 // dir_per_ray: `dirs` is [n_rays, 3], one row per ray (0: [n, 3], the row of the stride's first sample)
 template <int C, int V, bool WIDE, int TS>
 __global__ __launch_bounds__((MShape<C, TS>::kWaves * 64)) void shade_bwd_mfma_rays_kernel(
-  F2N_SHADE_BWD_PARAMS(ray_img), int64_t n, int S, int dir_per_ray)
+  F2N_SHADE_BWD_PARAMS(dirs, ray_img), int64_t n, int S, int dir_per_ray)
 {
-  shade_bwd_mfma_body<C, V, WIDE, TS, true>(F2N_SHADE_BWD_ARGS(ray_img), n, S, dir_per_ray);
+  shade_bwd_mfma_body<C, V, WIDE, TS, true>(F2N_SHADE_BWD_ARGS(dirs, nullptr, ray_img), n, S, dir_per_ray);
+}
+
+// the ray-uniform form with the per-ray constant loaded: `ray_const` [n_rays, 80] from
+// shade_ray_const_kernel in place of the directions
+template <int C, int V, bool WIDE, int TS>
+__global__ __launch_bounds__((MShape<C, TS>::kWaves * 64)) void shade_bwd_mfma_rays_kernel_const(
+  F2N_SHADE_BWD_PARAMS(ray_const, ray_img), int64_t n, int S)
+{
+  shade_bwd_mfma_body<C, V, WIDE, TS, true, true>(
+    F2N_SHADE_BWD_ARGS(nullptr, ray_const, ray_img), n, S, 1);
 }
 #undef F2N_SHADE_BWD_PARAMS
 #undef F2N_SHADE_BWD_ARGS
@@ -911,15 +966,23 @@ __global__ __launch_bounds__((MShape<C, TS>::kWaves * 64)) void shade_bwd_mfma_r
 // are loaded once per stride through wave-uniform addresses, sh_basis runs once, and the SH half of
 // the hidden layer is formed for one sample tile (16 products) and starts all four: 176 products
 // per stride instead of 224, no SH tile in LDS and none of its syncs.  No pre_out in that form.
-template <int C, bool WIDE, int W, bool RAYS>
+//
+// RC (with RAYS; f2n_shade_fwd_rays_const): c comes from `ray_const` [n_rays, 80], written once per
+// ray by shade_ray_const_kernel -- one 16-byte load per neuron tile, the address wave-uniform apart
+// from q: tile 0 issued with the stride's encoding, tiles 1..3 behind the head layer (kRcEarly).
+// The direction loads, sh_basis and the 16 products drop out: 160 products per stride, the same
+// bits.  `dirs` is not read.
+template <int C, bool WIDE, int W, bool RAYS, bool RC = false>
 __device__ __forceinline__ void shade_fwd_mfma_body(
   const float * __restrict__ enc, const float * __restrict__ dirs,
-  const int32_t * __restrict__ sample_img, const float * __restrict__ p_w_h,
+  const float * __restrict__ ray_const, const int32_t * __restrict__ sample_img,
+  const float * __restrict__ p_w_h,
   const float * __restrict__ p_b_h, const float * __restrict__ p_w1,
   const float * __restrict__ p_b1, const float * __restrict__ p_w2,
   const float * __restrict__ p_b2, const float * __restrict__ p_emb, float * __restrict__ logit,
   float * __restrict__ rgb, float * __restrict__ pre_out, int64_t n, int n_per_ray, int dir_per_ray)
 {
+  static_assert(RAYS || !RC, "the per-ray constant belongs to the ray-uniform form");
   using S = FShape<C, W>;
   constexpr int kS1 = S::kS1, kP = S::kP;
   __shared__ __attribute__((aligned(16))) float lds_all[RAYS ? S::kWFloats : S::kLdsFloats];
@@ -956,7 +1019,15 @@ __device__ __forceinline__ void shade_fwd_mfma_body(
       for (int T = 0; T < 4; T++) eB[t][T] = ld_row(enc + (int64_t)t * n, offS[T] + cE);
     int img[4] = {0, 0, 0, 0};
     float dir[3];
-    if constexpr (RAYS) {
+    f32x4 cR[4];  // RC: the stride's c, rows 16M+4q+r
+    const float * rc = nullptr;
+    if constexpr (RC) {
+      const uint32_t ray = (uint32_t)s0 / (uint32_t)n_per_ray;
+      if (has_emb) img[0] = sample_img[ray];
+      rc = ray_const + (int64_t)ray * kRayConst;
+#pragma unroll
+      for (int M = 0; M < kRcEarly; M++) cR[M] = *reinterpret_cast<const f32x4 *>(rc + 16 * M + 4 * q);
+    } else if constexpr (RAYS) {
       const uint32_t ray = (has_emb || dir_per_ray) ? (uint32_t)s0 / (uint32_t)n_per_ray : 0u;
       if (has_emb) img[0] = sample_img[ray];
       const int64_t drow = dir_per_ray ? (int64_t)ray : s0;
@@ -1001,8 +1072,11 @@ __device__ __forceinline__ void shade_fwd_mfma_body(
             e4[T] = *reinterpret_cast<const f32x4 *>(p_emb + (int64_t)img[T] * kOut1 + 4 * q);
       }
       float sh[16];
-      sh_basis<4>(dir[0], dir[1], dir[2], sh);
-      if constexpr (RAYS) {
+      if constexpr (!RC) sh_basis<4>(dir[0], dir[1], dir[2], sh);
+      if constexpr (RC) {
+#pragma unroll
+        for (int M = kRcEarly; M < 4; M++) cR[M] = *reinterpret_cast<const f32x4 *>(rc + 16 * M + 4 * q);
+      } else if constexpr (RAYS) {
 #pragma unroll
         for (int t = 0; t < 4; t++)
           Xs[t][0] = pick4(q, sh[t], sh[4 + t], sh[8 + t], sh[12 + t]);
@@ -1038,9 +1112,14 @@ __device__ __forceinline__ void shade_fwd_mfma_body(
       f32x4 pre[4];
       if constexpr (RAYS) {
         // c = b1 + w1[:, 16:32] . SH(dir) for one sample tile: the same in every column
-        f32x4 c = *reinterpret_cast<const f32x4 *>(lds_w + S::oB1 + 16 * M + 4 * q);
+        f32x4 c;
+        if constexpr (RC) {
+          c = cR[M];
+        } else {
+          c = *reinterpret_cast<const f32x4 *>(lds_w + S::oB1 + 16 * M + 4 * q);
 #pragma unroll
-        for (int t = 4; t < 8; t++) c = mfma16(wop[(S::oWA2 + M * 8 + t) * 64], Xs[t - 4][0], c);
+          for (int t = 4; t < 8; t++) c = mfma16(wop[(S::oWA2 + M * 8 + t) * 64], Xs[t - 4][0], c);
+        }
 #pragma unroll
         for (int T = 0; T < 4; T++) pre[T] = c;
 #pragma unroll
@@ -1086,8 +1165,8 @@ __device__ __forceinline__ void shade_fwd_mfma_body(
   }
 }
 
-#define F2N_SHADE_FWD_PARAMS(IMG)                                                                     \
-  const float * __restrict__ enc, const float * __restrict__ dirs, const int32_t * __restrict__ IMG,  \
+#define F2N_SHADE_FWD_PARAMS(DIRS, IMG)                                                               \
+  const float * __restrict__ enc, const float * __restrict__ DIRS, const int32_t * __restrict__ IMG,  \
     const float * __restrict__ p_w_h, const float * __restrict__ p_b_h,                               \
     const float * __restrict__ p_w1, const float * __restrict__ p_b1,                                 \
     const float * __restrict__ p_w2, const float * __restrict__ p_b2,                                 \
@@ -1095,21 +1174,65 @@ __device__ __forceinline__ void shade_fwd_mfma_body(
 
 template <int C, bool WIDE, int W>
 __global__ __launch_bounds__(W * 64) void shade_fwd_mfma_kernel(
-  F2N_SHADE_FWD_PARAMS(sample_img), float * __restrict__ pre_out, int64_t n)
+  F2N_SHADE_FWD_PARAMS(dirs, sample_img), float * __restrict__ pre_out, int64_t n)
 {
   shade_fwd_mfma_body<C, WIDE, W, false>(
-    enc, dirs, sample_img, p_w_h, p_b_h, p_w1, p_b1, p_w2, p_b2, p_emb, logit, rgb, pre_out, n, 0, 0);
+    enc, dirs, nullptr, sample_img, p_w_h, p_b_h, p_w1, p_b1, p_w2, p_b2, p_emb, logit, rgb, pre_out, n,
+    0, 0);
 }
 
 // ray-uniform form: n = n_rays * S samples in ray-major order, S % 64 == 0, one image id per ray;
 // dir_per_ray as in shade_bwd_mfma_rays_kernel
 template <int C, bool WIDE, int W>
 __global__ __launch_bounds__(W * 64) void shade_fwd_mfma_rays_kernel(
-  F2N_SHADE_FWD_PARAMS(ray_img), int64_t n, int S, int dir_per_ray)
+  F2N_SHADE_FWD_PARAMS(dirs, ray_img), int64_t n, int S, int dir_per_ray)
 {
   shade_fwd_mfma_body<C, WIDE, W, true>(
-    enc, dirs, ray_img, p_w_h, p_b_h, p_w1, p_b1, p_w2, p_b2, p_emb, logit, rgb, nullptr, n, S,
-    dir_per_ray);
+    enc, dirs, nullptr, ray_img, p_w_h, p_b_h, p_w1, p_b1, p_w2, p_b2, p_emb, logit, rgb, nullptr, n,
+    S, dir_per_ray);
+}
+
+// the ray-uniform form with the per-ray constant loaded: `ray_const` [n_rays, 80] in place of the
+// directions
+template <int C, bool WIDE, int W>
+__global__ __launch_bounds__(W * 64) void shade_fwd_mfma_rays_kernel_const(
+  F2N_SHADE_FWD_PARAMS(ray_const, ray_img), int64_t n, int S)
+{
+  shade_fwd_mfma_body<C, WIDE, W, true, true>(
+    enc, nullptr, ray_const, ray_img, p_w_h, p_b_h, p_w1, p_b1, p_w2, p_b2, p_emb, logit, rgb,
+    nullptr, n, S, 1);
+}
+
+// The per-ray constant: out[ray] = { c[64] = b1 + w1[:, 16:32] . SH16(dir), SH16(dir)[16] }.  One wave
+// takes 16 rays as the 16 columns of the products the network kernels issue for one: lane (q, m)
+// supplies b = SH row 4q + t' of ray m against the same a = w1[16M+m][16 + 4q + t'], k-steps t = 4..7
+// in that order from b1[16M+4q+r].  A column of a product does not depend on its neighbours, so row
+// `ray` holds the bits the in-kernel form gives every sample of the ray.  Lane (q, m) ends up with
+// c[16M+4q+r] of ray m -- the 16 bytes lane (q, .) of a consumer loads per M -- and writes the four SH
+// rows it supplied behind them.
+__global__ __launch_bounds__(256) void shade_ray_const_kernel(
+  const float * __restrict__ dirs, const float * __restrict__ p_w1, const float * __restrict__ p_b1,
+  float * __restrict__ out, int n_rays)
+{
+  const int lane = lane_id(), q = lane >> 4, m = lane & 15;
+  const int64_t ray = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + m;
+  const int64_t rd = (ray < n_rays) ? ray : n_rays - 1;  // a partial tile reads a real ray
+  float sh[16];
+  sh_basis<4>(dirs[rd * 3], dirs[rd * 3 + 1], dirs[rd * 3 + 2], sh);
+  f32x4 b;
+#pragma unroll
+  for (int t = 0; t < 4; t++) b[t] = pick4(q, sh[t], sh[4 + t], sh[8 + t], sh[12 + t]);
+  float * row = out + ray * kRayConst;
+#pragma unroll
+  for (int M = 0; M < 4; M++) {
+    f32x4 c;
+#pragma unroll
+    for (int r = 0; r < 4; r++) c[r] = p_b1[16 * M + 4 * q + r];
+#pragma unroll
+    for (int t = 4; t < 8; t++) c = mfma16(p_w1[(16 * M + m) * kIn2 + 16 + 4 * q + (t - 4)], b[t - 4], c);
+    if (ray < n_rays) *reinterpret_cast<f32x4 *>(row + 16 * M + 4 * q) = c;
+  }
+  if (ray < n_rays) *reinterpret_cast<f32x4 *>(row + kHid + 4 * q) = b;
 }
 #undef F2N_SHADE_FWD_PARAMS
 
@@ -1131,9 +1254,11 @@ bool shade_bwd_mfma_supports(int C, int64_t n)
 
 // S = 0: the per-sample kernels (img = one id per sample); S > 0: the ray-uniform kernels
 // (img = one id per ray, n = n_rays * S; dir_per_ray: dirs [n_rays, 3] instead of [n, 3]).  The same
-// choice of form (TS, fences, WIDE) for both.
+// choice of form (TS, fences, WIDE) for both.  ray_const (with S > 0): the ray-uniform kernels that
+// load the per-ray constant, instantiation for instantiation the set of the ones that form it.
 static int launch_shade_bwd_mfma_any(
-  const float * enc_cm, int C, const float * dirs, const int32_t * img, const float * w_h,
+  const float * enc_cm, int C, const float * dirs, const float * ray_const, const int32_t * img,
+  const float * w_h,
   const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
   const float * app_emb, const float * d_logit, const float * d_rgb, float * d_enc_cm,
   float * g_w_h, float * g_b_h, float * g_w1, float * g_b1, float * g_w2, float * g_b2,
@@ -1159,7 +1284,13 @@ static int launch_shade_bwd_mfma_any(
     using MS = MShape<CC, TT>;                                                                       \
     const int64_t n_strides = (n + MS::kStride - 1) / MS::kStride;                                   \
     const unsigned grid = (unsigned)std::min<int64_t>(256, (n_strides + MS::kWaves - 1) / MS::kWaves); \
-    if (S > 0) {                                                                                     \
+    if (S > 0 && ray_const) {                                                                        \
+      if constexpr (!(CC == 64 && WW && TT == 2)) /* rays_one_wave */                                \
+        hipLaunchKernelGGL(                                                                          \
+          (shade_bwd_mfma_rays_kernel_const<CC, VV, WW, TT>), dim3(grid), dim3(MS::kWaves * 64), 0,  \
+          stream, enc_cm, ray_const, img, w_h, b_h, w1, b1, w2, b2, app_emb, d_logit, d_rgb,         \
+          d_enc_cm, g_w_h, g_b_h, g_w1, g_b1, g_w2, g_b2, g_app_emb, n, S);                          \
+    } else if (S > 0) {                                                                              \
       if constexpr (!(CC == 64 && WW && TT == 2)) /* rays_one_wave */                                \
         hipLaunchKernelGGL(                                                                          \
           (shade_bwd_mfma_rays_kernel<CC, VV, WW, TT>), dim3(grid), dim3(MS::kWaves * 64), 0,        \
@@ -1199,8 +1330,8 @@ int launch_shade_bwd_mfma(
   float * g_app_emb, int64_t n, hipStream_t stream)
 {
   return launch_shade_bwd_mfma_any(
-    enc_cm, C, dirs, sample_img, w_h, b_h, w1, b1, w2, b2, app_emb, d_logit, d_rgb, d_enc_cm, g_w_h,
-    g_b_h, g_w1, g_b1, g_w2, g_b2, g_app_emb, n, 0, 0, stream);
+    enc_cm, C, dirs, nullptr, sample_img, w_h, b_h, w1, b1, w2, b2, app_emb, d_logit, d_rgb, d_enc_cm,
+    g_w_h, g_b_h, g_w1, g_b1, g_w2, g_b2, g_app_emb, n, 0, 0, stream);
 }
 
 int launch_shade_bwd_mfma_rays(
@@ -1212,14 +1343,30 @@ int launch_shade_bwd_mfma_rays(
 {
   if (S <= 0 || S % 64 != 0 || n_rays <= 0) return F2N_E_INVALID_ARG;
   return launch_shade_bwd_mfma_any(
-    enc_cm, C, dirs, ray_img, w_h, b_h, w1, b1, w2, b2, app_emb, d_logit, d_rgb, d_enc_cm, g_w_h,
-    g_b_h, g_w1, g_b1, g_w2, g_b2, g_app_emb, (int64_t)n_rays * S, S, dir_per_ray ? 1 : 0, stream);
+    enc_cm, C, dirs, nullptr, ray_img, w_h, b_h, w1, b1, w2, b2, app_emb, d_logit, d_rgb, d_enc_cm,
+    g_w_h, g_b_h, g_w1, g_b1, g_w2, g_b2, g_app_emb, (int64_t)n_rays * S, S, dir_per_ray ? 1 : 0,
+    stream);
+}
+
+int launch_shade_bwd_mfma_rays_const(
+  const float * enc_cm, int C, const float * ray_const, const int32_t * ray_img, const float * w_h,
+  const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
+  const float * app_emb, const float * d_logit, const float * d_rgb, float * d_enc_cm,
+  float * g_w_h, float * g_b_h, float * g_w1, float * g_b1, float * g_w2, float * g_b2,
+  float * g_app_emb, int n_rays, int S, hipStream_t stream)
+{
+  if (S <= 0 || S % 64 != 0 || n_rays <= 0 || !ray_const) return F2N_E_INVALID_ARG;
+  if (reinterpret_cast<uintptr_t>(ray_const) & 15u) return F2N_E_INVALID_ARG;  // read as float4
+  return launch_shade_bwd_mfma_any(
+    enc_cm, C, nullptr, ray_const, ray_img, w_h, b_h, w1, b1, w2, b2, app_emb, d_logit, d_rgb,
+    d_enc_cm, g_w_h, g_b_h, g_w1, g_b1, g_w2, g_b2, g_app_emb, (int64_t)n_rays * S, S, 1, stream);
 }
 
 
 // S = 0: the per-sample kernels; S > 0: the ray-uniform kernels (img per ray, no pre_cm)
 static int launch_shade_fwd_mfma_any(
-  const float * enc_cm, int C, const float * dirs, const int32_t * img, const float * w_h,
+  const float * enc_cm, int C, const float * dirs, const float * ray_const, const int32_t * img,
+  const float * w_h,
   const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
   const float * app_emb, float * logit, float * rgb, float * pre_cm, int64_t n, int S,
   int dir_per_ray, hipStream_t stream)
@@ -1233,7 +1380,11 @@ static int launch_shade_fwd_mfma_any(
   {                                                                                                \
     constexpr int kW = KW;                                                                         \
     const unsigned grid = (unsigned)std::min<int64_t>(256, (n_strides + kW - 1) / kW);             \
-    if (S > 0)                                                                                     \
+    if (S > 0 && ray_const)                                                                        \
+      hipLaunchKernelGGL(                                                                          \
+        (shade_fwd_mfma_rays_kernel_const<CC, WW, KW>), dim3(grid), dim3(kW * 64), 0, stream,      \
+        enc_cm, ray_const, img, w_h, b_h, w1, b1, w2, b2, app_emb, logit, rgb, n, S);              \
+    else if (S > 0)                                                                                \
       hipLaunchKernelGGL(                                                                          \
         (shade_fwd_mfma_rays_kernel<CC, WW, KW>), dim3(grid), dim3(kW * 64), 0, stream, enc_cm,    \
         dirs, img, w_h, b_h, w1, b1, w2, b2, app_emb, logit, rgb, n, S, dir_per_ray);              \
@@ -1265,8 +1416,8 @@ int launch_shade_fwd_mfma(
   const float * app_emb, float * logit, float * rgb, float * pre_cm, int64_t n, hipStream_t stream)
 {
   return launch_shade_fwd_mfma_any(
-    enc_cm, C, dirs, sample_img, w_h, b_h, w1, b1, w2, b2, app_emb, logit, rgb, pre_cm, n, 0, 0,
-    stream);
+    enc_cm, C, dirs, nullptr, sample_img, w_h, b_h, w1, b1, w2, b2, app_emb, logit, rgb, pre_cm, n, 0,
+    0, stream);
 }
 
 int launch_shade_fwd_mfma_rays(
@@ -1277,8 +1428,32 @@ int launch_shade_fwd_mfma_rays(
 {
   if (S <= 0 || S % 64 != 0 || n_rays <= 0) return F2N_E_INVALID_ARG;
   return launch_shade_fwd_mfma_any(
-    enc_cm, C, dirs, ray_img, w_h, b_h, w1, b1, w2, b2, app_emb, logit, rgb, nullptr,
+    enc_cm, C, dirs, nullptr, ray_img, w_h, b_h, w1, b1, w2, b2, app_emb, logit, rgb, nullptr,
     (int64_t)n_rays * S, S, dir_per_ray ? 1 : 0, stream);
+}
+
+int launch_shade_fwd_mfma_rays_const(
+  const float * enc_cm, int C, const float * ray_const, const int32_t * ray_img, const float * w_h,
+  const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
+  const float * app_emb, float * logit, float * rgb, int n_rays, int S, hipStream_t stream)
+{
+  if (S <= 0 || S % 64 != 0 || n_rays <= 0 || !ray_const) return F2N_E_INVALID_ARG;
+  if (reinterpret_cast<uintptr_t>(ray_const) & 15u) return F2N_E_INVALID_ARG;  // read as float4
+  return launch_shade_fwd_mfma_any(
+    enc_cm, C, nullptr, ray_const, ray_img, w_h, b_h, w1, b1, w2, b2, app_emb, logit, rgb, nullptr,
+    (int64_t)n_rays * S, S, 1, stream);
+}
+
+int launch_shade_ray_const(
+  const float * ray_dirs, const float * w1, const float * b1, float * ray_const, int n_rays,
+  hipStream_t stream)
+{
+  if (n_rays <= 0 || !ray_dirs || !w1 || !b1 || !ray_const) return F2N_E_INVALID_ARG;
+  if (reinterpret_cast<uintptr_t>(ray_const) & 15u) return F2N_E_INVALID_ARG;  // written as float4
+  const unsigned grid = (unsigned)(((int64_t)n_rays + 63) / 64);  // 4 waves of 16 rays per workgroup
+  hipLaunchKernelGGL(
+    shade_ray_const_kernel, dim3(grid), dim3(256), 0, stream, ray_dirs, w1, b1, ray_const, n_rays);
+  return f2n_launch_status();
 }
 
 }  // namespace f2n_detail

@@ -981,6 +981,43 @@ int f2n_shade_bwd_raydirs(
   float * g_w_h, float * g_b_h, float * g_w1, float * g_b1, float * g_w2, float * g_b2,
   float * g_app_emb, int n_rays, int S, void * stream);
 
+/* The per-ray half of the hidden layer formed ONCE per ray instead of once per stride of the two
+ * entries above (which form it twice per ray forward and four times backward at S = 128) -- the SH
+ * input of src/sh_shader.cpp:24-28 (src/sh_shader.cu:11-103) through the first Linear of the colour MLP.
+ *   ray_const [n_rays, F2N_SHADE_RAY_CONST_FLOATS], 16-byte aligned; row of a ray:
+ *     [0, 64)   c[j] = b1[j] + sum_i w1[j][16 + i] SH16(dir)[i], the f32 chain the ray-uniform kernels
+ *               run: from b1[j], fmaf over i = 0, 4, 8, 12, 1, 5, 9, 13, 2, ... (k-step by k-step of the
+ *               matrix product, the four quarters of a k-step in order)
+ *     [64, 80)  SH16(dir), as f2n_sh_encode evaluates it
+ * f2n_shade_ray_const writes it from ray_dirs [n_rays, 3], w1 [64, 32] and b1 [64] in one small launch
+ * (a wavefront takes 16 rays as the 16 columns of the products the network kernels issue for one, so
+ * a row holds the bits those kernels form themselves).  n_rays = 0 is F2N_OK; n_rays < 0, a null or a
+ * misaligned ray_const F2N_E_INVALID_ARG. */
+#define F2N_SHADE_RAY_CONST_FLOATS 80
+int f2n_shade_ray_const(
+  const float * ray_dirs, const float * w1, const float * b1, float * ray_const, int n_rays,
+  void * stream);
+
+/* f2n_shade_fwd_raydirs / f2n_shade_bwd_raydirs loading that row instead of forming it: kernels of
+ * their own (shade_*_mfma_rays_kernel_const), 16 matrix products per stride fewer, no direction loads
+ * and no SH evaluation; the same reference lines as f2n_shade_fwd_rays, src/renderer.cpp:93-104.
+ * ray_const must have been written from the w1 and b1 passed here and from the rays' directions.
+ * Same status codes and the same choice of form as those entries; logit, rgb and d_enc are theirs bit
+ * for bit, the parameter gradients the same f32 terms in the same per-wave order.  The forward takes
+ * no directions; the backward takes ray_dirs [n_rays, 3] in the place f2n_shade_bwd_raydirs does
+ * (required, and not read while every form of the loading kernel fits its registers: all do). */
+int f2n_shade_fwd_rays_const(
+  const float * enc_cm, int C, const float * ray_const, const int32_t * ray_img, const float * w_h,
+  const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
+  const float * app_emb, float * logit, float * rgb, int n_rays, int S, void * stream);
+
+int f2n_shade_bwd_rays_const(
+  const float * enc_cm, int C, const float * ray_dirs, const float * ray_const,
+  const int32_t * ray_img, const float * w_h, const float * b_h, const float * w1, const float * b1,
+  const float * w2, const float * b2, const float * app_emb, const float * d_logit,
+  const float * d_rgb, float * d_enc_cm, float * g_w_h, float * g_b_h, float * g_w1, float * g_b1,
+  float * g_w2, float * g_b2, float * g_app_emb, int n_rays, int S, void * stream);
+
 /* ------------------------------------------------------------------ one-pass inference render - */
 
 /* Renderer::render without gradients as ONE kernel, rays in and colours out -- src/renderer.cpp:33-123

@@ -24,6 +24,12 @@ csv.field_size_limit(1 << 30)
 def short(name):
     # hash_fwd_raytile_kernel_groups is the same operator as hash_fwd_raytile_kernel, and that is the
     # key bench.py looks the forward up under
+    # shade_fwd_mfma_rays_kernel_const / shade_bwd_mfma_rays_kernel_const (the dense route's network
+    # kernels, which load the per-ray constant) are the operators bench.py looks up as shade_fwd_kernel
+    # and shade_bwd_mfma_kernel.  shade_ray_const_kernel (a few microseconds in front of the forward)
+    # keeps its own key: an average per dispatch over two different kernels would describe neither.
+    name = re.sub(r"shade_fwd_mfma_rays_kernel_const\b", "shade_fwd_kernel", name)
+    name = re.sub(r"shade_bwd_mfma_rays_kernel_const\b", "shade_bwd_mfma_kernel", name)
     m = re.search(r"(\w+_kernel)\b", name.replace("_kernel_groups", "_kernel"))
     if m and "anonymous" in name:
         return m.group(1)
