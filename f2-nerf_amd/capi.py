@@ -17,6 +17,7 @@ _CTYPES = {
     "int64_t": ctypes.c_int64,
     "uint32_t": ctypes.c_uint32,
     "float": ctypes.c_float,
+    "double": ctypes.c_double,
 }
 
 

@@ -441,6 +441,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     py::arg("dist") = py::none(), py::arg("attempts") = 32,
     "a batch of n_patches P x P patches: sample_masked_rays' dict (tries and patch_weight per "
     "patch, ray_weight the patch's weight on its rays); see f2n::sample_patch_rays");
+  m.def(
+    "level_weights",
+    [](double alpha, int64_t L) {
+      auto [w, la] = f2n::level_weights(alpha, L);
+      return py::make_tuple(w, la);
+    },
+    py::arg("alpha"), py::arg("n_levels"), "f2n_level_weights -> (weights [L] on the CPU, l_active)");
+  py::class_<f2n::CoarseToFine>(m, "CoarseToFine")
+    .def(py::init([](double start, double end, double base) {
+           return f2n::CoarseToFine{start, end, base};
+         }),
+         py::arg("start") = 0., py::arg("end") = 1., py::arg("base") = 1.)
+    .def_readwrite("start", &f2n::CoarseToFine::start)
+    .def_readwrite("end", &f2n::CoarseToFine::end)
+    .def_readwrite("base", &f2n::CoarseToFine::base)
+    .def("alpha_at", &f2n::CoarseToFine::alpha_at, py::arg("it"), py::arg("n_levels"),
+         "base + (L - base) * clamp((it - start) / (end - start), 0, 1)");
   m.def("ray_order", &f2n::ray_order, "caller indices of rays_d sorted into pixel-compact bundles");
   m.def("manual_seed", [](uint64_t s) { torch::manual_seed(s); });
   m.def("kernel_timer_enable", &f2n::kernel_timer_enable);
@@ -480,6 +497,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def("set_exact_point_grad", &Hash3DAnchored::set_exact_point_grad,
          "Hash3DAnchoredOptions::exact_point_grad: points and rays that require a gradient receive the "
          "encoding's true derivative instead of the reference's point gradient (quirk Q5)")
+    .def("set_level_weights", &Hash3DAnchored::set_level_weights, py::arg("weights"),
+         "per-level weights [L] >= 0 (CPU or device), folded into the field head; copied in place "
+         "into one persistent device tensor: see Hash3DAnchored::set_level_weights")
+    .def("clear_level_weights", &Hash3DAnchored::clear_level_weights)
+    .def("level_weights", [](const Hash3DAnchored & s) { return tensor_or_none(s.level_weights()); },
+         "the host copy [L] of the weights, or None when none are set")
+    .def("active_levels", &Hash3DAnchored::active_levels,
+         "1 + the index of the last non-zero weight; n_levels when none are set")
+    .def("head_weight", &Hash3DAnchored::head_weight,
+         "mlp.weight itself without level weights, else mlp.weight * (lw (x) 1_F) (carries autograd)")
+    .def("set_skip_masked_levels",
+         [](Hash3DAnchored & s, bool on) { s.options_.skip_masked_levels = on; },
+         "Hash3DAnchoredOptions::skip_masked_levels: walk active_levels() levels only (default on)")
+    .def_property_readonly(
+      "skip_masked_levels", [](const Hash3DAnchored & s) { return s.options_.skip_masked_levels; })
     .def_readonly("pool_size", &Hash3DAnchored::pool_size_)
     .def_readonly("local_size", &Hash3DAnchored::local_size_)
     .def_readonly("level_stride", &Hash3DAnchored::level_stride_)
@@ -868,6 +900,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
          "rays that require grad take the fused path: see RendererOptions::fused_ray_grad")
     .def("set_exact_ray_grad", [](Renderer & r, bool on) { r.scene_field_->set_exact_point_grad(on); },
          "the scene field's Hash3DAnchoredOptions::exact_point_grad, on every route")
+    .def("set_level_weights", &Renderer::set_level_weights, py::arg("weights"),
+         "per-level weights [L] >= 0 of the scene field, on every route: see Renderer::set_level_weights")
+    .def("set_coarse_to_fine", &Renderer::set_coarse_to_fine, py::arg("alpha"),
+         "the weights of f2n_level_weights for a progress alpha in [1, L]")
+    .def("clear_level_weights", &Renderer::clear_level_weights)
+    .def("level_weights", [](const Renderer & r) { return tensor_or_none(r.scene_field_->level_weights()); })
+    .def("active_levels", [](const Renderer & r) { return r.scene_field_->active_levels(); })
+    .def("set_skip_masked_levels",
+         [](Renderer & r, bool on) { r.scene_field_->options_.skip_masked_levels = on; },
+         "the scene field's Hash3DAnchoredOptions::skip_masked_levels")
     .def("set_margin_min_samples", [](Renderer & r, int64_t n) { r.options_.margin_min_samples = n; })
     .def("set_ray_order_min_rays", [](Renderer & r, int64_t n) { r.options_.ray_order_min_rays = n; },
          "dense first pass: bucket the rays from this many on (RendererOptions::ray_order_min_rays)")
@@ -1022,7 +1064,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def_readwrite("one_pass", &LocalizerParam::one_pass)
     .def_readwrite("one_pass_head", &LocalizerParam::one_pass_head)
     .def_readwrite("dist_params", &LocalizerParam::dist_params)
-    .def_readwrite("exact_ray_grad", &LocalizerParam::exact_ray_grad);
+    .def_readwrite("exact_ray_grad", &LocalizerParam::exact_ray_grad)
+    .def_readwrite("level_alpha", &LocalizerParam::level_alpha);
 
   py::class_<Localizer, std::shared_ptr<Localizer>>(m, "Localizer")
     .def(py::init<const LocalizerParam &>(), py::arg("param"),
@@ -1033,6 +1076,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
       py::arg("param"), py::arg("renderer"), py::arg("intrinsic"), py::arg("height"),
       py::arg("width"), py::arg("center"), py::arg("radius"))
     .def("render_image", &Localizer::render_image, py::call_guard<py::gil_scoped_release>())
+    .def("set_level_alpha", &Localizer::set_level_alpha, py::arg("alpha"),
+         "LocalizerParam::level_alpha afterwards: < 0 clears the renderer's level weights")
     .def(
       "optimize_pose_by_random_search",
       [](Localizer & l, const Tensor & pose, const Tensor & image, int64_t n, float coeff,

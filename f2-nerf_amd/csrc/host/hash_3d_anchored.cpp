@@ -170,13 +170,42 @@ f2n::FieldArgs Hash3DAnchored::kernel_args(const Tensor & table16) const
           (int)options_.n_levels,
           (int)options_.n_channels,
           (uint32_t)local_size_,
-          level_stride_};
+          level_stride_,
+          walk_levels()};
 }
 
 std::pair<Tensor, Tensor> Hash3DAnchored::density_head() const
 {
-  return {mlp_->weight.detach().select(0, 0).contiguous(),
+  return {head_weight().detach().select(0, 0).contiguous(),
           mlp_->bias.detach().slice(0, 0, 1).contiguous()};
+}
+
+void Hash3DAnchored::set_level_weights(const Tensor & weights)
+{
+  const int64_t L = options_.n_levels, F = options_.n_channels;
+  TORCH_CHECK(weights.defined() && weights.numel() == L, "level weights must be [n_levels]");
+  Tensor host =
+    weights.detach().to(torch::kCPU, torch::kFloat32).reshape({L}).contiguous().clone();
+  const float * w = host.data_ptr<float>();
+  int64_t last = -1;
+  for (int64_t l = 0; l < L; l++) {
+    TORCH_CHECK(std::isfinite(w[l]) && w[l] >= 0.f, "level weights must be finite and >= 0");
+    if (w[l] != 0.f) last = l;
+  }
+  TORCH_CHECK(last >= 0, "level weights: at least one level must be active");
+  Tensor cols = host.repeat_interleave(F);  // lw (x) 1_F, [L*F]
+  if (!level_cols_.defined() || level_cols_.device() != mlp_->weight.device())
+    level_cols_ = torch::empty({L * F}, mlp_->weight.options().requires_grad(false));
+  level_cols_.copy_(cols);
+  level_weights_host_ = host;
+  active_levels_ = last + 1;
+  has_level_weights_ = true;
+}
+
+Tensor Hash3DAnchored::head_weight() const
+{
+  if (!has_level_weights_) return mlp_->weight;
+  return mlp_->weight * level_cols_;
 }
 
 Tensor Hash3DAnchored::density_grad(const Tensor & points_in)
@@ -194,7 +223,7 @@ Tensor Hash3DAnchored::density_grad(const Tensor & points_in)
   f2n::check(
     f2n_density_grad(
       points.data_ptr<float>(), g.table, g.primes, g.bias, g.mul, w0.data_ptr<float>(),
-      grad.data_ptr<float>(), n, g.L, g.F, g.T, g.level_stride, stream),
+      grad.data_ptr<float>(), n, g.L_walk, g.F, g.T, g.level_stride, stream),
     "f2n_density_grad");
   return grad;
 }
@@ -244,7 +273,8 @@ Tensor Hash3DAnchored::encode_cached(
 
 Tensor Hash3DAnchored::query(const Tensor & points)
 {
-  return mlp_->forward(encode(points));
+  if (!has_level_weights_) return mlp_->forward(encode(points));
+  return torch::linear(encode(points), head_weight(), mlp_->bias);
 }
 
 std::vector<torch::optim::OptimizerParamGroup> Hash3DAnchored::optim_param_groups(float lr)
@@ -273,6 +303,9 @@ variable_list Hash3DAnchoredFunction::forward(
   points = f2n::dev_f32(points, "Hash3DAnchoredFunction points");
   TORCH_CHECK(points.dim() == 2 && points.size(1) == 3, "points must be [n, 3]");
   ctx->save_for_backward({points, feat_pool});
+  // the levels walked now are the levels the backward walks, whatever the weights are by then
+  const int L_walk = field->walk_levels();
+  ctx->saved_data["L_walk"] = (int64_t)L_walk;
 
   const int64_t n = points.size(0);
   const int L = (int)field->options_.n_levels, F = (int)field->options_.n_channels;
@@ -284,6 +317,8 @@ variable_list Hash3DAnchoredFunction::forward(
   // of 64 scattered 8-byte pieces (2.5x faster encode on MI355X) -- and the caller receives the
   // reference's logical shape [n, L*F] as a transposed view.
   Tensor out_cm = torch::empty({(int64_t)L * F, n}, points.options());
+  // the rows of the levels left out are zeros, not whatever the allocator hands over: 0 * NaN is NaN
+  if (L_walk < L) out_cm.slice(0, (int64_t)L_walk * F).zero_();
   {
     f2n::ScopedKernelTimer timer("hash_fwd", f2n::current_stream(points), (double)n);
     const int64_t spr = info->samples_per_ray_;
@@ -291,13 +326,13 @@ variable_list Hash3DAnchoredFunction::forward(
       f2n::check(
         f2n_hash_fwd_raytile(
           points.data_ptr<float>(), g.table, g.primes, g.bias, g.mul, out_cm.data_ptr<float>(),
-          (int)(n / spr), (int)spr, g.L, g.F, g.T, g.level_stride, f2n::current_stream(points)),
+          (int)(n / spr), (int)spr, L_walk, g.F, g.T, g.level_stride, f2n::current_stream(points)),
         "f2n_hash_fwd_raytile");
     } else {
       f2n::check(
         f2n_hash_fwd(
           points.data_ptr<float>(), g.table, g.primes, g.bias, g.mul, out_cm.data_ptr<float>(), 1, n,
-          nullptr, n, g.L, g.F, g.T, g.level_stride, f2n::current_stream(points)),
+          nullptr, n, L_walk, g.F, g.T, g.level_stride, f2n::current_stream(points)),
         "f2n_hash_fwd");
     }
   }
@@ -315,6 +350,7 @@ variable_list Hash3DAnchoredFunction::backward(AutogradContext * ctx, variable_l
 
   const int64_t n = points.size(0);
   const int L = (int)field->options_.n_levels, F = (int)field->options_.n_channels;
+  const int L_walk = (int)ctx->saved_data["L_walk"].toInt();  // the forward's
   const float grad_scale = 128.f;  // reference hash_3d_anchored.cu:190
 
   // the incoming gradient may be row-major [n, C] or a transposed (channel-major) view; both are
@@ -349,7 +385,7 @@ variable_list Hash3DAnchoredFunction::backward(AutogradContext * ctx, variable_l
   // capped at 64 GiB: bigger batches run in rounds); it is further capped at half of the device's
   // free memory, and when even that cannot be allocated the atomic kernel takes over.
   int64_t ws_bytes =
-    q5_points ? 0 : f2n_hash_bwd_workspace_bytes(n, L, F, g.T);
+    q5_points ? 0 : f2n_hash_bwd_workspace_bytes(n, L_walk, F, g.T);
   Tensor ws;
   if (ws_bytes > 0 && field->options_.binned_backward) {
     size_t free_b = 0, total_b = 0;
@@ -374,7 +410,7 @@ variable_list Hash3DAnchoredFunction::backward(AutogradContext * ctx, variable_l
     f2n::ScopedKernelTimer timer("hash_bwd", stream, (double)n);
     const int st = f2n_hash_bwd_binned(
       points.data_ptr<float>(), g.primes, g.bias, g.mul, grad_in.data_ptr<float>(), ld_point,
-      ld_chan, embeds_grad.data_ptr<float>(), n, g.L, g.F, g.T, g.level_stride, grad_scale,
+      ld_chan, embeds_grad.data_ptr<float>(), n, L_walk, g.F, g.T, g.level_stride, grad_scale,
       ws.data_ptr(), ws_bytes, stream);
     if (st != F2N_E_UNSUPPORTED) f2n::check(st, "f2n_hash_bwd_binned");
     done = (st == F2N_OK);  // unsupported = the (shrunk) workspace holds not even one tile
@@ -385,7 +421,7 @@ variable_list Hash3DAnchoredFunction::backward(AutogradContext * ctx, variable_l
       f2n_hash_bwd(
         points.data_ptr<float>(), g.table, g.primes, g.bias, g.mul, grad_in.data_ptr<float>(),
         ld_point, ld_chan, embeds_grad.data_ptr<float>(),
-        q5_points ? points_grad.data_ptr<float>() : nullptr, n, g.L, g.F, g.T, g.level_stride,
+        q5_points ? points_grad.data_ptr<float>() : nullptr, n, L_walk, g.F, g.T, g.level_stride,
         grad_scale, stream),
       "f2n_hash_bwd");
   }
@@ -394,7 +430,7 @@ variable_list Hash3DAnchoredFunction::backward(AutogradContext * ctx, variable_l
     f2n::check(
       f2n_hash_pts_grad_exact(
         points.data_ptr<float>(), g.table, g.primes, g.bias, g.mul, grad_in.data_ptr<float>(),
-        ld_point, ld_chan, points_grad.data_ptr<float>(), n, g.L, g.F, g.T, g.level_stride, stream),
+        ld_point, ld_chan, points_grad.data_ptr<float>(), n, L_walk, g.F, g.T, g.level_stride, stream),
       "f2n_hash_pts_grad_exact");
   }
   return {points_grad, in_place ? Tensor() : embeds_grad, Tensor()};

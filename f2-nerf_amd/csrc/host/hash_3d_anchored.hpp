@@ -38,6 +38,11 @@ struct Hash3DAnchoredOptions
   // a cell-centre derivative and rounded through f16): the magnitude changes, learning rates tuned
   // with it off do not carry over.  Off: every route launches what it always launched.
   bool exact_point_grad = false;
+  // With level weights set (set_level_weights) whose tail is zero, the kernels that take L as a loop
+  // bound are called with active_levels() instead: the levels the head multiplies by zero are not
+  // gathered at all, forward or backward, and their rows of the encoding are zero-filled.  Off: every
+  // level is walked and the fold alone applies the weights (the A/B arm; the same results).
+  bool skip_masked_levels = true;
   torch::Device device = f2n::default_device();
 };
 
@@ -54,6 +59,7 @@ struct FieldArgs
   int L, F;
   uint32_t T;
   int64_t level_stride;
+  int L_walk;  // the loop bound for entries that walk the levels: L, or fewer (Hash3DAnchored::walk_levels)
 };
 
 }  // namespace f2n
@@ -72,6 +78,8 @@ public:
   // samples_per_ray > 0 declares `points` a dense ray-major [n_rays, samples_per_ray] grid: the
   // forward then walks neighbouring rays per wavefront (f2n_hash_fwd_raytile), same results.
   // contracted_out, if given, receives the contracted points (to hand back to encode_cached).
+  // Level weights (below) are NOT applied here: the features are the unweighted ones, with exact
+  // zeros in the rows of the levels that skip_masked_levels leaves out.
   Tensor encode(const Tensor & points, int64_t samples_per_ray = 0, Tensor * contracted_out = nullptr);
 
   // encode() of positions that are contracted already (f2n_sample_dense writes them): `x` [n, 3] goes
@@ -87,9 +95,36 @@ public:
   Tensor encode_cached(
     const Tensor & points, const Tensor & enc_cm, const Tensor & contracted = Tensor());
 
-  // Row 0 of mlp_ (weight [L*F], bias [1]) as contiguous device tensors: the density head the fused
-  // ray march evaluates in-kernel.
+  // Row 0 of head_weight() and of mlp_'s bias (weight [L*F], bias [1]) as contiguous device tensors:
+  // the density head the fused ray march evaluates in-kernel.
   std::pair<Tensor, Tensor> density_head() const;
+
+  // ---- level weights: coarse-to-fine training and level-of-detail renders ----
+  // lw[L] >= 0 scales what level l contributes to the head: h = b_h + sum_l lw[l] W_h[:, lF..lF+F) enc_l,
+  // i.e. the head with its columns scaled.  The weights are FOLDED into the head (head_weight());
+  // no encode kernel applies them, and d_enc = W_eff^T d_h carries them into every gradient.
+  // encode() / encode_contracted() therefore return UNWEIGHTED features -- with exact zeros for the
+  // levels skip_masked_levels leaves out.
+  //   set_level_weights  a CPU or device [L] tensor of finite values >= 0, the last non-zero one
+  //                      deciding active_levels().  Copied IN PLACE into one persistent device tensor:
+  //                      a captured graph sees later values (it stays valid while walk_levels() does
+  //                      not change).
+  //   clear_level_weights  back to the field without weights, launch for launch.
+  void set_level_weights(const Tensor & weights);
+  void clear_level_weights() { has_level_weights_ = false; }
+  bool has_level_weights() const { return has_level_weights_; }
+  // the host copy [L] (undefined when none are set) / 1 + the index of the last non-zero weight (L
+  // when none are set)
+  Tensor level_weights() const { return has_level_weights_ ? level_weights_host_ : Tensor(); }
+  int64_t active_levels() const { return has_level_weights_ ? active_levels_ : options_.n_levels; }
+  // what the kernels that loop over levels are given: active_levels() under skip_masked_levels, else L
+  int walk_levels() const
+  {
+    return (int)(options_.skip_masked_levels ? active_levels() : options_.n_levels);
+  }
+  // mlp_->weight itself when no weights are set; otherwise mlp_->weight * (lw (x) 1_F), one ATen
+  // product that autograd differentiates (g_W_h = g_W_eff * cols).
+  Tensor head_weight() const;
 
   // d(density logit)/d(position) at the raw points [n, 3] -> [n, 3]: the spatial gradient of the
   // trilinear interpolant query() evaluates, followed by row 0 of mlp_ and taken through the
@@ -132,6 +167,11 @@ private:
   Tensor feat_pool_f16_;
   const void * shadow_src_ = nullptr;
   uint32_t shadow_version_ = 0;
+
+  bool has_level_weights_ = false;
+  int64_t active_levels_ = 0;
+  Tensor level_weights_host_;  // [L] f32, CPU
+  Tensor level_cols_;          // [L*F] f32 on the device: lw (x) 1_F, rewritten in place
 };
 
 class Hash3DAnchoredInfo : public torch::CustomClassHolder

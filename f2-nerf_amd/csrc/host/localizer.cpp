@@ -107,6 +107,7 @@ void Localizer::init(
   // they take the fused path (RendererOptions::fused_ray_grad)
   renderer_->options_.fused_ray_grad = true;
   if (param_.exact_ray_grad) renderer_->scene_field_->set_exact_point_grad(true);
+  if (param_.level_alpha >= 0.) renderer_->set_coarse_to_fine(param_.level_alpha);
   if (param_.one_pass) {
     renderer_->set_one_pass(true);
     renderer_->set_one_pass_head(param_.one_pass_head);
@@ -124,6 +125,15 @@ void Localizer::init(
   // Column j is the NeRF axis j (x right, y up, z back) written in the world frame (x front, y left,
   // z up): right = -left, up = up, back = -front.  A signed permutation, so products with it are exact.
   axes_ = torch::tensor({0.f, 0.f, -1.f, -1.f, 0.f, 0.f, 0.f, 1.f, 0.f}).view({3, 3}).to(dev);
+}
+
+void Localizer::set_level_alpha(double alpha)
+{
+  param_.level_alpha = alpha;
+  if (alpha >= 0.)
+    renderer_->set_coarse_to_fine(alpha);
+  else
+    renderer_->clear_level_weights();
 }
 
 std::array<float, 6> Localizer::noise_sigmas(float noise_coeff) const

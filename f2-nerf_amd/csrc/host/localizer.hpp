@@ -53,6 +53,11 @@ struct LocalizerParam
   // The gradient is about a quarter the size: a learning rate tuned without it does not carry over.
   // Not part of inference_params.yaml either.
   bool exact_ray_grad = false;
+  // Level of detail of every render the Localizer makes: the coarse-to-fine progress alpha in
+  // [1, n_levels] handed to Renderer::set_coarse_to_fine in init (a wide, smooth basin for the
+  // particles and the pose optimiser, and fewer levels to gather).  < 0: off, the renderer's weights
+  // are left as they are.  Not part of inference_params.yaml either.
+  double level_alpha = -1.;
 };
 
 namespace f2n
@@ -123,6 +128,9 @@ public:
 
   // {pos x, y, z, rot x, y, z} in the NeRF frame for f2n_perturb_poses (src/localizer.cpp:74-79)
   std::array<float, 6> noise_sigmas(float noise_coeff) const;
+
+  // LocalizerParam::level_alpha for a Localizer that exists already; < 0 clears the renderer's weights
+  void set_level_alpha(double alpha);
 
   float radius() const { return radius_; }
   int infer_height() const { return infer_height_; }

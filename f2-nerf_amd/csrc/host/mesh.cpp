@@ -48,7 +48,7 @@ Tensor density_lattice(
     f2n_density_lattice(
       g.table, g.primes, g.bias, g.mul, head.first.data_ptr<float>(),
       head.second.data_ptr<float>(), logit.data_ptr<float>(), lo[0], lo[1], lo[2], step[0], step[1],
-      step[2], (int)dims[0], (int)dims[1], (int)dims[2], g.L, g.F, g.T, g.level_stride, stream),
+      step[2], (int)dims[0], (int)dims[1], (int)dims[2], g.L_walk, g.F, g.T, g.level_stride, stream),
     "f2n_density_lattice");
   return logit;
 }

@@ -30,7 +30,7 @@ void OccupancyGrid::update(Hash3DAnchored & field, float threshold, float decay,
     f2n_occ_update(
       g.table, g.primes, g.bias, g.mul, head.first.data_ptr<float>(), head.second.data_ptr<float>(),
       f2n::fptr(u), density_.data_ptr<float>(),
-      reinterpret_cast<uint32_t *>(words_.data_ptr<int32_t>()), (int)G_, g.L, g.F, g.T,
+      reinterpret_cast<uint32_t *>(words_.data_ptr<int32_t>()), (int)G_, g.L_walk, g.F, g.T,
       g.level_stride, 3.f, threshold, decay, f2n::current_stream(words_)),
     "f2n_occ_update");
 }

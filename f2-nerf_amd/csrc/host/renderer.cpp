@@ -213,6 +213,7 @@ public:
     Hash3DAnchored * field = hash3d_info.toCustomClass<Hash3DAnchoredInfo>()->hash3d_;
     ctx->saved_data["hash3d_info"] = hash3d_info;
     ctx->saved_data["n_rays"] = rays_o.size(0);
+    ctx->saved_data["L_walk"] = (int64_t)field->walk_levels();  // the levels the encoding walked
     ctx->save_for_backward(
       {f2n::dev_f32(pts.detach(), "kept pts"), f2n::dev_f32(t.detach(), "kept t"),
        f2n::dev_i32(bounds, "kept bounds"), f2n::dev_f32(rays_d.detach(), "rays_d"),
@@ -240,6 +241,7 @@ public:
           ctx->saved_data["hash3d_info"].toCustomClass<Hash3DAnchoredInfo>()->hash3d_;
         const int64_t n = pts.size(0);
         const f2n::FieldArgs fa = field->kernel_args(table16);
+        const int L_walk = (int)ctx->saved_data["L_walk"].toInt();
         const auto [g, ld_point, ld_chan] = f2n::encoding_grad_strides(g_enc, n, (int64_t)fa.L * fa.F);
         void * stream = f2n::current_stream(pts);
         if (field->options_.exact_point_grad) {
@@ -249,7 +251,7 @@ public:
             f2n_hash_rays_grad_exact(
               pts.data_ptr<float>(), t.data_ptr<float>(), bounds.data_ptr<int32_t>(),
               rays_d.data_ptr<float>(), fa.table, fa.primes, fa.bias, fa.mul, g.data_ptr<float>(),
-              ld_point, ld_chan, d_o.data_ptr<float>(), d_d.data_ptr<float>(), (int)n_rays, fa.L,
+              ld_point, ld_chan, d_o.data_ptr<float>(), d_d.data_ptr<float>(), (int)n_rays, L_walk,
               fa.F, fa.T, fa.level_stride, stream),
             "f2n_hash_rays_grad_exact");
         } else {
@@ -258,7 +260,7 @@ public:
             f2n_hash_rays_grad(
               pts.data_ptr<float>(), t.data_ptr<float>(), bounds.data_ptr<int32_t>(),
               rays_d.data_ptr<float>(), fa.table, fa.primes, fa.bias, fa.mul, g.data_ptr<float>(),
-              ld_point, ld_chan, d_o.data_ptr<float>(), d_d.data_ptr<float>(), (int)n_rays, fa.L,
+              ld_point, ld_chan, d_o.data_ptr<float>(), d_d.data_ptr<float>(), (int)n_rays, L_walk,
               fa.F, fa.T, fa.level_stride, 128.f /* hash_3d_anchored.cu:190 */, stream),
             "f2n_hash_rays_grad");
         }
@@ -549,7 +551,7 @@ RenderResult Renderer::render_fused(
           rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), f2n::fptr(noise), g.table, g.primes,
           g.bias, g.mul, head.first.data_ptr<float>(), head.second.data_ptr<float>(),
           occupancy_->words_ptr(), (int)occupancy_->resolution(), counts.data_ptr<int32_t>(),
-          len.data_ptr<int32_t>(), n_rays, S, pts_sampler_->options_.step, g.L, g.F, g.T,
+          len.data_ptr<int32_t>(), n_rays, S, pts_sampler_->options_.step, g.L_walk, g.F, g.T,
           g.level_stride, options_.early_stop_trans, 3.f, stream),
         "f2n_density_march_occ");
     } else {
@@ -558,7 +560,7 @@ RenderResult Renderer::render_fused(
       f2n_density_march(
         rays_o.data_ptr<float>(), rays_d.data_ptr<float>(), f2n::fptr(noise), g.table, g.primes,
         g.bias, g.mul, head.first.data_ptr<float>(), head.second.data_ptr<float>(),
-        counts.data_ptr<int32_t>(), n_rays, S, pts_sampler_->options_.step, g.L, g.F, g.T,
+        counts.data_ptr<int32_t>(), n_rays, S, pts_sampler_->options_.step, g.L_walk, g.F, g.T,
         g.level_stride, options_.early_stop_trans, 3.f, stream),
       "f2n_density_march");
     }
@@ -899,7 +901,7 @@ Renderer::Shaded Renderer::shade(
     const bool per_ray = kept.ray_dirs.defined();  // (the lean dense route)
     f2n::ShadeOut sh = f2n::shade_rays(
       enc, per_ray ? kept.ray_dirs : kept.dirs, mode == RunningMode::TRAIN ? emb_idx : Tensor(), S,
-      scene_field_->mlp_->weight, scene_field_->mlp_->bias, mlp[0], mlp[1], mlp[2], mlp[3], emb,
+      scene_field_->head_weight(), scene_field_->mlp_->bias, mlp[0], mlp[1], mlp[2], mlp[3], emb,
       per_ray);
     return {sh.logit.unsqueeze(1), sh.rgb};
   }
@@ -907,7 +909,7 @@ Renderer::Shaded Renderer::shade(
   if (mode == RunningMode::TRAIN)
     sample_img = CustomOps::ScatterIdx((int)n_kept, kept.pts_idx_bounds, emb_idx);
   f2n::ShadeOut sh = f2n::shade(
-    enc, kept.dirs, sample_img, scene_field_->mlp_->weight, scene_field_->mlp_->bias, mlp[0],
+    enc, kept.dirs, sample_img, scene_field_->head_weight(), scene_field_->mlp_->bias, mlp[0],
     mlp[1], mlp[2], mlp[3], emb);
   return {sh.logit.unsqueeze(1), sh.rgb};
 }
@@ -973,10 +975,33 @@ Tensor Renderer::ray_normals(const SampleResultFlex & kept, const Tensor & weigh
   f2n::check(
     f2n_ray_normals(
       pts.data_ptr<float>(), bounds.data_ptr<int32_t>(), weights.data_ptr<float>(), g.table,
-      g.primes, g.bias, g.mul, w0.data_ptr<float>(), normals.data_ptr<float>(), (int)n_rays, g.L,
+      g.primes, g.bias, g.mul, w0.data_ptr<float>(), normals.data_ptr<float>(), (int)n_rays, g.L_walk,
       g.F, g.T, g.level_stride, stream),
     "f2n_ray_normals");
   return normals;
+}
+
+// ---- level weights -------------------------------------------------------------------------------
+
+double f2n::CoarseToFine::alpha_at(double it, int64_t L) const
+{
+  double u = end > start ? (it - start) / (end - start) : (it >= start ? 1. : 0.);
+  u = std::min(1., std::max(0., u));
+  return base + ((double)L - base) * u;
+}
+
+std::pair<Tensor, int64_t> f2n::level_weights(double alpha, int64_t L)
+{
+  TORCH_CHECK(L >= 1 && L <= F2N_MAX_LEVELS, "level_weights: n_levels out of range");
+  Tensor w = torch::empty({L}, torch::TensorOptions().dtype(torch::kFloat32));
+  int l_active = 0;
+  f2n::check(f2n_level_weights(alpha, (int)L, w.data_ptr<float>(), &l_active), "f2n_level_weights");
+  return {w, (int64_t)l_active};
+}
+
+void Renderer::set_coarse_to_fine(double alpha)
+{
+  scene_field_->set_level_weights(f2n::level_weights(alpha, scene_field_->options_.n_levels).first);
 }
 
 // ---- one-pass inference render ---------------------------------------------------------------------
@@ -1029,13 +1054,14 @@ void Renderer::render_rays_into(
   Hash3DAnchored & field = *scene_field_;
   const Tensor table16 = field.table_f16();
   const f2n::FieldArgs g = field.kernel_args(table16);
-  const Tensor w_h = f2n::dev_f32(field.mlp_->weight.detach(), "field head weight");
+  const Tensor w_h = f2n::dev_f32(field.head_weight().detach(), "field head weight");
   const Tensor b_h = f2n::dev_f32(field.mlp_->bias.detach(), "field head bias");
   auto mlp = shader_->mlp_params();
   const Tensor w1 = f2n::dev_f32(mlp[0].detach(), "shader w1"), b1 = f2n::dev_f32(mlp[1].detach(), "shader b1");
   const Tensor w2 = f2n::dev_f32(mlp[2].detach(), "shader w2"), b2 = f2n::dev_f32(mlp[3].detach(), "shader b2");
   const Tensor emb = train ? f2n::dev_f32(app_emb_.detach(), "app_emb") : Tensor();
   void * stream = f2n::current_stream(rays_o);
+  // (the level-of-detail entries: g.L_walk == g.L is the entry without it, launch for launch)
   // 0: one launch; otherwise the head (n_head >= S: whole rays) and, for a shorter head, the tail
   const int head_opt = options_.one_pass_head;
   const int n_head = head_opt < 0 ? S : std::min(head_opt, S);
@@ -1057,17 +1083,20 @@ void Renderer::render_rays_into(
     occupancy_ ? occupancy_->words_ptr() : nullptr,                                                \
     occupancy_ ? (int)occupancy_->resolution() : 0, bg.data_ptr<float>(),                          \
     colors.data_ptr<float>(), depths.data_ptr<float>(), last_trans.data_ptr<float>(),              \
-    kept.data_ptr<int32_t>(), nullptr, n_rays, S, pts_sampler_->options_.step, g.L, g.F, g.T,      \
+    kept.data_ptr<int32_t>(), nullptr, n_rays, S, pts_sampler_->options_.step, g.L, g.L_walk, g.F, \
+    g.T,                                                                                           \
     g.level_stride, options_.early_stop_trans, 3.f, 1e-2f
   if (head_opt == 0) {
-    f2n::check(f2n_render_rays(F2N_RENDER_RAYS_ARGS, stream), "f2n_render_rays");
+    f2n::check(f2n_render_rays_lod(F2N_RENDER_RAYS_ARGS, stream), "f2n_render_rays_lod");
     return;
   }
   f2n::check(
-    f2n_render_rays_head(F2N_RENDER_RAYS_ARGS, n_head, state, stream), "f2n_render_rays_head");
+    f2n_render_rays_head_lod(F2N_RENDER_RAYS_ARGS, n_head, state, stream),
+    "f2n_render_rays_head_lod");
   if (n_head < S)
     f2n::check(
-      f2n_render_rays_tail(F2N_RENDER_RAYS_ARGS, n_head, state, stream), "f2n_render_rays_tail");
+      f2n_render_rays_tail_lod(F2N_RENDER_RAYS_ARGS, n_head, state, stream),
+      "f2n_render_rays_tail_lod");
 #undef F2N_RENDER_RAYS_ARGS
 }
 

@@ -263,6 +263,19 @@ public:
   void set_background(std::shared_ptr<f2n::EnvMap> env) { background_ = std::move(env); }
   const std::shared_ptr<f2n::EnvMap> & background() const { return background_; }
 
+  // Per-level weights of the field (Hash3DAnchored::set_level_weights): coarse-to-fine training and
+  // level-of-detail renders.  Never set (the default): every route as without these calls, launch for
+  // launch and bit for bit; all ones: the same bits.  Folded into the field head, so every route --
+  // op by op, march, dense, lean bucketed, with an occupancy grid, train_step, render_rays and the
+  // one-pass path (the f2n_render_rays_lod entries), normals, the mesh, the Localizer -- honours them.
+  // set_coarse_to_fine(alpha): the weights of f2n_level_weights for a progress alpha in [1, L]
+  // (f2n::CoarseToFine::alpha_at makes one from an iteration).  Values move in place: a captured
+  // step stays valid while the number of active levels does not change.  Checkpoints hold the raw
+  // parameters; the schedule's state stays with the caller.
+  void set_level_weights(const Tensor & weights) { scene_field_->set_level_weights(weights); }
+  void set_coarse_to_fine(double alpha);
+  void clear_level_weights() { scene_field_->clear_level_weights(); }
+
   RendererOptions options_;
   std::shared_ptr<PtsSampler> pts_sampler_;
   std::shared_ptr<Hash3DAnchored> scene_field_;
@@ -419,6 +432,18 @@ struct TrainStepResult
 // Caller indices of the rays sorted into pixel-compact bundles: the stable sort of their
 // f2n_ray_keys, int64 [n].
 Tensor ray_order(const Tensor & rays_d);
+
+// The coarse-to-fine schedule of bundle-adjusting fields: the progress
+//   alpha = base + (L - base) * clamp((it - start) / (end - start), 0, 1)
+// that Renderer::set_coarse_to_fine takes.  end <= start: `base` before start, L from start on.
+struct CoarseToFine
+{
+  double start = 0., end = 1., base = 1.;
+  double alpha_at(double it, int64_t L) const;
+};
+
+// f2n_level_weights as a CPU tensor [L] and its number of active levels.
+std::pair<Tensor, int64_t> level_weights(double alpha, int64_t L);
 
 TrainStepResult train_step(
   Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,

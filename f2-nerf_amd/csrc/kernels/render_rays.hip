@@ -35,7 +35,7 @@ namespace
 
 template <int C, int F, bool POW2>
 __global__ __launch_bounds__(RShape<C>::kWaves * 64) void render_rays_kernel(
-  F2N_RENDER_PARAMS, int corner_order)
+  F2N_RENDER_PARAMS, int corner_order, int L_active)
 {
   using R = RShape<C>;
   using FS = typename R::FS;
@@ -53,16 +53,42 @@ __global__ __launch_bounds__(RShape<C>::kWaves * 64) void render_rays_kernel(
   const RenderArgs a = {rays_o, rays_d, noise,      table, primes,     bias,  mul, p_w_h,
                         p_emb,  ray_img, bits,      G,     bg,         colors, depths, last_trans,
                         kept,   len,     S,         step,  T,          level_stride, t_thresh,
-                        density_shift,   t_shift, corner_order};
+                        density_shift,   t_shift, corner_order, L_active};
   const RayResume whole = {0, {0.f, 0.f, 0.f, 0.f}, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0, 0};
   __half * tile = reinterpret_cast<__half *>(lds_all + FS::kWFloats + wave * R::kWaveFloats);
   float * OUT = lds_all + FS::kWFloats + wave * R::kWaveFloats + R::kTileFloats;
+  zero_tile_tail<C, F>(tile, L_active, lane);
 
   for (int r = (int)blockIdx.x * R::kWaves + wave; r < n_rays; r += (int)gridDim.x * R::kWaves)
     render_one_ray<C, F, POW2>(a, r, whole, lds_w, tile, OUT, lane, has_emb, has_grid, bias0);
 }
 
 }  // namespace
+
+extern "C" int f2n_render_rays_lod(
+  const float * rays_o, const float * rays_d, const float * noise, const uint16_t * table,
+  const int32_t * primes, const float * bias, const float * mul, const float * w_h,
+  const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
+  const float * app_emb, const int32_t * ray_img, const uint32_t * occ_bits, int G, const float * bg,
+  float * colors, float * depths, float * last_trans, int32_t * kept, int32_t * len, int n_rays,
+  int S, float step, int L, int L_active, int F, uint32_t T, int64_t level_stride, float t_thresh,
+  float density_shift, float t_shift, void * stream)
+{
+  bool launch;
+  const int st = render_args_status(F2N_RENDER_KARGS, L, F, L_active, S, nullptr, &launch);
+  if (st != F2N_OK || !launch) return st;
+  hipStream_t s = (hipStream_t)stream;
+  // persistent workgroups: the weight operands are staged once per workgroup, not once per 8 rays
+  f2n_dispatch_width_field(L, F, T, [&](auto cc, auto ff, auto p2) {
+    using R = RShape<decltype(cc)::value>;
+    const unsigned grid = std::min<unsigned>(f2n_div_up(n_rays, R::kWaves), 512u);
+    hipLaunchKernelGGL(
+      (render_rays_kernel<decltype(cc)::value, decltype(ff)::value, decltype(p2)::value>),
+      dim3(grid), dim3(R::kWaves * 64), 0, s, F2N_RENDER_KARGS,
+      f2n_get_option(F2N_OPT_GATHER_PAIRED), L_active);
+  });
+  return f2n_launch_status();
+}
 
 extern "C" int f2n_render_rays(
   const float * rays_o, const float * rays_d, const float * noise, const uint16_t * table,
@@ -73,18 +99,8 @@ extern "C" int f2n_render_rays(
   int S, float step, int L, int F, uint32_t T, int64_t level_stride, float t_thresh,
   float density_shift, float t_shift, void * stream)
 {
-  bool launch;
-  const int st = render_args_status(F2N_RENDER_KARGS, L, F, S, nullptr, &launch);
-  if (st != F2N_OK || !launch) return st;
-  hipStream_t s = (hipStream_t)stream;
-  // persistent workgroups: the weight operands are staged once per workgroup, not once per 8 rays
-  f2n_dispatch_width_field(L, F, T, [&](auto cc, auto ff, auto p2) {
-    using R = RShape<decltype(cc)::value>;
-    const unsigned grid = std::min<unsigned>(f2n_div_up(n_rays, R::kWaves), 512u);
-    hipLaunchKernelGGL(
-      (render_rays_kernel<decltype(cc)::value, decltype(ff)::value, decltype(p2)::value>),
-      dim3(grid), dim3(R::kWaves * 64), 0, s, F2N_RENDER_KARGS,
-      f2n_get_option(F2N_OPT_GATHER_PAIRED));
-  });
-  return f2n_launch_status();
+  return f2n_render_rays_lod(
+    rays_o, rays_d, noise, table, primes, bias, mul, w_h, b_h, w1, b1, w2, b2, app_emb, ray_img,
+    occ_bits, G, bg, colors, depths, last_trans, kept, len, n_rays, S, step, L, L, F, T, level_stride,
+    t_thresh, density_shift, t_shift, stream);
 }

@@ -76,13 +76,14 @@ __device__ __forceinline__ float group_sum(float v, int m, int lane)
 
 template <int C, int F, bool POW2>
 __global__ __launch_bounds__(HShape<C>::kWaves * 64) void render_rays_head_kernel(
-  F2N_RENDER_PARAMS, float * __restrict__ state, int n_head, int corner_order)
+  F2N_RENDER_PARAMS, float * __restrict__ state, int n_head, int corner_order,
+  int L_active)
 {
   using H = HShape<C>;
   using R = RShape<C>;
   using FS = typename R::FS;
   using RL = RayLanes<8>;
-  constexpr int L = C / F, kS1 = FS::kS1, kPitch = R::kPitch;
+  constexpr int kS1 = FS::kS1, kPitch = R::kPitch;
   __shared__ __attribute__((aligned(16))) float lds_all[H::kLdsFloats];
   float * lds_w = lds_all;
   stage_fwd_weights<C, H::kWaves>(lds_w, p_w_h, p_b_h, p_w1, p_b1, p_w2, p_b2);
@@ -105,6 +106,7 @@ __global__ __launch_bounds__(HShape<C>::kWaves * 64) void render_rays_head_kerne
   const bool hand_over = n_head < S;  // (then n_head is a multiple of 64)
   const int k_end = hand_over ? n_head : S;
   const int n_groups = (n_rays + 7) >> 3;
+  zero_tile_tail<C, F>(tile, L_active, lane);
 
   for (int w8 = (int)blockIdx.x * H::kWaves + wave; w8 < n_groups; w8 += (int)gridDim.x * H::kWaves) {
     const int r_raw = (w8 << 3) + g;
@@ -150,7 +152,7 @@ __global__ __launch_bounds__(HShape<C>::kWaves * 64) void render_rays_head_kerne
       if (om != 0ull) {  // (wave-uniform)
         if (occ) {       // (no cross-lane move inside)
           const float logit = density_chain<F, POW2>(
-            x, y, z, table, primes, bias, mul, p_w_h, bias0, L, T, level_stride, corner_order,
+            x, y, z, table, primes, bias, mul, p_w_h, bias0, L_active, T, level_stride, corner_order,
             [&](int c, __half hv) { tile[c * kPitch + lane] = hv; });
           const float sigma = expf(logit - density_shift);
           sec = sigma * sm.dt;
@@ -285,7 +287,8 @@ __global__ __launch_bounds__(HShape<C>::kWaves * 64) void render_rays_head_kerne
 
 template <int C, int F, bool POW2>
 __global__ __launch_bounds__(RShape<C>::kWaves * 64) void render_rays_tail_kernel(
-  F2N_RENDER_PARAMS, const float * __restrict__ state, int n_head, int corner_order)
+  F2N_RENDER_PARAMS, const float * __restrict__ state, int n_head, int corner_order,
+  int L_active)
 {
   using R = RShape<C>;
   using FS = typename R::FS;
@@ -302,9 +305,10 @@ __global__ __launch_bounds__(RShape<C>::kWaves * 64) void render_rays_tail_kerne
   const RenderArgs a = {rays_o, rays_d, noise,      table, primes,     bias,  mul, p_w_h,
                         p_emb,  ray_img, bits,      G,     bg,         colors, depths, last_trans,
                         kept,   len,     S,         step,  T,          level_stride, t_thresh,
-                        density_shift,   t_shift, corner_order};
+                        density_shift,   t_shift, corner_order, L_active};
   __half * tile = reinterpret_cast<__half *>(lds_all + FS::kWFloats + wave * R::kWaveFloats);
   float * OUT = lds_all + FS::kWFloats + wave * R::kWaveFloats + R::kTileFloats;
+  zero_tile_tail<C, F>(tile, L_active, lane);
 
   for (int r = (int)blockIdx.x * R::kWaves + wave; r < n_rays; r += (int)gridDim.x * R::kWaves) {
     // (r lives in scalar registers: the state is fetched with scalar loads, the skip is wave-uniform)
@@ -323,17 +327,17 @@ extern "C" int64_t f2n_render_rays_state_bytes(int n_rays)
   return n_rays < 0 ? -1 : (int64_t)n_rays * kStateWords * 4;
 }
 
-extern "C" int f2n_render_rays_head(
+extern "C" int f2n_render_rays_head_lod(
   const float * rays_o, const float * rays_d, const float * noise, const uint16_t * table,
   const int32_t * primes, const float * bias, const float * mul, const float * w_h,
   const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
   const float * app_emb, const int32_t * ray_img, const uint32_t * occ_bits, int G, const float * bg,
   float * colors, float * depths, float * last_trans, int32_t * kept, int32_t * len, int n_rays,
-  int S, float step, int L, int F, uint32_t T, int64_t level_stride, float t_thresh,
+  int S, float step, int L, int L_active, int F, uint32_t T, int64_t level_stride, float t_thresh,
   float density_shift, float t_shift, int n_head, void * state, void * stream)
 {
   bool launch;
-  const int st = render_args_status(F2N_RENDER_KARGS, L, F, n_head, state, &launch);
+  const int st = render_args_status(F2N_RENDER_KARGS, L, F, L_active, n_head, state, &launch);
   if (st != F2N_OK || !launch) return st;
   hipStream_t s = (hipStream_t)stream;
   // persistent workgroups, 12 waves of 8 rays each, one per CU
@@ -343,9 +347,49 @@ extern "C" int f2n_render_rays_head(
     hipLaunchKernelGGL(
       (render_rays_head_kernel<decltype(cc)::value, decltype(ff)::value, decltype(p2)::value>),
       dim3(grid), dim3(H::kWaves * 64), 0, s, F2N_RENDER_KARGS, static_cast<float *>(state),
-      n_head, f2n_get_option(F2N_OPT_GATHER_PAIRED));
+      n_head, f2n_get_option(F2N_OPT_GATHER_PAIRED), L_active);
   });
   return f2n_launch_status();
+}
+
+extern "C" int f2n_render_rays_tail_lod(
+  const float * rays_o, const float * rays_d, const float * noise, const uint16_t * table,
+  const int32_t * primes, const float * bias, const float * mul, const float * w_h,
+  const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
+  const float * app_emb, const int32_t * ray_img, const uint32_t * occ_bits, int G, const float * bg,
+  float * colors, float * depths, float * last_trans, int32_t * kept, int32_t * len, int n_rays,
+  int S, float step, int L, int L_active, int F, uint32_t T, int64_t level_stride, float t_thresh,
+  float density_shift, float t_shift, int n_head, const void * state, void * stream)
+{
+  bool launch;
+  const int st = render_args_status(F2N_RENDER_KARGS, L, F, L_active, n_head, state, &launch);
+  if (st != F2N_OK || !launch) return st;
+  if (n_head >= S) return F2N_OK;  // the head rendered every ray whole: nothing is pending
+  hipStream_t s = (hipStream_t)stream;
+  f2n_dispatch_width_field(L, F, T, [&](auto cc, auto ff, auto p2) {
+    using R = RShape<decltype(cc)::value>;
+    const unsigned grid = std::min<unsigned>(f2n_div_up(n_rays, R::kWaves), 512u);
+    hipLaunchKernelGGL(
+      (render_rays_tail_kernel<decltype(cc)::value, decltype(ff)::value, decltype(p2)::value>),
+      dim3(grid), dim3(R::kWaves * 64), 0, s, F2N_RENDER_KARGS, static_cast<const float *>(state),
+      n_head, f2n_get_option(F2N_OPT_GATHER_PAIRED), L_active);
+  });
+  return f2n_launch_status();
+}
+
+extern "C" int f2n_render_rays_head(
+  const float * rays_o, const float * rays_d, const float * noise, const uint16_t * table,
+  const int32_t * primes, const float * bias, const float * mul, const float * w_h,
+  const float * b_h, const float * w1, const float * b1, const float * w2, const float * b2,
+  const float * app_emb, const int32_t * ray_img, const uint32_t * occ_bits, int G, const float * bg,
+  float * colors, float * depths, float * last_trans, int32_t * kept, int32_t * len, int n_rays,
+  int S, float step, int L, int F, uint32_t T, int64_t level_stride, float t_thresh,
+  float density_shift, float t_shift, int n_head, void * state, void * stream)
+{
+  return f2n_render_rays_head_lod(
+    rays_o, rays_d, noise, table, primes, bias, mul, w_h, b_h, w1, b1, w2, b2, app_emb, ray_img,
+    occ_bits, G, bg, colors, depths, last_trans, kept, len, n_rays, S, step, L, L, F, T, level_stride,
+    t_thresh, density_shift, t_shift, n_head, state, stream);
 }
 
 extern "C" int f2n_render_rays_tail(
@@ -357,18 +401,8 @@ extern "C" int f2n_render_rays_tail(
   int S, float step, int L, int F, uint32_t T, int64_t level_stride, float t_thresh,
   float density_shift, float t_shift, int n_head, const void * state, void * stream)
 {
-  bool launch;
-  const int st = render_args_status(F2N_RENDER_KARGS, L, F, n_head, state, &launch);
-  if (st != F2N_OK || !launch) return st;
-  if (n_head >= S) return F2N_OK;  // the head rendered every ray whole: nothing is pending
-  hipStream_t s = (hipStream_t)stream;
-  f2n_dispatch_width_field(L, F, T, [&](auto cc, auto ff, auto p2) {
-    using R = RShape<decltype(cc)::value>;
-    const unsigned grid = std::min<unsigned>(f2n_div_up(n_rays, R::kWaves), 512u);
-    hipLaunchKernelGGL(
-      (render_rays_tail_kernel<decltype(cc)::value, decltype(ff)::value, decltype(p2)::value>),
-      dim3(grid), dim3(R::kWaves * 64), 0, s, F2N_RENDER_KARGS, static_cast<const float *>(state),
-      n_head, f2n_get_option(F2N_OPT_GATHER_PAIRED));
-  });
-  return f2n_launch_status();
+  return f2n_render_rays_tail_lod(
+    rays_o, rays_d, noise, table, primes, bias, mul, w_h, b_h, w1, b1, w2, b2, app_emb, ray_img,
+    occ_bits, G, bg, colors, depths, last_trans, kept, len, n_rays, S, step, L, L, F, T, level_stride,
+    t_thresh, density_shift, t_shift, n_head, state, stream);
 }

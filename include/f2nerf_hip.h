@@ -1105,6 +1105,72 @@ int f2n_render_rays_tail(
   float t_thresh, float density_shift, float t_shift, int n_head, const void * state,
   void * stream);
 
+/* ------------------------------------------------------------------ level weights -------------- */
+
+/* Coarse-to-fine weights of the encoding's L levels from a progress alpha in [1, L] (the schedule of
+ * bundle-adjusting fields), for level l = 0 .. L-1:
+ *   w_l = 0                               for alpha - l <= 0
+ *   w_l = (1 - cos(pi (alpha - l))) / 2   for 0 < alpha - l < 1
+ *   w_l = 1                               otherwise
+ * evaluated in double and rounded to f32.  No counterpart in the reference, whose
+ * Hash3DAnchored::Query (src/hash_3d_anchored.cpp:79-87) hands every level to the head at full
+ * weight; a caller applies the weights by scaling the head's columns (W_h[:, lF..lF+F) by w_l), which
+ * every kernel that takes w_h then honours with no change of its own.
+ *   w_host    [L] floats, HOST memory
+ *   l_active  1 + the index of the last non-zero weight (>= 1): the levels a level-of-detail entry
+ *             below has to walk
+ * Host arithmetic, no HIP work.  F2N_E_INVALID_ARG for L < 1, L > F2N_MAX_LEVELS, alpha < 1, a
+ * non-finite alpha or a NULL pointer; alpha > L is taken as L. */
+int f2n_level_weights(double alpha, int L, float * w_host, int * l_active);
+
+/* The three one-pass entries above with a level of detail: the field is walked over its first
+ * L_active levels only, and the network sees zeros for the others -- what a head whose columns from
+ * L_active * F on are zero computes, without gathering what it would multiply by zero.
+ * No counterpart in the reference, whose Renderer::Render (src/renderer.cpp:33-123) always queries
+ * every level.  Each wavefront clears rows [L_active * F, C) of its f16 tile once, before its first stride;
+ * table, primes, bias, mul, w_h and level_stride stay those of the full L.
+ *   L_active  1 <= L_active <= L, else F2N_E_INVALID_ARG (after every check of the entry without it,
+ *             before any HIP work).  L_active == L: the entry without it, launch for launch and bit
+ *             for bit -- which is how those entries are implemented.
+ * Everything else as the entry of the same name without the suffix. */
+int f2n_render_rays_lod(
+  const float * rays_o, const float * rays_d, const float * noise /* [n_rays,S] or NULL */,
+  const uint16_t * table, const int32_t * primes, const float * bias, const float * mul,
+  const float * w_h, const float * b_h, const float * w1, const float * b1,
+  const float * w2, const float * b2,
+  const float * app_emb, const int32_t * ray_img /* both NULL: no appearance embedding */,
+  const uint32_t * occ_bits /* NULL: no grid */, int G,
+  const float * bg, float * colors, float * depths, float * last_trans,
+  int32_t * kept, int32_t * len /* may be NULL */,
+  int n_rays, int S, float step, int L, int L_active, int F, uint32_t T, int64_t level_stride,
+  float t_thresh, float density_shift, float t_shift, void * stream);
+/* f2n_render_rays_head over L_active levels (see f2n_render_rays_lod; src/renderer.cpp:33-123). */
+int f2n_render_rays_head_lod(
+  const float * rays_o, const float * rays_d, const float * noise /* [n_rays,S] or NULL */,
+  const uint16_t * table, const int32_t * primes, const float * bias, const float * mul,
+  const float * w_h, const float * b_h, const float * w1, const float * b1,
+  const float * w2, const float * b2,
+  const float * app_emb, const int32_t * ray_img /* both NULL: no appearance embedding */,
+  const uint32_t * occ_bits /* NULL: no grid */, int G,
+  const float * bg, float * colors, float * depths, float * last_trans,
+  int32_t * kept, int32_t * len /* may be NULL */,
+  int n_rays, int S, float step, int L, int L_active, int F, uint32_t T, int64_t level_stride,
+  float t_thresh, float density_shift, float t_shift, int n_head, void * state, void * stream);
+/* f2n_render_rays_tail over L_active levels (see f2n_render_rays_lod; src/renderer.cpp:33-123):
+ * the same L_active as the head before it. */
+int f2n_render_rays_tail_lod(
+  const float * rays_o, const float * rays_d, const float * noise /* [n_rays,S] or NULL */,
+  const uint16_t * table, const int32_t * primes, const float * bias, const float * mul,
+  const float * w_h, const float * b_h, const float * w1, const float * b1,
+  const float * w2, const float * b2,
+  const float * app_emb, const int32_t * ray_img /* both NULL: no appearance embedding */,
+  const uint32_t * occ_bits /* NULL: no grid */, int G,
+  const float * bg, float * colors, float * depths, float * last_trans,
+  int32_t * kept, int32_t * len /* may be NULL */,
+  int n_rays, int S, float step, int L, int L_active, int F, uint32_t T, int64_t level_stride,
+  float t_thresh, float density_shift, float t_shift, int n_head, const void * state,
+  void * stream);
+
 /* ------------------------------------------------------------------ optimiser (section 8f) ----- */
 
 /* One fused pass of torch::optim::Adam::step() over one f32 parameter tensor -- the call at

@@ -30,6 +30,12 @@
                    cameras, and the PSNR of four held-out views rendered from their true poses.
                    --exact-grad: the refiner run receives the encoding's true derivative.  Its
                    magnitude is a third to a quarter of Q5's: --pose-lr is NOT rescaled.
+                   --c2f START:END:BASE: coarse-to-fine level weights on the refiner run
+                   (host.CoarseToFine: alpha = BASE before iteration START, n_levels from END on,
+                   Renderer.set_coarse_to_fine every iteration; the held-out views are rendered with
+                   the weights of the moment).  --pose-lr-decay G: the pose optimiser's rate falls
+                   to G * --pose-lr over the run, exponentially (done here, in the tool: the refiner
+                   has no schedule of its own).
 
 Prints one JSON line per measurement (also appended to --out).
 """
@@ -221,6 +227,11 @@ def recover_once(host, dev, args, refine):
         refiner.set_fixed(fixed)
         pose_opt = refiner.make_adam(args.pose_lr)
     bg = torch.tensor(scene.BACKGROUND, device=dev).expand(512, 3).contiguous()
+    c2f = None
+    if args.c2f and refine:
+        start, end, base = (float(v) for v in args.c2f.split(":"))
+        c2f = host.CoarseToFine(start=start, end=end, base=base)
+        hr.set_coarse_to_fine(c2f.alpha_at(0.0, scene.L))
 
     def report(it):
         est = refiner.poses().detach() if refine else noisy
@@ -234,11 +245,19 @@ def recover_once(host, dev, args, refine):
                     "psnr_heldout": round(scene.psnr(views, truth), 3),
                     "rot_noise_deg": round(math.degrees(args.rot_noise), 3),
                     "pos_noise": args.pos_noise, "pose_lr": args.pose_lr if refine else None,
-                    "exact_grad": bool(args.exact_grad and refine)},
+                    "exact_grad": bool(args.exact_grad and refine),
+                    "c2f": args.c2f if c2f is not None else None,
+                    "alpha": round(c2f.alpha_at(float(it), scene.L), 4) if c2f is not None else None,
+                    "active_levels": int(hr.active_levels()),
+                    "pose_lr_decay": args.pose_lr_decay if refine else None},
                    args.out)
 
     report(0)
     for it in range(1, args.iters + 1):
+        if c2f is not None:
+            hr.set_coarse_to_fine(c2f.alpha_at(float(it), scene.L))
+        if refine and args.pose_lr_decay != 1.0:
+            pose_opt.set_lr(args.pose_lr * args.pose_lr_decay ** (it / args.iters))
         if refine:
             o, d, gt, cam = refiner.sample_random_rays(intr, hw, hw, 512, images=images)
             pose_opt.zero_grad()
@@ -270,6 +289,10 @@ def main():
     ap.add_argument("--pos-noise", type=float, default=0.02)
     ap.add_argument("--exact-grad", action="store_true",
                     help="Hash3DAnchoredOptions::exact_point_grad on: the encoding's true derivative")
+    ap.add_argument("--c2f", default="", metavar="START:END:BASE",
+                    help="--part recover: coarse-to-fine level weights on the refiner run")
+    ap.add_argument("--pose-lr-decay", type=float, default=1.0,
+                    help="--part recover: the pose rate ends at this fraction of --pose-lr")
     ap.add_argument("--inner", type=int, default=20, help="--part kernels: launches per timed window")
     ap.add_argument("--no-baseline", action="store_true",
                     help="--part recover: skip the run without a refiner")
