@@ -145,3 +145,30 @@ def call(name, *args, stream=None):
     st = fn(*[_ptr(a) for a in args], stream)
     if st != 0:
         raise F2NError("%s failed: %s (%d)" % (full, L.status_string(st), st))
+
+
+def robust_workspace_words(n_rays):
+    """f2n_robust_workspace_words: the u32 words f2n_robust_weights needs, 0 for an invalid n_rays."""
+    return int(lib().cdll.f2n_robust_workspace_words(int(n_rays)))
+
+
+def robust_weights(colors, target, ray_weight=None, P=0, nbhd=8, quantile=0.5, box_thresh=0.5,
+                   nbhd_thresh=0.6, out=None):
+    """f2n_robust_weights on device tensors: colors, target [n, 3] f32, ray_weight [n] f32 or None.
+    -> (weight [n] f32, omega [n] u8, stats [4] f32 = {T, N_c, sum w0, sum omega}).  `out` may hand in
+    (weight, omega, stats, workspace) to write into, e.g. under a graph capture."""
+    import torch
+
+    n = colors.shape[0]
+    if out is None:
+        words = robust_workspace_words(n)
+        if words == 0:
+            raise F2NError("f2n_robust_weights: n_rays must be in 1 .. 2^24 - 1")
+        out = (torch.empty(n, dtype=torch.float32, device=colors.device),
+               torch.empty(n, dtype=torch.uint8, device=colors.device),
+               torch.empty(4, dtype=torch.float32, device=colors.device),
+               torch.empty(words, dtype=torch.int32, device=colors.device))
+    weight, omega, stats, workspace = out
+    call("robust_weights", colors, target, ray_weight, n, P, nbhd, quantile, box_thresh,
+         nbhd_thresh, weight, omega, stats, workspace)
+    return weight, omega, stats

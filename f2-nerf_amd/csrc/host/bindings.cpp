@@ -635,6 +635,31 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def_readwrite("ssim_weight", &f2n::PatchLoss::ssim_weight)
     .def_property_readonly(
       "patch_weight", [](const f2n::PatchLoss & p) { return tensor_or_none(p.patch_weight); });
+  py::class_<f2n::RobustLoss>(m, "RobustLoss")
+    .def(
+      py::init([](float quantile, float box_thresh, float nbhd_thresh, int patch, int nbhd) {
+        return f2n::RobustLoss{quantile, box_thresh, nbhd_thresh, patch, nbhd};
+      }),
+      py::arg("quantile") = 1.f, py::arg("box_thresh") = .5f, py::arg("nbhd_thresh") = .6f,
+      py::arg("patch") = 0, py::arg("nbhd") = 8,
+      "the trimmed colour loss of f2n_robust_weights: the quantile of the residuals kept (>= 1: off), "
+      "the thresholds of the 3 x 3 box and of the block vote, the patch side P (0: scattered rays) "
+      "and the side of a block")
+    .def_readwrite("quantile", &f2n::RobustLoss::quantile)
+    .def_readwrite("box_thresh", &f2n::RobustLoss::box_thresh)
+    .def_readwrite("nbhd_thresh", &f2n::RobustLoss::nbhd_thresh)
+    .def_readwrite("patch", &f2n::RobustLoss::patch)
+    .def_readwrite("nbhd", &f2n::RobustLoss::nbhd);
+  m.def(
+    "robust_weights",
+    [](const Tensor & colors, const Tensor & target, const f2n::RobustLoss & opt,
+       const c10::optional<Tensor> & ray_weight) {
+      f2n::RobustWeights w = f2n::robust_weights(colors, target, opt_tensor(ray_weight), opt);
+      return py::make_tuple(w.weight, w.omega, w.stats);
+    },
+    py::arg("colors"), py::arg("target"), py::arg("opt"), py::arg("ray_weight") = py::none(),
+    "f2n_robust_weights: colors, target [n,3], ray_weight [n] | None -> (weight [n] f32, omega [n] "
+    "u8, stats [4] = {T, N_c, sum of the pixel labels, sum of the final labels}); no host read");
   py::class_<f2n::DepthLossOptions>(m, "DepthLossOptions")
     .def(
       py::init([](float empty, float near, float expected, float eps) {
@@ -871,6 +896,37 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
       "and an optional RaySupervision: always six elements, (loss, sq_err_sum, n_values, "
       "n_samples, weight_sum | None, colors | None).  patch 0 or ssim_weight 0 is "
       "train_step_supervised, launch for launch")
+    .def(
+      "train_step_robust",
+      [](Renderer & r, const Tensor & o, const Tensor & d, const Tensor & emb_idx, const Tensor & gt,
+         const f2n::RobustLoss & robust, const f2n::PatchLoss & patch,
+         const f2n::RaySupervision & sup, float var_loss_weight,
+         const c10::optional<Tensor> & noise, const c10::optional<Tensor> & bg, bool backward,
+         float dist_loss_weight, const c10::optional<Tensor> & depth_target,
+         const f2n::DepthLossOptions & depth_loss) {
+        f2n::TrainStepResult out;
+        {
+          py::gil_scoped_release no_gil;
+          out = f2n::train_step(
+            r, o, d, emb_idx, gt, var_loss_weight, dist_loss_weight, opt_tensor(noise),
+            opt_tensor(bg), backward, opt_tensor(depth_target), depth_loss, sup, patch, robust);
+        }
+        return py::make_tuple(
+          out.loss, out.sq_err_sum, out.n_values, out.n_samples, tensor_or_none(out.weight_sum),
+          tensor_or_none(out.colors), tensor_or_none(out.robust_weight),
+          tensor_or_none(out.robust_stats));
+      },
+      py::arg("rays_o"), py::arg("rays_d"), py::arg("emb_idx"), py::arg("gt_colors"),
+      py::arg("robust"), py::arg("patch") = f2n::PatchLoss(),
+      py::arg("sup") = f2n::RaySupervision(), py::arg("var_loss_weight") = 0.f,
+      py::arg("noise") = py::none(), py::arg("bg_color") = py::none(), py::arg("backward") = true,
+      py::arg("dist_loss_weight") = 0.f, py::arg("depth_target") = py::none(),
+      py::arg("depth_loss") = f2n::DepthLossOptions(),
+      "train_step with a RobustLoss (the trimmed colour loss: rays the render cannot explain are "
+      "dropped from every per-ray term), an optional PatchLoss and RaySupervision: always eight "
+      "elements, (loss, sq_err_sum, n_values, n_samples, weight_sum | None, colors | None, "
+      "robust_weight | None, robust_stats | None).  quantile >= 1 is train_step_patches, launch for "
+      "launch")
     .def("named_parameters", [](Renderer & r) { return named_params(r); })
     .def("zero_grad", [](Renderer & r) { r.zero_grad(); })
     .def(

@@ -5,6 +5,7 @@
 
 #include "ragged_ops.hpp"
 #include "rays.hpp"
+#include "robust_loss.hpp"
 
 #include <c10/hip/HIPGuard.h>
 #include <hip/hip_runtime_api.h>
@@ -1413,11 +1414,12 @@ static f2n::TrainStepResult train_step_sup(
   const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
   const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
   const f2n::DepthLossOptions & depth_loss, const f2n::RaySupervision & sup,
-  const f2n::PatchLoss * patch)
+  const f2n::PatchLoss * patch, const f2n::RobustLoss * robust = nullptr)
 {
   using namespace f2n;
-  // (no supervision: the call without it, launch for launch)
-  if (!sup.ray_weight.defined() && !sup.alpha.defined())
+  // (no supervision: the call without it, launch for launch; a robust loss makes per-ray weights of
+  // its own, so it takes the body below also when the caller gave none)
+  if (!robust && !sup.ray_weight.defined() && !sup.alpha.defined())
     return train_step_plain(
       renderer, rays_o, rays_d, emb_idx, gt_colors, var_loss_weight, dist_loss_weight, noise,
       bg_color, run_backward, depth_target, depth_loss, sup.want_colors, patch);
@@ -1460,6 +1462,29 @@ static f2n::TrainStepResult train_step_sup(
   RenderResult res = renderer.render_for_loss(
     rays_o, rays_d, emb_idx, RunningMode::TRAIN, noise, bg_color, want_dist,
     want_depth ? depth_target : Tensor(), want_depth ? depth_loss.eps : 0.f, want_opacity);
+  // the colour target the colour loss uses: a gt + (1 - a) bg when the alpha target composites
+  // (formed where it is first needed, so that a step without the robust loss launches as before)
+  Tensor target;
+  const auto colour_target = [&]() {
+    if (target.defined()) return target;
+    target = gt_colors;
+    if (alpha.defined() && !plain_target) {
+      const Tensor a = alpha.unsqueeze(1);
+      target = a * gt_colors.detach() + (1.f - a) * bg_color.detach();
+    }
+    return target;
+  };
+  // The robust loss: the render's own colours, detached, decide which rays the colour loss and the
+  // regularisers see.  From here on its weight m_r omega_r stands wherever the caller's m_r stood --
+  // train_loss_sup, the opacity, distortion and depth terms: a rejected ray regularises nothing.  The
+  // D-SSIM term keeps the caller's patch_weight: it scores a patch as a whole and is not trimmed.
+  Tensor robust_weight, robust_stats;
+  if (robust) {
+    torch::NoGradGuard no_grad;
+    RobustWeights rw = robust_weights(res.colors.detach(), colour_target(), m, *robust);
+    m = robust_weight = rw.weight;
+    robust_stats = rw.stats;
+  }
   Tensor var = res.weight_var.defined() ? res.weight_var
                                         : CustomOps::WeightVar(res.weights, res.idx_start_end);
   if (var_loss_weight == 0.f) var = var.detach();
@@ -1503,16 +1528,10 @@ static f2n::TrainStepResult train_step_sup(
                                 : plain_target ? opacity_term.detach()
                                                : stats[3].detach();
   renderer.last_ssim_loss_ = Tensor();
-  if (patch) {
-    // the colour target the colour loss used: a gt + (1 - a) bg when the alpha target composites
-    Tensor target = gt_colors;
-    if (alpha.defined() && !plain_target) {
-      const Tensor a = alpha.unsqueeze(1);
-      target = a * gt_colors.detach() + (1.f - a) * bg_color.detach();
-    }
-    loss = add_patch_term(renderer, loss, res.colors, target, *patch);
-  }
+  if (patch) loss = add_patch_term(renderer, loss, res.colors, colour_target(), *patch);
   TrainStepResult out;
+  out.robust_weight = robust_weight;
+  out.robust_stats = robust_stats;
   out.loss = loss.detach();
   out.sq_err_sum = stats[4].detach();
   out.n_values = res.colors.numel();
@@ -1545,4 +1564,20 @@ f2n::TrainStepResult f2n::train_step(
   return train_step_sup(
     renderer, rays_o, rays_d, emb_idx, gt_colors, var_loss_weight, dist_loss_weight, noise, bg_color,
     run_backward, depth_target, depth_loss, sup, want_ssim ? &patch : nullptr);
+}
+
+f2n::TrainStepResult f2n::train_step(
+  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
+  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
+  const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
+  const DepthLossOptions & depth_loss, const RaySupervision & sup, const PatchLoss & patch,
+  const RobustLoss & robust)
+{
+  const bool want_ssim = patch.patch != 0 && patch.ssim_weight != 0.f;
+  // (quantile >= 1: the call without it, launch for launch -- the rule for dist_loss_weight == 0)
+  const bool want_robust = !(robust.quantile >= 1.f);
+  return train_step_sup(
+    renderer, rays_o, rays_d, emb_idx, gt_colors, var_loss_weight, dist_loss_weight, noise, bg_color,
+    run_backward, depth_target, depth_loss, sup, want_ssim ? &patch : nullptr,
+    want_robust ? &robust : nullptr);
 }

@@ -37,6 +37,7 @@
 #include "occupancy_grid.hpp"
 #include "points_sampler.hpp"
 #include "rays.hpp"
+#include "robust_loss.hpp"
 #include "sh_shader.hpp"
 
 namespace f2n
@@ -427,6 +428,11 @@ struct TrainStepResult
   // RaySupervision::want_colors only: the render's colours [n_rays, 3], detached (what
   // ErrorMap::accumulate takes); undefined otherwise
   Tensor colors;
+  // RobustLoss only: the weight m_r omega_r the step's terms used ([n_rays], detached; what
+  // ErrorMap::accumulate takes as its ray_weight, so that the map does not chase what the loss
+  // rejected) and f2n_robust_weights' {T, N_c, sum of the pixel labels, sum of the final labels}
+  // ([4], device); both undefined when the robust loss is off
+  Tensor robust_weight, robust_stats;
 };
 
 // Caller indices of the rays sorted into pixel-compact bundles: the stable sort of their
@@ -544,5 +550,22 @@ TrainStepResult train_step(
   const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
   const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
   const DepthLossOptions & depth_loss, const RaySupervision & sup, const PatchLoss & patch);
+
+// ... with a trimmed colour loss (robust_loss.hpp; f2n_robust_weights has the rule).  After the
+// render, under no-grad, the render's own detached colours and the colour target the colour loss uses
+// (a gt + (1 - a) bg where the alpha target composites) give per-ray weights m_r omega_r, and those
+// stand wherever m_r stands in the call above: f2n::train_loss_sup and the opacity, distortion and
+// depth terms -- a rejected ray contributes exact zeros and regularises nothing.  The D-SSIM term
+// keeps the caller's patch_weight.  The body of the supervised step runs also when the caller gave
+// neither ray_weight nor alpha.  robust.patch is the P of the rule (0: scattered rays) and need not be
+// PatchLoss::patch.  TrainStepResult::robust_weight and robust_stats are filled; no host read.
+// quantile >= 1 is the call above, launch for launch and bit for bit -- the rule for
+// dist_loss_weight == 0.
+TrainStepResult train_step(
+  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
+  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
+  const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
+  const DepthLossOptions & depth_loss, const RaySupervision & sup, const PatchLoss & patch,
+  const RobustLoss & robust);
 
 }  // namespace f2n

@@ -1429,6 +1429,42 @@ int f2n_draw_patches(
   uint32_t seed_hi, int attempts, int32_t * cam, int32_t * ij, int32_t * tries,
   float * patch_weight, void * stream);
 
+/* ------------------------------------------------------------------ robust loss --------------- */
+
+/* Per-ray weights of a trimmed colour loss with patch-smoothed inlier masks (RobustNeRF, Sabour et
+ * al., CVPR 2023, section 3.2), beside f2n_loss_sup_fwd, whose ray_weight they become.  The reference
+ * has no such loss: src/main_functions/train_manager.cpp:78-96 averages over every ray of the batch.
+ *   colors, target [n_rays, 3] f32; ray_weight [n_rays] m_r, null = 1.
+ *   A ray is considered iff m_r != 0; one that is not gets weight +0 and omega 0, takes no part in any
+ *   count and its colours are not read.  eps_r = (d0 d0 + d1 d1) + d2 d2 in f32 with d = colors -
+ *   target, a non-finite eps becoming +inf.  N_c considered rays,
+ *     k = min(N_c, max(1, (int64)ceil((double)quantile N_c))),
+ *   T the k-th smallest eps among them, found exactly by radix selection on its bits (LDS histograms
+ *   of integer atomics).  w0_r = isfinite(eps_r) && eps_r <= T: every tie at T is an inlier.
+ *   P > 0: the rays are n_rays / P^2 patches of P x P pixels in the layout of f2n_draw_patches.
+ *     W_r: over the considered pixels of the 3 x 3 window clipped to the patch, cnt of them and s with
+ *       w0 = 1, W = cnt > 0 && (float)s >= box_thresh (float)cnt;
+ *     R_block: the patch tiled from its top-left corner into nbhd x nbhd blocks (edge blocks are what
+ *       is left), cnt considered pixels and s of them with W = 1, R = cnt > 0 && (float)s >=
+ *       nbhd_thresh (float)cnt;
+ *     omega_r = w0_r | W_r | R_block(r) for a considered ray.
+ *   P = 0: scattered rays, omega = w0.
+ *   weight_out [n_rays] = m_r where omega_r is set, else +0; omega_out [n_rays] u8 or null: omega
+ *   itself; stats4 = {T, N_c, sum w0, sum omega}, the counts integer sums converted at the end.
+ *   N_c == 0: T = 0 and every output is zero.
+ *   workspace: f2n_robust_workspace_words(n_rays) u32 words (0 for an invalid n_rays).
+ * One launch for P = 0, three for P > 0 (select, one workgroup per patch, the patches' counts); no
+ * workgroup waits on another, nothing is read on the host, no float atomics: the same bits on every
+ * run, and capturable in a hipGraph.  The arithmetic and its order are fixed in the header comment of
+ * robust_mask.hip.  Valid: 1 <= n_rays < 2^24; P == 0, or 3 <= P <= 64 with n_rays % P^2 == 0 and
+ * 1 <= nbhd <= P; quantile in (0, 1]; both thresholds in [0, 1] (NaN is invalid); colors, target,
+ * weight_out, stats4 and workspace not null.  Anything else: F2N_E_INVALID_ARG before any HIP work. */
+int64_t f2n_robust_workspace_words(int n_rays);
+int f2n_robust_weights(
+  const float * colors, const float * target, const float * ray_weight, int n_rays, int P, int nbhd,
+  float quantile, float box_thresh, float nbhd_thresh, float * weight_out, uint8_t * omega_out,
+  float * stats4, uint32_t * workspace, void * stream);
+
 /* ------------------------------------------------------------------ localiser ----------------- */
 
 /* The particle loop of Localizer::optimize_pose_by_random_search -- src/localizer.cpp:88-118 (per
