@@ -557,6 +557,51 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def("encode", &SHShader::encode)
     .def("named_parameters", [](SHShader & s) { return named_params(s); });
 
+  // ---- camera visibility (occ_visibility.hpp) ------------------------------------------------------
+  py::class_<f2n::VisibilityOptions>(m, "VisibilityOptions")
+    .def(
+      py::init([](int64_t resolution, int pixel_stride, int n_steps, float step, int min_views,
+                  int dilate) {
+        f2n::VisibilityOptions o;
+        o.resolution = resolution;
+        o.pixel_stride = pixel_stride;
+        o.n_steps = n_steps;
+        o.step = step;
+        o.min_views = min_views;
+        o.dilate = dilate;
+        return o;
+      }),
+      py::arg("resolution") = 128, py::arg("pixel_stride") = 1, py::arg("n_steps") = -1,
+      py::arg("step") = 1.0f / 256, py::arg("min_views") = 1, py::arg("dilate") = 1)
+    .def_readwrite("resolution", &f2n::VisibilityOptions::resolution)
+    .def_readwrite("pixel_stride", &f2n::VisibilityOptions::pixel_stride)
+    .def_readwrite("n_steps", &f2n::VisibilityOptions::n_steps)
+    .def_readwrite("step", &f2n::VisibilityOptions::step)
+    .def_readwrite("min_views", &f2n::VisibilityOptions::min_views)
+    .def_readwrite("dilate", &f2n::VisibilityOptions::dilate);
+  m.def(
+    "camera_view_counts",
+    [](const Tensor & poses, const Tensor & intr, int64_t h, int64_t w,
+       const f2n::VisibilityOptions & opts, const c10::optional<Tensor> & dist,
+       const f2n::PixelMask * mask) {
+      return f2n::camera_view_counts(poses, intr, h, w, opts, opt_tensor(dist), mask);
+    },
+    py::arg("poses"), py::arg("intrinsics"), py::arg("h"), py::arg("w"),
+    py::arg("opts") = f2n::VisibilityOptions(), py::arg("dist") = py::none(),
+    py::arg("mask") = py::none(),
+    "uint8 [G,G,G]: how many cameras see each cell (saturating at 255); poses are the normalised ones");
+  m.def(
+    "camera_visibility",
+    [](const Tensor & poses, const Tensor & intr, int64_t h, int64_t w,
+       const f2n::VisibilityOptions & opts, const c10::optional<Tensor> & dist,
+       const f2n::PixelMask * mask) {
+      return f2n::camera_visibility(poses, intr, h, w, opts, opt_tensor(dist), mask);
+    },
+    py::arg("poses"), py::arg("intrinsics"), py::arg("h"), py::arg("w"),
+    py::arg("opts") = f2n::VisibilityOptions(), py::arg("dist") = py::none(),
+    py::arg("mask") = py::none(),
+    "int32 [G^3/32] words of `view count >= min_views`: what OccupancyGrid.set_allowed takes");
+
   // ---- OccupancyGrid -----------------------------------------------------------------------------
   py::class_<OccupancyGrid, std::shared_ptr<OccupancyGrid>>(m, "OccupancyGrid")
     .def(
@@ -578,6 +623,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     .def("fraction", &OccupancyGrid::fraction)
     .def_property_readonly("resolution", &OccupancyGrid::resolution)
     .def_property_readonly("words", &OccupancyGrid::words)
+    .def(
+      "set_allowed", &OccupancyGrid::set_allowed, py::arg("words"),
+      "int32 [G^3/32] words (camera_visibility): no bit outside them is ever on while they are set")
+    .def("clear_allowed", &OccupancyGrid::clear_allowed)
+    .def(
+      "allowed",
+      [](const OccupancyGrid & g) {
+        return g.allowed().defined() ? c10::optional<Tensor>(g.allowed()) : c10::nullopt;
+      },
+      "the allowed words, or None")
+    .def(
+      "carve_to_cameras",
+      [](OccupancyGrid & g, const Tensor & poses, const Tensor & intr, int64_t h, int64_t w,
+         const f2n::VisibilityOptions & opts, const c10::optional<Tensor> & dist,
+         const f2n::PixelMask * mask) {
+        g.carve_to_cameras(poses, intr, h, w, opts, opt_tensor(dist), mask);
+      },
+      py::arg("poses"), py::arg("intrinsics"), py::arg("h"), py::arg("w"),
+      py::arg("opts") = f2n::VisibilityOptions(), py::arg("dist") = py::none(),
+      py::arg("mask") = py::none(),
+      "set_allowed(camera_visibility(...)) at the grid's own resolution")
     .def_property_readonly_static(
       "DEFAULT_THRESHOLD", [](py::object) { return OccupancyGrid::kDefaultThreshold; })
     .def_property_readonly_static(

@@ -33,6 +33,7 @@ void OccupancyGrid::update(Hash3DAnchored & field, float threshold, float decay,
       reinterpret_cast<uint32_t *>(words_.data_ptr<int32_t>()), (int)G_, g.L_walk, g.F, g.T,
       g.level_stride, 3.f, threshold, decay, f2n::current_stream(words_)),
     "f2n_occ_update");
+  if (allowed_.defined()) words_.bitwise_and_(allowed_);
 }
 
 void OccupancyGrid::set_bits(const Tensor & occupied)
@@ -49,6 +50,25 @@ void OccupancyGrid::set_bits(const Tensor & occupied)
       .sum(1);
   packed = torch::where(packed >= (int64_t(1) << 31), packed - (int64_t(1) << 32), packed);
   words_.copy_(packed.to(torch::kInt32));
+  if (allowed_.defined()) words_.bitwise_and_(allowed_);
+}
+
+void OccupancyGrid::set_allowed(const Tensor & words)
+{
+  torch::NoGradGuard no_grad;
+  TORCH_CHECK(
+    words.defined() && words.scalar_type() == torch::kInt32 && words.numel() == words_.numel(),
+    "OccupancyGrid::set_allowed: int32 [G^3 / 32] words");
+  allowed_ = words.detach().to(words_.device()).reshape({words_.numel()}).clone();
+  words_.bitwise_and_(allowed_);
+}
+
+void OccupancyGrid::carve_to_cameras(
+  const Tensor & poses, const Tensor & intrinsics, int64_t h, int64_t w,
+  f2n::VisibilityOptions opts, const Tensor & dist, const f2n::PixelMask * mask)
+{
+  opts.resolution = G_;
+  set_allowed(f2n::camera_visibility(poses, intrinsics, h, w, opts, dist, mask));
 }
 
 Tensor OccupancyGrid::bits() const

@@ -10,9 +10,16 @@
 // grid is the render without one with the density of every sample in an unoccupied cell set to
 // exactly zero, and those samples dropped.  A fresh grid is all ones: nothing is skipped until the
 // first update().
+//
+// The allowed mask (set_allowed / carve_to_cameras): a set of cells, usually the ones the training
+// cameras can sample (occ_visibility.hpp), outside which no bit is ever on.  While it is set,
+// words_ &= allowed_ at once, after every update() and after every set_bits(): one in-place ATen op, no
+// host read.  density() is untouched, so clear_allowed() and an update() restore the plain grid.  Like
+// the grid itself the mask is not a parameter or buffer: it is rebuilt from the cameras after loading.
 #pragma once
 
 #include "hash_3d_anchored.hpp"
+#include "occ_visibility.hpp"
 
 class OccupancyGrid
 {
@@ -38,10 +45,21 @@ public:
     const Tensor & probe = Tensor());
 
   void set_bits(const Tensor & occupied);  // bool [G,G,G], indexed [cz][cy][cx]
-  Tensor bits() const;                     // bool [G,G,G]
+  Tensor bits() const;                     // bool [G,G,G]: the effective bits (inside the allowed mask)
   Tensor density() const { return density_.view({G_, G_, G_}); }
   Tensor occupied(const Tensor & points) const;  // raw points [n,3] -> bool [n]
   double fraction() const;                       // occupied cells / all cells (a host read)
+
+  // words: int32 [G^3/32] as camera_visibility returns them (copied).  Without a mask update() and
+  // set_bits() make exactly the launches they make without this feature.
+  void set_allowed(const Tensor & words);
+  void clear_allowed() { allowed_ = Tensor(); }
+  const Tensor & allowed() const { return allowed_; }  // undefined = no mask
+  // set_allowed(camera_visibility(...)) at the grid's own resolution (opts.resolution is ignored)
+  void carve_to_cameras(
+    const Tensor & poses, const Tensor & intrinsics, int64_t h, int64_t w,
+    f2n::VisibilityOptions opts = {}, const Tensor & dist = {},
+    const f2n::PixelMask * mask = nullptr);
 
   int64_t resolution() const { return G_; }
   const Tensor & words() const { return words_; }  // int32 [G^3/32]: the bitfield as the kernels read it
@@ -54,4 +72,5 @@ private:
   int64_t G_;
   Tensor words_;    // int32 [G^3 / 32]
   Tensor density_;  // float [G^3]
+  Tensor allowed_;  // int32 [G^3 / 32], undefined = no mask
 };

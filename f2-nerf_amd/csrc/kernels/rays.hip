@@ -64,10 +64,9 @@ __global__ __launch_bounds__(F2N_BLOCK) void gen_rays_dist_kernel(
   const float * P = poses + cam * pose_ld;  // rows of 4: [R | t]
   float u, v;
   camera_pixel_to_dir(intrinsics + cam * 9, load_lens(dist, cam), row, col, u, v);
-  const float w = -1.f;
 #pragma unroll
   for (int a = 0; a < 3; a++) {
-    rays_d[3 * r + a] = fmaf(P[4 * a + 2], w, fmaf(P[4 * a + 1], v, P[4 * a] * u));
+    rays_d[3 * r + a] = camera_dir_to_world(P, a, u, v);
     rays_o[3 * r + a] = P[4 * a + 3];
   }
 }

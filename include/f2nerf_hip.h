@@ -845,6 +845,48 @@ int f2n_sample_compact_occ(
   const int32_t * len, const uint32_t * bits, int G, float * pts, float * dirs, float * dt,
   float * t, int n_rays, int S, float step, void * stream);
 
+/* The cells the training cameras can sample (no reference counterpart).  "Camera c marks cell i":
+ * there is a walked pixel (row, col) of c and a k in [0, n_steps) such that VALIDATE sample k of that
+ * pixel's ray -- the direction of f2n_gen_rays_dist (src/rays.cpp:7-28: pixel centre at +0.5; the
+ * Newton steps when the camera's row of dist is non-zero, the pinhole expression when it is zero or
+ * dist is NULL), origin = the pose's translation, f2n_sample_rays' walk (src/points_sampler.cpp:31-48)
+ * with all-ones noise, S = n_steps and the given step -- contracts (src/hash_3d_anchored.cpp:79-82)
+ * into cell i (the cell expression above).  The kernel calls the device functions
+ * those entries call: the same bits.  A sample with a non-finite contracted coordinate marks nothing.
+ * Walked pixels at pixel_stride s >= 1: rows min(a*s, h-1) for a = 0 .. ceil((h-1)/s), columns
+ * likewise, so the last row and the last column are always walked; with mask_bits (f2n_mask_pack's
+ * layout: global pixel g = (cam*h + row)*w + col, cam the camera's ABSOLUTE row in the tables) a
+ * pixel whose bit is 0 is skipped.
+ *   poses [*, pose_ld] (pose_ld 12 or 16), intrinsics [*, 9], dist [*, 4] or NULL: the tables of
+ *   f2n_gen_rays_dist; cameras cam_first .. cam_first + n_cams - 1 are walked
+ *   bits [G^3/32]: ORed into, never cleared
+ * One wavefront per ray in 64-sample strides (f2n_density_march_occ without the field), a
+ * persistent grid-stride loop over the rays; integer atomic OR only, issued where the bit read as 0
+ * and by the first lane of a run of equal cells: the result does not depend on the order of arrival.
+ * A null table or bits, a G the grid does not accept, pose_ld not 12 or 16, h, w, pixel_stride or
+ * n_steps < 1, n_steps > 65536, cam_first < 0, n_cams < 0, step not positive and finite:
+ * F2N_E_INVALID_ARG before any HIP work; then n_cams == 0: F2N_OK, nothing written.  No allocation,
+ * no synchronisation, no host read: capturable in a graph, like the three entries below. */
+int f2n_occ_mark_rays(
+  const float * poses, int pose_ld, const float * intrinsics, const float * dist, int cam_first,
+  int n_cams, int h, int w, int pixel_stride, const uint32_t * mask_bits, int n_steps, float step,
+  uint32_t * bits, int G, void * stream);
+
+/* out bit (x, y, z) = OR of in over |dx|, |dy|, |dz| <= 1 inside [0, G)^3: no wrap-around.  A TRAIN
+ * sample (src/points_sampler.cpp:31-36: jitter in [0.5, 1.5) steps) lies within half a step of a
+ * VALIDATE sample of its ray; while that is at most a cell, one pass covers it.  One thread per cell,
+ * no atomics.  in == out, a null or a bad G: F2N_E_INVALID_ARG. */
+int f2n_occ_dilate(const uint32_t * in, uint32_t * out, int G, void * stream);
+
+/* Views per cell: count [G^3] u8, count[i] = min(255, count[i] + bit i), called once per camera with
+ * that camera's (dilated) marks. */
+int f2n_occ_count_add(const uint32_t * bits, uint8_t * count, int G, void * stream);
+
+/* bit i = count[i] >= min_count; bits [G^3/32] overwritten: the grid the march reads
+ * (src/renderer.cpp:58-90 with f2n_density_march_occ) once ANDed into an occupancy bitfield. */
+int f2n_occ_count_bits(
+  const uint8_t * count, int min_count, uint32_t * bits, int G, void * stream);
+
 /* ------------------------------------------------------------------ ray order --------------- */
 
 /* Bucketing of a ray batch for the gather locality of f2n_hash_fwd_raytile (no reference
