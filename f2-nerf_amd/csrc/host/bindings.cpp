@@ -78,6 +78,21 @@ c10::optional<Tensor> tensor_or_none(const Tensor & t)
   return t.defined() ? c10::optional<Tensor>(t) : c10::nullopt;
 }
 
+// What every Renderer.train_step* entry does with its arguments: one f2n::train_step, the GIL
+// released (loss.backward() runs the autograd engine, which must not be entered holding it).
+f2n::TrainStepResult run_train_step(
+  Renderer & r, const Tensor & o, const Tensor & d, const Tensor & emb_idx, const Tensor & gt,
+  float var_loss_weight, const c10::optional<Tensor> & noise, const c10::optional<Tensor> & bg,
+  bool backward, float dist_loss_weight, const c10::optional<Tensor> & depth_target,
+  const f2n::DepthLossOptions & depth_loss, const f2n::RaySupervision & sup = {},
+  const f2n::PatchLoss & patch = {}, const f2n::RobustLoss & robust = {})
+{
+  const f2n::LossTerms terms{
+    var_loss_weight, dist_loss_weight, opt_tensor(depth_target), depth_loss, sup, patch, robust};
+  py::gil_scoped_release no_gil;
+  return f2n::train_step(r, o, d, emb_idx, gt, terms, opt_tensor(noise), opt_tensor(bg), backward);
+}
+
 struct AdamHandle
 {
   std::shared_ptr<torch::optim::Optimizer> opt;
@@ -773,17 +788,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
          const std::string & mode, const c10::optional<Tensor> & noise,
          const c10::optional<Tensor> & bg, bool want_dist,
          const c10::optional<Tensor> & depth_target, float depth_eps) -> py::tuple {
+        const LossOutputs want{want_dist, opt_tensor(depth_target), depth_eps};
         RenderResult res;
         {
           py::gil_scoped_release no_gil;
-          // (no target: the overload that exists without it, not the new one with an undefined tensor)
-          res = depth_target.has_value()
-                  ? r.render_for_loss(
-                      o, d, opt_tensor(emb_idx), parse_mode(mode), opt_tensor(noise), opt_tensor(bg),
-                      want_dist, *depth_target, depth_eps)
-                  : r.render_for_loss(
-                      o, d, opt_tensor(emb_idx), parse_mode(mode), opt_tensor(noise), opt_tensor(bg),
-                      want_dist);
+          res = r.render_for_loss(
+            o, d, opt_tensor(emb_idx), parse_mode(mode), opt_tensor(noise), opt_tensor(bg), want);
         }
         if (depth_target.has_value())
           return py::make_tuple(
@@ -810,18 +820,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
          const std::string & mode, const c10::optional<Tensor> & noise,
          const c10::optional<Tensor> & bg, bool want_dist,
          const c10::optional<Tensor> & depth_target, float depth_eps, bool want_opacity) {
+        const LossOutputs want{want_dist, opt_tensor(depth_target), depth_eps, want_opacity};
         py::gil_scoped_release no_gil;
-        if (want_opacity)
-          return r.render_for_loss(
-            o, d, opt_tensor(emb_idx), parse_mode(mode), opt_tensor(noise), opt_tensor(bg), want_dist,
-            opt_tensor(depth_target), depth_eps, true);
-        return depth_target.has_value()
-                 ? r.render_for_loss(
-                     o, d, opt_tensor(emb_idx), parse_mode(mode), opt_tensor(noise), opt_tensor(bg),
-                     want_dist, *depth_target, depth_eps)
-                 : r.render_for_loss(
-                     o, d, opt_tensor(emb_idx), parse_mode(mode), opt_tensor(noise), opt_tensor(bg),
-                     want_dist);
+        return r.render_for_loss(
+          o, d, opt_tensor(emb_idx), parse_mode(mode), opt_tensor(noise), opt_tensor(bg), want);
       },
       py::arg("rays_o"), py::arg("rays_d"), py::arg("emb_idx") = py::none(),
       py::arg("mode") = "train", py::arg("noise") = py::none(), py::arg("bg_color") = py::none(),
@@ -886,14 +888,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
          float var_loss_weight, const c10::optional<Tensor> & noise,
          const c10::optional<Tensor> & bg, bool backward, float dist_loss_weight,
          const c10::optional<Tensor> & depth_target, const f2n::DepthLossOptions & depth_loss) {
-        f2n::TrainStepResult out;
-        {
-          // loss.backward() runs the autograd engine, which must not be entered holding the GIL
-          py::gil_scoped_release no_gil;
-          out = f2n::train_step(
-            r, o, d, emb_idx, gt, var_loss_weight, dist_loss_weight, opt_tensor(noise),
-            opt_tensor(bg), backward, opt_tensor(depth_target), depth_loss);
-        }
+        const f2n::TrainStepResult out = run_train_step(
+          r, o, d, emb_idx, gt, var_loss_weight, noise, bg, backward, dist_loss_weight, depth_target,
+          depth_loss);
         return py::make_tuple(out.loss, out.sq_err_sum, out.n_values, out.n_samples);
       },
       py::arg("rays_o"), py::arg("rays_d"), py::arg("emb_idx"), py::arg("gt_colors"),
@@ -911,13 +908,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
          const c10::optional<Tensor> & noise, const c10::optional<Tensor> & bg, bool backward,
          float dist_loss_weight, const c10::optional<Tensor> & depth_target,
          const f2n::DepthLossOptions & depth_loss) {
-        f2n::TrainStepResult out;
-        {
-          py::gil_scoped_release no_gil;
-          out = f2n::train_step(
-            r, o, d, emb_idx, gt, var_loss_weight, dist_loss_weight, opt_tensor(noise),
-            opt_tensor(bg), backward, opt_tensor(depth_target), depth_loss, sup);
-        }
+        const f2n::TrainStepResult out = run_train_step(
+          r, o, d, emb_idx, gt, var_loss_weight, noise, bg, backward, dist_loss_weight, depth_target,
+          depth_loss, sup);
         if (sup.want_colors)
           return py::make_tuple(
             out.loss, out.sq_err_sum, out.n_values, out.n_samples, tensor_or_none(out.weight_sum),
@@ -942,13 +935,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
          const c10::optional<Tensor> & noise, const c10::optional<Tensor> & bg, bool backward,
          float dist_loss_weight, const c10::optional<Tensor> & depth_target,
          const f2n::DepthLossOptions & depth_loss) {
-        f2n::TrainStepResult out;
-        {
-          py::gil_scoped_release no_gil;
-          out = f2n::train_step(
-            r, o, d, emb_idx, gt, var_loss_weight, dist_loss_weight, opt_tensor(noise),
-            opt_tensor(bg), backward, opt_tensor(depth_target), depth_loss, sup, patch);
-        }
+        const f2n::TrainStepResult out = run_train_step(
+          r, o, d, emb_idx, gt, var_loss_weight, noise, bg, backward, dist_loss_weight, depth_target,
+          depth_loss, sup, patch);
         return py::make_tuple(
           out.loss, out.sq_err_sum, out.n_values, out.n_samples, tensor_or_none(out.weight_sum),
           tensor_or_none(out.colors));
@@ -970,13 +959,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
          const c10::optional<Tensor> & noise, const c10::optional<Tensor> & bg, bool backward,
          float dist_loss_weight, const c10::optional<Tensor> & depth_target,
          const f2n::DepthLossOptions & depth_loss) {
-        f2n::TrainStepResult out;
-        {
-          py::gil_scoped_release no_gil;
-          out = f2n::train_step(
-            r, o, d, emb_idx, gt, var_loss_weight, dist_loss_weight, opt_tensor(noise),
-            opt_tensor(bg), backward, opt_tensor(depth_target), depth_loss, sup, patch, robust);
-        }
+        const f2n::TrainStepResult out = run_train_step(
+          r, o, d, emb_idx, gt, var_loss_weight, noise, bg, backward, dist_loss_weight, depth_target,
+          depth_loss, sup, patch, robust);
         return py::make_tuple(
           out.loss, out.sq_err_sum, out.n_values, out.n_samples, tensor_or_none(out.weight_sum),
           tensor_or_none(out.colors), tensor_or_none(out.robust_weight),

@@ -17,9 +17,9 @@
 //
 //   auto env = std::make_shared<f2n::EnvMap>(128, device);
 //   renderer.set_background(env);
-//   f2n::RaySupervision sup;  sup.alpha = alpha;  sup.opacity_weight = 1e-2f;
-//   sup.composite_target = false;                 // the colour target is the image, sky included
-//   f2n::train_step(renderer, o, d, cam, gt, ..., /*bg_color=*/Tensor(), true, ..., sup);
+//   f2n::LossTerms terms;  terms.sup.alpha = alpha;  terms.sup.opacity_weight = 1e-2f;
+//   terms.sup.composite_target = false;           // the colour target is the image, sky included
+//   f2n::train_step(renderer, o, d, cam, gt, terms, noise);   // bg_color left undefined
 //   field_adam.step();  sky_adam.step();          // sky_adam over env->optim_param_groups(lr)
 #pragma once
 

@@ -17,7 +17,7 @@
 //
 //   renderer.options_.fused_ray_grad = true;
 //   auto [rays, gt, cam] = calib.sample_random_rays(pose_refiner.poses(), h, w, n, images);
-//   f2n::train_step(renderer, rays.origins, rays.dirs, cam, gt, ...);
+//   f2n::train_step(renderer, rays.origins, rays.dirs, cam, gt, terms);   // a f2n::LossTerms
 //   field_adam.step();  pose_adam.step();  calib_adam.step();
 #pragma once
 

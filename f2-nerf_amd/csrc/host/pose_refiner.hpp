@@ -15,7 +15,7 @@
 //
 //   renderer.options_.fused_ray_grad = true;
 //   auto [rays, gt, cam] = refiner.sample_random_rays(intrinsics, h, w, n, images);
-//   f2n::train_step(renderer, rays.origins, rays.dirs, cam, gt, ...);
+//   f2n::train_step(renderer, rays.origins, rays.dirs, cam, gt, terms);   // a f2n::LossTerms
 //   field_adam.step();  pose_adam.step();   // pose_adam over refiner.optim_param_groups(lr)
 #pragma once
 

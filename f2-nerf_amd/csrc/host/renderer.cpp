@@ -312,51 +312,25 @@ RenderResult Renderer::render(
   const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
   const Tensor & noise_in, const Tensor & bg_in)
 {
-  return render_routed(rays_o, rays_d, emb_idx, mode, noise_in, bg_in, false, false);
+  return render_routed(rays_o, rays_d, emb_idx, mode, noise_in, bg_in, false, LossOutputs());
 }
 
 RenderResult Renderer::render_for_loss(
   const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-  const Tensor & noise_in, const Tensor & bg_in)
+  const Tensor & noise_in, const Tensor & bg_in, const LossOutputs & want)
 {
-  return render_routed(rays_o, rays_d, emb_idx, mode, noise_in, bg_in, true, false);
-}
-
-RenderResult Renderer::render_for_loss(
-  const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-  const Tensor & noise_in, const Tensor & bg_in, bool want_dist)
-{
-  return render_routed(rays_o, rays_d, emb_idx, mode, noise_in, bg_in, true, want_dist);
-}
-
-RenderResult Renderer::render_for_loss(
-  const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-  const Tensor & noise_in, const Tensor & bg_in, bool want_dist, const Tensor & depth_target,
-  float depth_eps)
-{
-  return render_routed(
-    rays_o, rays_d, emb_idx, mode, noise_in, bg_in, true, want_dist, depth_target, depth_eps);
-}
-
-RenderResult Renderer::render_for_loss(
-  const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-  const Tensor & noise_in, const Tensor & bg_in, bool want_dist, const Tensor & depth_target,
-  float depth_eps, bool want_opacity)
-{
-  return render_routed(
-    rays_o, rays_d, emb_idx, mode, noise_in, bg_in, true, want_dist, depth_target, depth_eps,
-    want_opacity);
+  return render_routed(rays_o, rays_d, emb_idx, mode, noise_in, bg_in, true, want);
 }
 
 RenderResult Renderer::render_routed(
   const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-  const Tensor & noise_in, const Tensor & bg_in, bool for_loss, bool want_dist,
-  const Tensor & depth_target, float depth_eps, bool want_opacity)
+  const Tensor & noise_in, const Tensor & bg_in, bool for_loss, const LossOutputs & want)
 {
   const int64_t n_rays = rays_o.size(0);
-  if (depth_target.defined()) {
-    TORCH_CHECK(depth_target.numel() == n_rays, "depth_target must be [n_rays]");
-    TORCH_CHECK(std::isfinite(depth_eps) && depth_eps >= 0.f, "depth_eps must be finite and >= 0");
+  if (want.depth_target.defined()) {
+    TORCH_CHECK(want.depth_target.numel() == n_rays, "depth_target must be [n_rays]");
+    TORCH_CHECK(
+      std::isfinite(want.depth_eps) && want.depth_eps >= 0.f, "depth_eps must be finite and >= 0");
   }
   const auto fopt = f2n::float_on(rays_o.device());
   // the uniform draw first, as ever (the generator stream does not depend on the route); the lean
@@ -368,21 +342,19 @@ RenderResult Renderer::render_routed(
     record_kept(0);
     RenderResult none{
       bg_color, torch::zeros({n_rays}, fopt), torch::full({n_rays}, 512.f, fopt), Tensor()};
-    if (want_dist) none.weight_dist = torch::zeros({n_rays}, fopt);
-    if (depth_target.defined()) none.depth_terms = torch::zeros({n_rays, 3}, fopt);
+    if (want.dist) none.weight_dist = torch::zeros({n_rays}, fopt);
+    if (want.depth_target.defined()) none.depth_terms = torch::zeros({n_rays, 3}, fopt);
     if (options_.normals) none.normals = torch::zeros({n_rays, 3}, fopt);
-    if (want_opacity) none.opacity = torch::zeros({n_rays}, fopt);
+    if (want.opacity) none.opacity = torch::zeros({n_rays}, fopt);
     return none;
   }
   Route route = choose_route(rays_o, rays_d, bg_color);
   route.noise_raw = route.lean && raw.defined();
   route.want_var = route.lean && route.bucketed && for_loss;
-  route.want_dist = want_dist;
-  route.want_opacity = want_opacity;
-  if (depth_target.defined()) {
-    route.depth_target = f2n::dev_f32(depth_target.detach(), "depth_target").reshape({n_rays});
-    route.depth_eps = depth_eps;
-  }
+  route.want = want;
+  if (want.depth_target.defined())
+    route.want.depth_target =
+      f2n::dev_f32(want.depth_target.detach(), "depth_target").reshape({n_rays});
   const Tensor noise = noise_in.defined() ? noise_in
                        : route.noise_raw  ? raw
                                           : PtsSampler::cook_noise(raw);
@@ -505,13 +477,24 @@ RenderResult Renderer::render_op_by_op(
                   last_trans.unsqueeze(-1) * bg_color;
   Tensor depths = FlexOps::Sum(weights * sampled_t, idx) / (1.f - last_trans + 1e-4f);
   RenderResult res{colors, depths, weights, idx};
-  if (route.want_dist) res.weight_dist = CustomOps::WeightDist(weights, kept.t, kept.dt, idx);
-  if (route.depth_target.defined())
-    res.depth_terms =
-      CustomOps::DepthSight(weights, kept.t, kept.dt, idx, route.depth_target, route.depth_eps);
+  per_ray_terms(res, weights, kept, route);
   if (options_.normals) res.normals = ray_normals(kept, weights);
-  if (route.want_opacity) res.opacity = FlexOps::Sum(weights, idx);
   return res;
+}
+
+// Where the kept samples' weights, t and dt lie side by side -- on every route, thinned by an
+// occupancy grid or not; t and dt get no gradient.  The opacity of a ray is the plain sum of its kept
+// samples' weights: the segment sum the op-by-op route composites with.
+void Renderer::per_ray_terms(
+  RenderResult & res, const Tensor & weights, const SampleResultFlex & kept, const Route & route)
+{
+  const Tensor & idx = kept.pts_idx_bounds;
+  const LossOutputs & want = route.want;
+  if (want.dist) res.weight_dist = CustomOps::WeightDist(weights, kept.t, kept.dt, idx);
+  if (want.depth_target.defined())
+    res.depth_terms =
+      CustomOps::DepthSight(weights, kept.t, kept.dt, idx, want.depth_target, want.depth_eps);
+  if (want.opacity) res.opacity = FlexOps::Sum(weights, idx);
 }
 
 // ---- fused routes --------------------------------------------------------------------------------
@@ -610,11 +593,11 @@ RenderResult Renderer::render_dense_bucketed(
     "f2n_ray_permute");
   // a depth target travels with its ray: bucketed ray j is the caller's ray perm[j]
   Route route_p = route;
-  if (route.depth_target.defined()) {
-    route_p.depth_target = torch::empty_like(route.depth_target);
+  if (route.want.depth_target.defined()) {
+    route_p.want.depth_target = torch::empty_like(route.want.depth_target);
     f2n::check(
       f2n_gather_rows(
-        route.depth_target.data_ptr<float>(), route_p.depth_target.data_ptr<float>(),
+        route.want.depth_target.data_ptr<float>(), route_p.want.depth_target.data_ptr<float>(),
         perm.data_ptr<int32_t>(), n_rays, 1, stream),
       "f2n_gather_rows");
   }
@@ -637,7 +620,7 @@ RenderResult Renderer::render_dense_bucketed(
   }
   // the distortion loss was taken in composite(), where the weights, t and dt of the bucketed order
   // lie: one float per ray rides back (nothing, when it was not asked for)
-  const Tensor dist = route.want_dist ? r.weight_dist : torch::empty({0}, rays_o.options());
+  const Tensor dist = route.want.dist ? r.weight_dist : torch::empty({0}, rays_o.options());
   // ... and so do the depth terms, three floats per ray, through a node of their own: without a
   // target nothing here is launched or recorded
   const Tensor terms =
@@ -654,14 +637,14 @@ RenderResult Renderer::render_dense_bucketed(
     auto out = RayUnpermuteFn::apply(
       r.colors, r.depths, var, dist, perm, inv, r.idx_start_end, bounds, /*S=*/1, /*rows=*/true);
     RenderResult res{
-      out[0], out[1], Tensor(), bounds, out[2], route.want_dist ? out[3] : Tensor(), terms};
+      out[0], out[1], Tensor(), bounds, out[2], route.want.dist ? out[3] : Tensor(), terms};
     res.opacity = opacity;
     return res;
   }
   auto out = RayUnpermuteFn::apply(
     r.colors, r.depths, r.weights, dist, perm, inv, r.idx_start_end, bounds, S, rows);
   RenderResult res{
-    out[0], out[1], out[2], bounds, Tensor(), route.want_dist ? out[3] : Tensor(), terms};
+    out[0], out[1], out[2], bounds, Tensor(), route.want.dist ? out[3] : Tensor(), terms};
   res.opacity = opacity;
   return res;
 }
@@ -941,17 +924,8 @@ RenderResult Renderer::composite(
   f2n::CompositeOut out = f2n::composite(
     shaded.field_out, shaded.rgb, kept.dt, kept.t, kept.pts_idx_bounds, bg_color, route.fused_net);
   RenderResult res{out.colors, out.depths, out.weights, kept.pts_idx_bounds};
-  // (here the kept samples' weights, t and dt lie side by side on every fused route, thinned by an
-  // occupancy grid or not; t and dt get no gradient)
-  if (route.want_dist)
-    res.weight_dist = CustomOps::WeightDist(out.weights, kept.t, kept.dt, kept.pts_idx_bounds);
-  if (route.depth_target.defined())
-    res.depth_terms = CustomOps::DepthSight(
-      out.weights, kept.t, kept.dt, kept.pts_idx_bounds, route.depth_target, route.depth_eps);
+  per_ray_terms(res, out.weights, kept, route);
   if (options_.normals && final) res.normals = ray_normals(kept, out.weights);
-  // (the opacity of a ray is the plain sum of its kept samples' weights: the segment sum the
-  // op-by-op route composites with)
-  if (route.want_opacity) res.opacity = FlexOps::Sum(out.weights, kept.pts_idx_bounds);
   return res;
 }
 
@@ -1297,143 +1271,25 @@ static Tensor add_patch_term(
   return loss + pl.ssim_weight * term;
 }
 
-static f2n::TrainStepResult train_step_plain(
-  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
-  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
-  const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
-  const f2n::DepthLossOptions & depth_loss, bool want_colors,
-  const f2n::PatchLoss * patch = nullptr);
-
 f2n::TrainStepResult f2n::train_step(
   Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
-  const Tensor & gt_colors, float var_loss_weight, const Tensor & noise, const Tensor & bg_color,
+  const Tensor & gt_colors, const LossTerms & terms, const Tensor & noise, const Tensor & bg_color,
   bool run_backward)
 {
-  return train_step(
-    renderer, rays_o, rays_d, emb_idx, gt_colors, var_loss_weight, 0.f, noise, bg_color,
-    run_backward);
-}
-
-f2n::TrainStepResult f2n::train_step(
-  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
-  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
-  const Tensor & bg_color, bool run_backward)
-{
-  return train_step(
-    renderer, rays_o, rays_d, emb_idx, gt_colors, var_loss_weight, dist_loss_weight, noise, bg_color,
-    run_backward, Tensor(), DepthLossOptions());
-}
-
-f2n::TrainStepResult f2n::train_step(
-  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
-  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
-  const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
-  const DepthLossOptions & depth_loss)
-{
-  return train_step_plain(
-    renderer, rays_o, rays_d, emb_idx, gt_colors, var_loss_weight, dist_loss_weight, noise, bg_color,
-    run_backward, depth_target, depth_loss, false);
-}
-
-// the step without per-ray supervision; want_colors only keeps a detached handle of the colours
-static f2n::TrainStepResult train_step_plain(
-  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
-  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
-  const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
-  const f2n::DepthLossOptions & depth_loss, bool want_colors, const f2n::PatchLoss * patch)
-{
-  using namespace f2n;
-  // (a zero distortion weight: the term is not computed and the call is the one without it)
-  const bool want_dist = dist_loss_weight != 0.f;
-  // (the same rule for the depth terms: no target, or three zero weights, and nothing of them exists)
-  const bool want_depth = depth_target.defined() && (depth_loss.empty != 0.f ||
-                                                      depth_loss.near != 0.f ||
-                                                      depth_loss.expected != 0.f);
-  // The per-batch constants of the term -- n_valid, counted on the device, and lambda_i / n_valid --
-  // are enqueued BEFORE the render, where the host runs ahead of the GPU: the dense route reads one
-  // flag back per chunk, and small launches made between that read and the backward are on the
-  // critical path.  One column sum, one dot product and one addition remain after it.
-  Tensor depth_n_valid, depth_coef;
-  if (want_depth) {
-    torch::NoGradGuard no_grad;
-    const Tensor z = f2n::dev_f32(depth_target.detach(), "depth_target").reshape({-1});
-    depth_n_valid = z.gt(0.f)
-                      .logical_and(z.lt(std::numeric_limits<float>::infinity()))
-                      .sum()
-                      .to(torch::kFloat32)
-                      .clamp_min(1.f);
-    Tensor lambda = torch::empty({3}, z.options());  // (filled by launches: nothing is copied over)
-    lambda.select(0, 0).fill_(depth_loss.empty);
-    lambda.select(0, 1).fill_(depth_loss.near);
-    lambda.select(0, 2).fill_(depth_loss.expected);
-    depth_coef = lambda / depth_n_valid;
-  }
-  RenderResult res = want_depth
-                       ? renderer.render_for_loss(
-                           rays_o, rays_d, emb_idx, RunningMode::TRAIN, noise, bg_color, want_dist,
-                           depth_target, depth_loss.eps)
-                       : renderer.render_for_loss(
-                           rays_o, rays_d, emb_idx, RunningMode::TRAIN, noise, bg_color, want_dist);
-  // colour loss + variance loss + squared error in two launches (f2n_loss_fwd; the ATen spelling of
-  // the reference, train_manager.cpp:78-96, is ~23 launches of a few microseconds each)
-  Tensor var = res.weight_var.defined() ? res.weight_var
-                                        : CustomOps::WeightVar(res.weights, res.idx_start_end);
-  // (a zero weight -- the reference's schedule starts there, train_manager.cpp:85-91 -- makes the
-  // variance term's gradient exactly zero: its backward kernel is not run at all)
-  if (var_loss_weight == 0.f) var = var.detach();
-  Tensor stats = f2n::train_loss(res.colors, gt_colors, var, var_loss_weight);  // {loss, c, v, sq}
-  Tensor loss = stats[0];
-  renderer.last_dist_loss_ = Tensor();
-  if (want_dist && res.weight_dist.numel() > 0) {
-    Tensor dist_loss = res.weight_dist.mean();
-    loss = loss + dist_loss_weight * dist_loss;
-    renderer.last_dist_loss_ = dist_loss.detach();
-  }
-  renderer.last_depth_loss_ = Tensor();
-  if (want_depth && res.depth_terms.numel() > 0) {
-    // invalid rays hold exact zeros: the sum over all rays is the sum over the valid ones
-    const Tensor sums = res.depth_terms.sum(0);  // [3]
-    loss = loss + torch::dot(sums, depth_coef);
-    renderer.last_depth_loss_ = sums.detach() / depth_n_valid;
-  }
-  renderer.last_opacity_loss_ = Tensor();
-  renderer.last_ssim_loss_ = Tensor();
-  if (patch) loss = add_patch_term(renderer, loss, res.colors, gt_colors, *patch);
-  TrainStepResult out;
-  out.loss = loss.detach();
-  out.sq_err_sum = stats[3].detach();
-  out.n_values = res.colors.numel();
-  out.n_samples = renderer.last_n_samples_;
-  if (want_colors) out.colors = res.colors.detach();
-  if (run_backward && loss.requires_grad()) loss.backward();
-  return out;
-}
-
-static f2n::TrainStepResult train_step_sup(
-  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
-  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
-  const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
-  const f2n::DepthLossOptions & depth_loss, const f2n::RaySupervision & sup,
-  const f2n::PatchLoss * patch, const f2n::RobustLoss * robust = nullptr)
-{
-  using namespace f2n;
-  // (no supervision: the call without it, launch for launch; a robust loss makes per-ray weights of
-  // its own, so it takes the body below also when the caller gave none)
-  if (!robust && !sup.ray_weight.defined() && !sup.alpha.defined())
-    return train_step_plain(
-      renderer, rays_o, rays_d, emb_idx, gt_colors, var_loss_weight, dist_loss_weight, noise,
-      bg_color, run_backward, depth_target, depth_loss, sup.want_colors, patch);
+  const RaySupervision & sup = terms.sup;
   const int64_t n_rays = rays_o.size(0);
+  // (a term that is off -- a zero weight, no target, quantile >= 1 -- is neither computed nor
+  // differentiated: the step is the one without it, launch for launch)
+  const bool want_dist = terms.want_dist(), want_depth = terms.want_depth();
+  const bool want_opacity = sup.want_opacity(), want_robust = terms.robust.active();
+  // per-ray weights (the caller's, or the robust loss's own): f2n::train_loss_sup and `* m` below;
+  // none: f2n::train_loss, and no multiply is issued
+  const bool weighted = terms.weighted();
   // composite_target off: the colour target is gt itself and alpha feeds the opacity term alone
   const bool plain_target = sup.alpha.defined() && !sup.composite_target;
   TORCH_CHECK(
     !sup.alpha.defined() || plain_target || bg_color.defined(),
     "train_step: an alpha target needs the bg_color the render blends in");
-  const bool want_dist = dist_loss_weight != 0.f;
-  const bool want_depth = depth_target.defined() && (depth_loss.empty != 0.f ||
-                                                      depth_loss.near != 0.f ||
-                                                      depth_loss.expected != 0.f);
-  const bool want_opacity = sup.alpha.defined() && sup.opacity_weight != 0.f;
   Tensor m, alpha;
   if (sup.ray_weight.defined()) {
     m = f2n::dev_f32(sup.ray_weight.detach(), "ray_weight").reshape({-1});
@@ -1443,25 +1299,32 @@ static f2n::TrainStepResult train_step_sup(
     alpha = f2n::dev_f32(sup.alpha.detach(), "alpha").reshape({-1});
     TORCH_CHECK(alpha.numel() == n_rays, "alpha must be [n_rays]");
   }
-  // (the depth term's per-batch constants before the render, as in the call above)
+  // The per-batch constants of the depth term -- n_valid, counted on the device, and lambda_i /
+  // n_valid -- are enqueued BEFORE the render, where the host runs ahead of the GPU: the dense route
+  // reads one flag back per chunk, and small launches made between that read and the backward are on
+  // the critical path.  One column sum, one dot product and one addition remain after it.
   Tensor depth_n_valid, depth_coef;
+  LossOutputs want;
+  want.dist = want_dist;
+  want.opacity = want_opacity;
   if (want_depth) {
     torch::NoGradGuard no_grad;
-    const Tensor z = f2n::dev_f32(depth_target.detach(), "depth_target").reshape({-1});
+    const Tensor z = f2n::dev_f32(terms.depth_target.detach(), "depth_target").reshape({-1});
     depth_n_valid = z.gt(0.f)
                       .logical_and(z.lt(std::numeric_limits<float>::infinity()))
                       .sum()
                       .to(torch::kFloat32)
                       .clamp_min(1.f);
-    Tensor lambda = torch::empty({3}, z.options());
-    lambda.select(0, 0).fill_(depth_loss.empty);
-    lambda.select(0, 1).fill_(depth_loss.near);
-    lambda.select(0, 2).fill_(depth_loss.expected);
+    Tensor lambda = torch::empty({3}, z.options());  // (filled by launches: nothing is copied over)
+    lambda.select(0, 0).fill_(terms.depth.empty);
+    lambda.select(0, 1).fill_(terms.depth.near);
+    lambda.select(0, 2).fill_(terms.depth.expected);
     depth_coef = lambda / depth_n_valid;
+    want.depth_target = terms.depth_target;
+    want.depth_eps = terms.depth.eps;
   }
-  RenderResult res = renderer.render_for_loss(
-    rays_o, rays_d, emb_idx, RunningMode::TRAIN, noise, bg_color, want_dist,
-    want_depth ? depth_target : Tensor(), want_depth ? depth_loss.eps : 0.f, want_opacity);
+  RenderResult res =
+    renderer.render_for_loss(rays_o, rays_d, emb_idx, RunningMode::TRAIN, noise, bg_color, want);
   // the colour target the colour loss uses: a gt + (1 - a) bg when the alpha target composites
   // (formed where it is first needed, so that a step without the robust loss launches as before)
   Tensor target;
@@ -1478,106 +1341,74 @@ static f2n::TrainStepResult train_step_sup(
   // regularisers see.  From here on its weight m_r omega_r stands wherever the caller's m_r stood --
   // train_loss_sup, the opacity, distortion and depth terms: a rejected ray regularises nothing.  The
   // D-SSIM term keeps the caller's patch_weight: it scores a patch as a whole and is not trimmed.
-  Tensor robust_weight, robust_stats;
-  if (robust) {
+  TrainStepResult out;
+  if (want_robust) {
     torch::NoGradGuard no_grad;
-    RobustWeights rw = robust_weights(res.colors.detach(), colour_target(), m, *robust);
-    m = robust_weight = rw.weight;
-    robust_stats = rw.stats;
+    RobustWeights rw = robust_weights(res.colors.detach(), colour_target(), m, terms.robust);
+    m = out.robust_weight = rw.weight;
+    out.robust_stats = rw.stats;
   }
   Tensor var = res.weight_var.defined() ? res.weight_var
                                         : CustomOps::WeightVar(res.weights, res.idx_start_end);
-  if (var_loss_weight == 0.f) var = var.detach();
-  // {loss, colour, var, opacity term, weighted squared error, sum of the weights}: three launches
-  Tensor stats =
-    plain_target
-      ? f2n::train_loss_sup(
-          res.colors, gt_colors, var, Tensor(), m, Tensor(), Tensor(), var_loss_weight, 0.f)
-      : f2n::train_loss_sup(
-          res.colors, gt_colors, var, res.opacity, m, alpha,
-          alpha.defined() ? bg_color.detach() : Tensor(), var_loss_weight, sup.opacity_weight);
-  Tensor loss = stats[0];
-  // ... and the opacity term beside it, from the entry's own device scalar: W = sum m (1 when that
-  // is not positive), d = O - a where m != 0 and exactly 0 elsewhere (the term and the opacity's
-  // gradient of a masked ray are exact zeros), opac = sum m d^2 / W.  No host read.
-  Tensor opacity_term;
-  if (plain_target && want_opacity) {
-    Tensor d = res.opacity - alpha;
-    if (m.defined()) d = d.masked_fill(m.eq(0.f), 0.f);
-    const Tensor sq = d * d;
-    const Tensor sum_m = stats[5].detach();
-    const Tensor W = torch::where(sum_m.gt(0.f), sum_m, torch::ones_like(sum_m));
-    opacity_term = (m.defined() ? m * sq : sq).sum() / W;
-    loss = loss + sup.opacity_weight * opacity_term;
+  // (a zero weight -- the reference's schedule starts there, train_manager.cpp:85-91 -- makes the
+  // variance term's gradient exactly zero: its backward kernel is not run at all)
+  if (terms.var_weight == 0.f) var = var.detach();
+  Tensor loss, opacity_term;
+  if (!weighted) {
+    // colour loss + variance loss + squared error in two launches (f2n_loss_fwd; the ATen spelling of
+    // the reference, train_manager.cpp:78-96, is ~23 launches of a few microseconds each)
+    const Tensor stats = f2n::train_loss(res.colors, gt_colors, var, terms.var_weight);
+    loss = stats[0];  // {loss, colour, var, sq}
+    out.sq_err_sum = stats[3].detach();
+  } else {
+    // {loss, colour, var, opacity term, weighted squared error, sum of the weights}: three launches
+    const Tensor stats =
+      plain_target
+        ? f2n::train_loss_sup(
+            res.colors, gt_colors, var, Tensor(), m, Tensor(), Tensor(), terms.var_weight, 0.f)
+        : f2n::train_loss_sup(
+            res.colors, gt_colors, var, res.opacity, m, alpha,
+            alpha.defined() ? bg_color.detach() : Tensor(), terms.var_weight, sup.opacity_weight);
+    loss = stats[0];
+    out.sq_err_sum = stats[4].detach();
+    out.weight_sum = stats[5].detach();
+    if (want_opacity && !plain_target) opacity_term = stats[3];
+    // ... or the opacity term beside it, from the entry's own device scalar: W = sum m (1 when that
+    // is not positive), d = O - a where m != 0 and exactly 0 elsewhere (the term and the opacity's
+    // gradient of a masked ray are exact zeros), opac = sum m d^2 / W.  No host read.
+    if (want_opacity && plain_target) {
+      Tensor d = res.opacity - alpha;
+      if (m.defined()) d = d.masked_fill(m.eq(0.f), 0.f);
+      const Tensor sq = d * d;
+      const Tensor W = torch::where(
+        out.weight_sum.gt(0.f), out.weight_sum, torch::ones_like(out.weight_sum));
+      opacity_term = (m.defined() ? m * sq : sq).sum() / W;
+      loss = loss + sup.opacity_weight * opacity_term;
+    }
   }
+  renderer.last_opacity_loss_ = opacity_term.defined() ? opacity_term.detach() : Tensor();
   // the regularisers: a masked ray takes no part in them either (the per-ray terms are weighted
   // before their reductions, which keep their divisors)
   renderer.last_dist_loss_ = Tensor();
   if (want_dist && res.weight_dist.numel() > 0) {
     Tensor dist_loss = (m.defined() ? res.weight_dist * m : res.weight_dist).mean();
-    loss = loss + dist_loss_weight * dist_loss;
+    loss = loss + terms.dist_weight * dist_loss;
     renderer.last_dist_loss_ = dist_loss.detach();
   }
   renderer.last_depth_loss_ = Tensor();
   if (want_depth && res.depth_terms.numel() > 0) {
+    // invalid rays hold exact zeros: the sum over all rays is the sum over the valid ones
     const Tensor sums = (m.defined() ? res.depth_terms * m.unsqueeze(1) : res.depth_terms).sum(0);
     loss = loss + torch::dot(sums, depth_coef);
     renderer.last_depth_loss_ = sums.detach() / depth_n_valid;
   }
-  renderer.last_opacity_loss_ = !want_opacity  ? Tensor()
-                                : plain_target ? opacity_term.detach()
-                                               : stats[3].detach();
   renderer.last_ssim_loss_ = Tensor();
-  if (patch) loss = add_patch_term(renderer, loss, res.colors, colour_target(), *patch);
-  TrainStepResult out;
-  out.robust_weight = robust_weight;
-  out.robust_stats = robust_stats;
+  if (terms.patch.active())
+    loss = add_patch_term(renderer, loss, res.colors, colour_target(), terms.patch);
   out.loss = loss.detach();
-  out.sq_err_sum = stats[4].detach();
   out.n_values = res.colors.numel();
   out.n_samples = renderer.last_n_samples_;
-  out.weight_sum = stats[5].detach();
   if (sup.want_colors) out.colors = res.colors.detach();
   if (run_backward && loss.requires_grad()) loss.backward();
   return out;
-}
-
-f2n::TrainStepResult f2n::train_step(
-  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
-  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
-  const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
-  const DepthLossOptions & depth_loss, const RaySupervision & sup)
-{
-  return train_step_sup(
-    renderer, rays_o, rays_d, emb_idx, gt_colors, var_loss_weight, dist_loss_weight, noise, bg_color,
-    run_backward, depth_target, depth_loss, sup, nullptr);
-}
-
-f2n::TrainStepResult f2n::train_step(
-  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
-  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
-  const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
-  const DepthLossOptions & depth_loss, const RaySupervision & sup, const PatchLoss & patch)
-{
-  // (no patch term: the call without it, launch for launch -- the rule for dist_loss_weight == 0)
-  const bool want_ssim = patch.patch != 0 && patch.ssim_weight != 0.f;
-  return train_step_sup(
-    renderer, rays_o, rays_d, emb_idx, gt_colors, var_loss_weight, dist_loss_weight, noise, bg_color,
-    run_backward, depth_target, depth_loss, sup, want_ssim ? &patch : nullptr);
-}
-
-f2n::TrainStepResult f2n::train_step(
-  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
-  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
-  const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
-  const DepthLossOptions & depth_loss, const RaySupervision & sup, const PatchLoss & patch,
-  const RobustLoss & robust)
-{
-  const bool want_ssim = patch.patch != 0 && patch.ssim_weight != 0.f;
-  // (quantile >= 1: the call without it, launch for launch -- the rule for dist_loss_weight == 0)
-  const bool want_robust = !(robust.quantile >= 1.f);
-  return train_step_sup(
-    renderer, rays_o, rays_d, emb_idx, gt_colors, var_loss_weight, dist_loss_weight, noise, bg_color,
-    run_backward, depth_target, depth_loss, sup, want_ssim ? &patch : nullptr,
-    want_robust ? &robust : nullptr);
 }

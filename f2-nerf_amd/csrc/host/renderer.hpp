@@ -24,6 +24,10 @@
 // unoccupied cell counts as exactly zero and those samples are dropped: the march skips them
 // (f2n_density_march_occ / f2n_sample_compact_occ), op-by-op masks them, the dense route is not
 // taken (it encodes everything, which is the cost the grid removes).
+//
+// A loss asks for more than colours through one struct each: Renderer::render_for_loss takes a
+// LossOutputs (the per-ray extras every route can hand back), f2n::train_step a LossTerms (the terms
+// of the loss).  A field left at its default changes no launch and no bit.
 #pragma once
 
 #include <memory>
@@ -72,8 +76,8 @@ struct RenderResult
   // Renderer::render_for_loss only, and only when it says so: CustomOps::WeightVar of the weights,
   // [n_rays] in the caller's order; `weights` is then undefined
   Tensor weight_var;
-  // Renderer::render_for_loss with want_dist only: CustomOps::WeightDist of the kept samples'
-  // weights, t and dt, [n_rays] in the caller's order, on every route; undefined otherwise
+  // Renderer::render_for_loss with LossOutputs::dist only: CustomOps::WeightDist of the kept
+  // samples' weights, t and dt, [n_rays] in the caller's order, on every route; undefined otherwise
   Tensor weight_dist;
   // Renderer::render_for_loss with a depth target only: CustomOps::DepthSight of the kept samples'
   // weights, t and dt against that target, [n_rays, 3] = (empty space, near surface, expected depth)
@@ -82,10 +86,31 @@ struct RenderResult
   // RendererOptions::normals only: N_r = sum_k w_k n^_k over the kept samples (f2n_ray_normals),
   // [n_rays, 3] in the caller's order, detached, not renormalised; undefined when the option is off
   Tensor normals;
-  // Renderer::render_for_loss with want_opacity only: FlexOps::Sum of the kept samples' weights,
-  // [n_rays] in the caller's order, on every route (1 - the transmittance left behind the last kept
-  // sample, to rounding), with the gradient going to the weights; undefined otherwise
+  // Renderer::render_for_loss with LossOutputs::opacity only: FlexOps::Sum of the kept samples'
+  // weights, [n_rays] in the caller's order, on every route (1 - the transmittance left behind the
+  // last kept sample, to rounding), with the gradient going to the weights; undefined otherwise
   Tensor opacity;
+};
+
+// What Renderer::render_for_loss hands back beside colours, depths, weights and bounds.  Every field
+// works on every route (op by op, march, dense, lean bucketed, with an occupancy grid attached): the
+// term is taken where the kept samples' weights, t and dt lie, and on the bucketed routes its per-ray
+// result rides back to the caller's order with colours and depths -- nothing per-sample is gathered
+// for it.  A field left off launches nothing, and colours, depths, weights and bounds keep their bits
+// whatever is asked for.
+struct LossOutputs
+{
+  // RenderResult::weight_dist, the per-ray distortion loss.  t and dt get no gradient (sample
+  // positions are data on every training route).
+  bool dist = false;
+  // defined: RenderResult::depth_terms against it.  [n_rays], each ray's target distance along the
+  // ray, in the units of the rays (0, negative or non-finite: the ray has no return); on the bucketed
+  // routes it is permuted with the rays.  It receives no gradient.
+  torch::Tensor depth_target;
+  float depth_eps = 0.f;  // >= 0: the half-width of the surface band around the target
+  // RenderResult::opacity, O_r = sum_k w_k over the ray's kept samples (what an alpha target is
+  // compared with), taken with f2n_seg_sum_fwd; the gradient goes to the weights.
+  bool opacity = false;
 };
 
 struct RendererOptions
@@ -175,38 +200,10 @@ public:
   // on the lean bucketed dense route the variance is taken from the weights where they lie and its
   // [n_rays] result travels back to the caller's order with colours and depths -- no [n, S] gather
   // either way.  There `weight_var` is defined and `weights` is not; everywhere else this is
-  // render() and `weight_var` is undefined.
+  // render() and `weight_var` is undefined.  `want` adds the per-ray extras of LossOutputs.
   RenderResult render_for_loss(
     const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-    const Tensor & noise, const Tensor & bg_color);
-  // ... and, with want_dist, for their per-ray distortion loss as well: `weight_dist` is defined on
-  // every route (op by op, march, dense, lean bucketed, with an occupancy grid attached), taken where
-  // the kept samples' weights, t and dt lie; on the bucketed routes its [n_rays] result rides back
-  // with colours and depths, nothing per-sample is gathered for it.  t and dt get no gradient (sample
-  // positions are data on every training route).  Everything else is what the call above returns.
-  RenderResult render_for_loss(
-    const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-    const Tensor & noise, const Tensor & bg_color, bool want_dist);
-  // ... and, with a depth target, for their line-of-sight depth terms: `depth_target` [n_rays] is each
-  // ray's target distance along the ray, in the units of the rays (0, negative or non-finite: the ray
-  // has no return), `depth_eps` >= 0 the half-width of the surface band.  `depth_terms` [n_rays, 3] is
-  // defined on every route want_dist works on, taken where the kept samples' weights, t and dt lie; on
-  // the bucketed routes the target is permuted with the rays and the result rides back with colours
-  // and depths, nothing per-sample is gathered.  The target receives no gradient.  An undefined target
-  // makes this the call above exactly; colours, depths, weights and bounds keep their bits either way.
-  RenderResult render_for_loss(
-    const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-    const Tensor & noise, const Tensor & bg_color, bool want_dist, const Tensor & depth_target,
-    float depth_eps);
-  // ... and, with want_opacity, for each ray's opacity O_r = sum_k w_k over its kept samples (what an
-  // alpha target is compared with): `opacity` [n_rays] is defined on every route want_dist works on,
-  // taken with f2n_seg_sum_fwd where the weights lie; on the bucketed routes its [n_rays] result rides
-  // back with colours and depths.  The gradient goes to the weights.  Without want_opacity this is the
-  // call above exactly; colours, depths, weights and bounds keep their bits either way.
-  RenderResult render_for_loss(
-    const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-    const Tensor & noise, const Tensor & bg_color, bool want_dist, const Tensor & depth_target,
-    float depth_eps, bool want_opacity);
+    const Tensor & noise, const Tensor & bg_color, const LossOutputs & want = {});
 
   // The no-grad render as one kernel launch (f2n_render_rays): colours [n, 3], depths [n], last_trans
   // [n] (1 - opacity of the ray: an alpha mask) and kept [n] int32 (samples composited per ray).
@@ -326,12 +323,9 @@ private:
     bool lean = false;
     bool noise_raw = false;  // lean: the noise is the renderer's own uniform draw, cooked in the sampler
     bool want_var = false;   // lean and bucketed, render_for_loss: hand back weight_var, not weights
-    bool want_dist = false;  // render_for_loss: hand back weight_dist too
-    // render_for_loss with a depth target: [n_rays] f32 in the order of the rays the route renders
-    // (render_dense_bucketed permutes it with them), else undefined; hand back depth_terms too
-    Tensor depth_target;
-    float depth_eps = 0.f;
-    bool want_opacity = false;  // render_for_loss: hand back opacity too
+    // render_for_loss: the extras to hand back.  want.depth_target is [n_rays] f32 in the order of the
+    // rays the route renders (render_dense_bucketed permutes it with them), else undefined
+    LossOutputs want;
   };
   // What the shading pass hands to compositing: the field head's output ([n, 1] density logit of the
   // fused network, [n, 16] otherwise) and the colours [n, 3].
@@ -343,8 +337,7 @@ private:
   Route choose_route(const Tensor & rays_o, const Tensor & rays_d, const Tensor & bg_color) const;
   RenderResult render_routed(
     const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx, RunningMode mode,
-    const Tensor & noise, const Tensor & bg_color, bool for_loss, bool want_dist,
-    const Tensor & depth_target = Tensor(), float depth_eps = 0.f, bool want_opacity = false);
+    const Tensor & noise, const Tensor & bg_color, bool for_loss, const LossOutputs & want);
   bool fused_net_applies() const;
   // f2n_render_rays -- or, by options_.one_pass_head, the head or head + tail -- into preallocated
   // outputs (rows of one chunk)
@@ -396,6 +389,10 @@ private:
     const SampleResultFlex & kept, const Tensor & emb_idx, RunningMode mode,
     const Tensor & bg_color, const Route & route, const Tensor & enc_cm = Tensor(),
     const Tensor & contracted = Tensor(), bool final = true);
+  // RenderResult::weight_dist, depth_terms and opacity of the kept samples' weights, as route.want
+  // asks: what render_op_by_op and composite share
+  void per_ray_terms(
+    RenderResult & res, const Tensor & weights, const SampleResultFlex & kept, const Route & route);
   // RenderResult::normals of the kept samples (raw positions) and their weights: one launch of
   // f2n_ray_normals, nothing recorded by autograd
   Tensor ray_normals(const SampleResultFlex & kept, const Tensor & weights);
@@ -451,21 +448,6 @@ struct CoarseToFine
 // f2n_level_weights as a CPU tensor [L] and its number of active levels.
 std::pair<Tensor, int64_t> level_weights(double alpha, int64_t L);
 
-TrainStepResult train_step(
-  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
-  const Tensor & gt_colors, float var_loss_weight, const Tensor & noise, const Tensor & bg_color,
-  bool run_backward);
-
-// ... with the distortion loss: loss = colour + var_loss_weight * var_loss + dist_loss_weight *
-// mean_r D_r (CustomOps::WeightDist; the mean is left in Renderer::last_dist_loss_).  A weight of
-// exactly 0 is the call above, launch for launch and bit for bit: the term is neither computed nor
-// differentiated, as for var_loss_weight == 0.  The schedule stays with the caller, like the
-// reference's variance-loss ramp (src/main_functions/train_manager.cpp:85-91).
-TrainStepResult train_step(
-  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
-  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
-  const Tensor & bg_color, bool run_backward);
-
 // Weights of the three line-of-sight depth terms (CustomOps::DepthSight) and the half-width of the
 // surface band.  All three weights exactly 0: no depth term.  The schedule (URF shrinks eps while
 // training) stays with the caller.
@@ -475,19 +457,8 @@ struct DepthLossOptions
   float near = 0.f;      // lambda of N_r: weight missing from the band around the return
   float expected = 0.f;  // lambda of X_r: squared error of the expected depth
   float eps = 0.f;       // half-width of the band, in the units of the rays
+  bool active() const { return empty != 0.f || near != 0.f || expected != 0.f; }
 };
-
-// ... with depth supervision: `depth_target` [n_rays] as in Renderer::render_for_loss, and
-//   loss += sum_i lambda_i * (sum over valid rays of term_i) / max(n_valid, 1),
-// n_valid counted on the device (no host read); the three means are left in
-// Renderer::last_depth_loss_.  An undefined target, or all three weights exactly 0, is the call above,
-// launch for launch and bit for bit: the term is neither computed nor differentiated -- the rule for
-// dist_loss_weight == 0.
-TrainStepResult train_step(
-  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
-  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
-  const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
-  const DepthLossOptions & depth_loss);
 
 // Per-ray supervision of a masked batch (f2n::sample_masked_rays makes one).  Both tensors undefined:
 // no supervision.
@@ -504,28 +475,9 @@ struct RaySupervision
   // term -- what a learned background (Renderer::set_background) needs, or its texture never sees
   // the image; bg_color may then be left undefined.
   bool composite_target = true;
+  bool weighted() const { return ray_weight.defined() || alpha.defined(); }
+  bool want_opacity() const { return alpha.defined() && opacity_weight != 0.f; }
 };
-
-// ... with masked rays and alpha targets (f2n::train_loss_sup).  The colour target of a ray becomes
-// a gt + (1 - a) bg with the background colour the render blended in -- bg_color, which is then
-// required -- both means divide by W = sum_r m_r (1 when that is not positive; no host read), and
-//   loss = colour + var_loss_weight * var + opacity_weight * sum_r m_r (O_r - a_r)^2 / W
-// with O_r the ray's rendered opacity (RenderResult::opacity; its mean term is left in
-// Renderer::last_opacity_loss_).  The distortion and depth terms are weighted by m_r as well, before
-// their reductions, which keep their divisors (n_rays, n_valid): a masked ray regularises nothing.
-// sq_err_sum is the weighted sum, weight_sum is sum_r m_r.  With ray_weight and alpha both undefined
-// this is the call above, launch for launch and bit for bit, whatever opacity_weight says
-// (want_colors then still fills TrainStepResult::colors, which costs no launch).
-// With composite_target = false the colour and variance terms are f2n_loss_sup_fwd's without alpha
-// (gt' = gt), and the opacity term is formed in ATen from that entry's device scalar W:
-//   d = O - a on the rays with m != 0, else 0;  opac = sum_r m_r d_r^2 / W;  loss += opacity_weight opac
-// -- no host read, last_opacity_loss_ filled, a ray with m_r = 0 contributes exact zeros to the term
-// and to the opacity's gradient.
-TrainStepResult train_step(
-  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
-  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
-  const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
-  const DepthLossOptions & depth_loss, const RaySupervision & sup);
 
 // A structural term on patches (f2n::sample_patch_rays makes such a batch; CustomOps::Ssim).
 // patch == 0 or ssim_weight == 0: no term.
@@ -534,38 +486,71 @@ struct PatchLoss
   int patch = 0;             // P: the rays are n_patches * P^2, patch-major, row-major in a patch
   float ssim_weight = 0.f;   // lambda of sum_b m_b (1 - SSIM_b) / M
   Tensor patch_weight;       // [n_patches] m_b: 0 drops the patch; undefined = 1
+  bool active() const { return patch != 0 && ssim_weight != 0.f; }
 };
 
-// ... with a D-SSIM term on patches:
-//   loss += ssim_weight * sum_b m_b (1 - SSIM_b) / M,  M = sum_b m_b (1 when that is not positive;
-// no host read), SSIM_b the unclamped SSIM of the render's colours viewed as [n_patches, P, P, 3]
-// against the colour target the colour loss used (a gt + (1 - a) bg where the alpha target
-// composites).  The gradient reaches the colours through CustomOps::Ssim as the distortion term's
-// reaches the weights; a patch with m_b = 0 contributes exact zeros.  The unweighted mean of
-// 1 - SSIM_b is left in Renderer::last_ssim_loss_.  A ray count that is no multiple of P^2, P < 11
-// or a patch_weight of another length throws.  patch == 0 or ssim_weight == 0 is the call above,
-// launch for launch and bit for bit.
-TrainStepResult train_step(
-  Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
-  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
-  const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
-  const DepthLossOptions & depth_loss, const RaySupervision & sup, const PatchLoss & patch);
+// The terms of f2n::train_step's loss beside the colour loss.  Each is off at its default, and a term
+// that is off is neither computed nor differentiated: the step is then the one without it, launch for
+// launch and bit for bit.  The schedules stay with the caller, like the reference's variance-loss
+// ramp (src/main_functions/train_manager.cpp:85-91).
+struct LossTerms
+{
+  float var_weight = 0.f;  // lambda of the weight-variance loss; 0: its backward kernel is not run
+  // The distortion loss: loss += dist_weight * mean_r D_r (CustomOps::WeightDist; the mean is left in
+  // Renderer::last_dist_loss_).  Exactly 0: off.
+  float dist_weight = 0.f;
+  // Depth supervision: `depth_target` [n_rays] as in LossOutputs, and
+  //   loss += sum_i lambda_i * (sum over valid rays of term_i) / max(n_valid, 1),
+  // n_valid counted on the device (no host read); the three means are left in
+  // Renderer::last_depth_loss_.  An undefined target, or all three weights exactly 0: off.
+  Tensor depth_target;
+  DepthLossOptions depth;
+  // Masked rays and alpha targets (f2n::train_loss_sup).  The colour target of a ray becomes
+  // a gt + (1 - a) bg with the background colour the render blended in -- bg_color, which is then
+  // required -- both means divide by W = sum_r m_r (1 when that is not positive; no host read), and
+  //   loss = colour + var_weight * var + opacity_weight * sum_r m_r (O_r - a_r)^2 / W
+  // with O_r the ray's rendered opacity (RenderResult::opacity; its mean term is left in
+  // Renderer::last_opacity_loss_).  The distortion and depth terms are weighted by m_r as well, before
+  // their reductions, which keep their divisors (n_rays, n_valid): a masked ray regularises nothing.
+  // sq_err_sum is the weighted sum, weight_sum is sum_r m_r.  With ray_weight and alpha both undefined:
+  // off, whatever opacity_weight says (want_colors then still fills TrainStepResult::colors, which
+  // costs no launch).
+  // With composite_target = false the colour and variance terms are f2n_loss_sup_fwd's without alpha
+  // (gt' = gt), and the opacity term is formed in ATen from that entry's device scalar W:
+  //   d = O - a on the rays with m != 0, else 0;  opac = sum_r m_r d_r^2 / W;  loss += opacity_weight opac
+  // -- no host read, last_opacity_loss_ filled, a ray with m_r = 0 contributes exact zeros to the term
+  // and to the opacity's gradient.
+  RaySupervision sup;
+  // A D-SSIM term on patches:
+  //   loss += ssim_weight * sum_b m_b (1 - SSIM_b) / M,  M = sum_b m_b (1 when that is not positive;
+  // no host read), SSIM_b the unclamped SSIM of the render's colours viewed as [n_patches, P, P, 3]
+  // against the colour target the colour loss used (a gt + (1 - a) bg where the alpha target
+  // composites).  The gradient reaches the colours through CustomOps::Ssim as the distortion term's
+  // reaches the weights; a patch with m_b = 0 contributes exact zeros.  The unweighted mean of
+  // 1 - SSIM_b is left in Renderer::last_ssim_loss_.  A ray count that is no multiple of P^2, P < 11
+  // or a patch_weight of another length throws.  patch == 0 or ssim_weight == 0: off.
+  PatchLoss patch;
+  // A trimmed colour loss (robust_loss.hpp; f2n_robust_weights has the rule).  After the render, under
+  // no-grad, the render's own detached colours and the colour target the colour loss uses (a gt +
+  // (1 - a) bg where the alpha target composites) give per-ray weights m_r omega_r, and those stand
+  // wherever m_r stands above: f2n::train_loss_sup and the opacity, distortion and depth terms -- a
+  // rejected ray contributes exact zeros and regularises nothing.  The D-SSIM term keeps the caller's
+  // patch_weight.  The weighted loss entry runs also when the caller gave neither ray_weight nor
+  // alpha.  robust.patch is the P of the rule (0: scattered rays) and need not be PatchLoss::patch.
+  // TrainStepResult::robust_weight and robust_stats are filled; no host read.  quantile >= 1: off.
+  RobustLoss robust;
 
-// ... with a trimmed colour loss (robust_loss.hpp; f2n_robust_weights has the rule).  After the
-// render, under no-grad, the render's own detached colours and the colour target the colour loss uses
-// (a gt + (1 - a) bg where the alpha target composites) give per-ray weights m_r omega_r, and those
-// stand wherever m_r stands in the call above: f2n::train_loss_sup and the opacity, distortion and
-// depth terms -- a rejected ray contributes exact zeros and regularises nothing.  The D-SSIM term
-// keeps the caller's patch_weight.  The body of the supervised step runs also when the caller gave
-// neither ray_weight nor alpha.  robust.patch is the P of the rule (0: scattered rays) and need not be
-// PatchLoss::patch.  TrainStepResult::robust_weight and robust_stats are filled; no host read.
-// quantile >= 1 is the call above, launch for launch and bit for bit -- the rule for
-// dist_loss_weight == 0.
+  bool want_dist() const { return dist_weight != 0.f; }
+  bool want_depth() const { return depth_target.defined() && depth.active(); }
+  // per-ray weights exist: the step goes through f2n::train_loss_sup, not f2n::train_loss
+  bool weighted() const { return robust.active() || sup.weighted(); }
+};
+
+// One training step: render(TRAIN), the colour loss and the terms of `terms`, backward().  `noise` and
+// `bg_color` as in Renderer::render.
 TrainStepResult train_step(
   Renderer & renderer, const Tensor & rays_o, const Tensor & rays_d, const Tensor & emb_idx,
-  const Tensor & gt_colors, float var_loss_weight, float dist_loss_weight, const Tensor & noise,
-  const Tensor & bg_color, bool run_backward, const Tensor & depth_target,
-  const DepthLossOptions & depth_loss, const RaySupervision & sup, const PatchLoss & patch,
-  const RobustLoss & robust);
+  const Tensor & gt_colors, const LossTerms & terms = {}, const Tensor & noise = {},
+  const Tensor & bg_color = {}, bool run_backward = true);
 
 }  // namespace f2n

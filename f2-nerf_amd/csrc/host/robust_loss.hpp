@@ -20,6 +20,7 @@ struct RobustLoss
   float nbhd_thresh = .6f;  // step 6: the share of restored pixels that restores a whole block
   int patch = 0;            // P: the rays are n_patches * P^2, patch-major; 0: scattered rays
   int nbhd = 8;             // the side of a block; clamped to P
+  bool active() const { return !(quantile >= 1.f); }
 };
 
 struct RobustWeights
